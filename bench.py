@@ -19,6 +19,12 @@ rank, no collective on the data path; `gloo` only carries the barrier and the
 max-reduction of the timings ("scaling": "weak").
 
 Weights are synthetic (no checkpoints offline) with the exact GGUF layout.
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(`--dump-outputs DIR` also writes the last timed step's codes and frame counts as
+DIR/*.npy). `--full` adds everything else the line can carry, each measured after
+the timed steps in runs of its own: the weak-scaling baseline, the codec, the op
+table and roofline, the CPU baseline and the other BASELINE configs.
 """
 from __future__ import annotations
 
@@ -240,6 +246,12 @@ def main() -> None:
                     help="utterances per GPU (default: configs[1]'s 1 at N=1, configs[3]'s 8 at N>1)")
     ap.add_argument("--frames", type=int, default=FRAMES)
     ap.add_argument("--tokens", type=int, default=TEXT_TOKENS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the result line can carry: the "
+                         "weak-scaling baseline, the codec, the op table / roofline, the CPU baseline and the "
+                         "other BASELINE configs (a plain run times the headline decode only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (codes, n_frames) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=4,
                     help="oracle threads for cpu_baseline (ggml's default n_threads, magpie.h:298,306)")
@@ -254,6 +266,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
     rank = int(os.environ.get("RANK", "0"))
@@ -280,8 +294,10 @@ def main() -> None:
         # one write(2) per line: the ranks share the launcher's stdout pipe
         os.write(1, (json.dumps({"rank": rank, "local_rank": local, "world": world, "ranks_seen": seen,
                                  "weights": args.weights, "batch_per_gpu": args.batch,
+                                 "full": args.full,
                                  "scaling_baseline": {"weights": "bf16", "batch_per_gpu": SCALE_BATCH,
-                                                      "measured": "rank 0 alone" if world > 1 else "after the headline"}})
+                                                      "measured": "rank 0 alone" if world > 1 else "after the headline"}
+                                 if args.full else None})
                      + "\n").encode())
         return
     # one rank per GPU; with fewer GPUs than ranks (a rehearsal) ranks share devices
@@ -330,7 +346,7 @@ def main() -> None:
     # run on this node: rank 0 decodes its share alone (the other ranks wait at the
     # barrier, their GPUs idle), then every rank decodes together
     solo = None
-    if dist is not None:
+    if dist is not None and args.full:
         barrier()
         if rank == 0:
             s_el, _, s_fr, _ = timed_decodes()
@@ -357,17 +373,20 @@ def main() -> None:
     value = total_frames / t_max
     ms_per_step = 1e3 * t_max / args.steps
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rr, "" if world == 1 else f"_rank{rank}")
+
     # ---- weak-scaling baseline: configs[3]'s per-GPU share (bf16, 8 utterances per GPU)
     # on ONE GPU. At N > 1 that is the workload itself, timed on rank 0 alone above;
     # at N = 1 (configs[1], f32 batch 1) it is timed here, after the headline decode, so a
     # SCALE series divides like by like: efficiency(N) = value(N) / (N x this value).
     scaling = None
     sb_desc = f"Magpie-357M bf16, batch={SCALE_BATCH}/GPU, {args.frames} frames/utterance, T={args.tokens} (configs[3] per-GPU share), one GPU"
-    if dist is not None:
+    if dist is not None and args.full:
         scaling = {"workload": sb_desc if (args.weights, B) == ("bf16", SCALE_BATCH) else
                    f"this line's workload on one GPU", "value": round(solo, 2) if solo else None,
                    "unit": "frames/s", "measured": "rank 0 alone in this run (other ranks idle at a barrier)"}
-    elif rank == 0:
+    elif rank == 0 and args.full:
         if (args.weights, B) == ("bf16", SCALE_BATCH):
             sval = value
         else:
@@ -387,7 +406,7 @@ def main() -> None:
     # ---- nano-codec on the device: every utterance's 256 frames as 32-frame chunks
     codec = None
     codec_path = os.path.join(cache, "nano_codec.gguf")
-    if not args.no_codec:
+    if args.full and not args.no_codec:
         if rank == 0 or world == 1:
             ma.synth_gguf(codec_path, kind="codec")
         if dist is not None:
@@ -449,7 +468,7 @@ def main() -> None:
     # event pair around the launch (event_pair_us, mp_hip_profile_ops).
     roofline = None
     op_table = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         dev.synthesize(toks, speakers=speakers, max_dec_steps=args.frames // 2, ignore_eos=True)
         names = dev.ops()
         kev = dev.profile_ops_kev(iters=args.profile_ops)
@@ -503,7 +522,7 @@ def main() -> None:
 
     # ---- CPU baseline: the oracle (C restatement, f32 accumulation) on the host cores
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, REPO)
         from oracle import oracle as orc  # cpu_baseline leg only
         res = orc.time_decode_fps(model_path, toks[0], args.frames, threads=args.cpu_threads, acc64=False)
@@ -532,7 +551,7 @@ def main() -> None:
 
     # ---- the other BASELINE configs' shapes on this GPU (rank 0 at N=1 only)
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         extra = measure_extra(model_path, codec_path if not args.no_codec else None, args)
 
     if rank == 0:
@@ -546,6 +565,7 @@ def main() -> None:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True,
             "scaling": "weak",
@@ -579,6 +599,19 @@ def main() -> None:
     dev.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir: str, res, suffix: str = "") -> None:
+    """What a caller of the timed path (Device.decode) receives, from the last timed step:
+    codes<suffix>.npy [B][frames][8] (codebook ids, exact in float32; rows past an
+    utterance's n_frames are -1) and n_frames<suffix>.npy [B]. The prompts, speakers and
+    weights are seeded, so the same arguments give the same inputs in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    codes = np.full((len(res.codes), int(max(res.n_frames.max(), 1)), 8), -1.0, np.float32)
+    for b, c in enumerate(res.codes):
+        codes[b, :len(c)] = c
+    np.save(os.path.join(out_dir, f"codes{suffix}.npy"), codes)
+    np.save(os.path.join(out_dir, f"n_frames{suffix}.npy"), res.n_frames.astype(np.float32))
 
 
 def cpu_model_name() -> str:

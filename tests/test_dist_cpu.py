@@ -153,7 +153,7 @@ def test_bench_gpus_2_spawns_two_ranks():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--dry-run"], env=env,
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--dry-run", "--full"], env=env,
                          capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [json.loads(x) for x in out.stdout.splitlines() if x.startswith("{")]
@@ -173,7 +173,7 @@ def test_bench_n1_dry_run_names_the_scaling_baseline():
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--dry-run"], env=env,
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--dry-run", "--full"], env=env,
                          capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
     x = json.loads(out.stdout.strip().splitlines()[-1])

@@ -238,6 +238,21 @@ def test_bench_bytes_per_frame_matches_survey():
     assert abs(bench.decoder_bytes_per_frame(1, 238.5, 64) / 1e6 - 388.4) < 0.5
 
 
+def test_bench_dump_outputs_writes_float32_arrays(tmp_path):
+    """--dump-outputs: the decode result's codes (ragged, padded with -1) and n_frames as float32 .npy."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(0)
+    codes = [rng.integers(0, 2016, (n, 8)).astype(np.int32) for n in (5, 3)]
+    res = bench.ma.SynthResult(codes, np.array([5, 3], np.int32), 0.0, 0.0, 5)
+    bench.dump_outputs(str(tmp_path / "out"), res)
+    c, n = np.load(tmp_path / "out" / "codes.npy"), np.load(tmp_path / "out" / "n_frames.npy")
+    assert c.dtype == np.float32 and c.shape == (2, 5, 8) and n.dtype == np.float32 and n.tolist() == [5.0, 3.0]
+    assert np.array_equal(c[0], codes[0]) and np.array_equal(c[1, :3], codes[1]) and (c[1, 3:] == -1).all()
+
+
 def _gfx950_code_objects(so_path, tmp_path):
     """Every gfx950 code object in a HIP shared library: the .hip_fatbin section is a
     run of clang offload bundles (one per translation unit), each '__CLANG_OFFLOAD_

@@ -6,7 +6,7 @@
 # usage: tools_dev/gpu_session.sh TAG STEP [STEP ...]
 #   tests[=LIB]          pytest -m gpu (LIB: an ab_libs/NAME.so to load instead)
 #   tests?[=LIB]         the same, but a test failure (pytest rc 1) does not stop the chain
-#   bench                the default bench.py line -> TAG_bench.json
+#   bench                the bench.py --full line -> TAG_bench.json
 #   ab=N:LIB[,LIB...]    alternating bench A/B: default library vs each ab_libs/LIB.so, N rounds
 #   ops=MODE:B[:LIB[:K=V]]  per-op dispatch intervals + wave spans (tools_dev/mode_ops.py);
 #                        LIB "-" = the default library; K=V e.g. MODE_XA=direct, MODE_KV=bf16
@@ -38,7 +38,7 @@ for STEP in "$@"; do
         if [ "$name" = "tests?" ] && [ $rc -eq 1 ]; then echo "tests failed (continuing)"; else echo "tests rc=$rc"; exit $rc; fi
       fi ;;
     bench)
-      timeout -k 10 300 python -u bench.py > "$OUT/${TAG}_bench.log" 2>&1
+      timeout -k 10 300 python -u bench.py --full > "$OUT/${TAG}_bench.log" 2>&1
       tail -1 "$OUT/${TAG}_bench.log" > "$OUT/${TAG}_bench.json"
       echo "bench ok" ;;
     ab)
@@ -64,7 +64,7 @@ for STEP in "$@"; do
       # arg (optional): K=V set for the profiled run, e.g. prof=MAGPIE_STREAM_PRIO=0
       d="$OUT/${TAG}_prof${arg:+_${arg//=/-}}"
       env MAGPIE_EAGER=1 $arg timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$d" -o prof \
-        -- python3 -u bench.py --no-cpu-baseline --no-extra > "$d.bench.log" 2>&1
+        -- python3 -u bench.py --full --no-cpu-baseline --no-extra > "$d.bench.log" 2>&1
       python3 tools_dev/prof_phase.py "$d/prof_kernel_trace.csv" "$d/phase_kernel_stats.csv" > "$d.phase.log"
       echo "rocprof ${arg:-default}: $(head -1 "$d.phase.log")" ;;
     pmc)
