@@ -1417,10 +1417,6 @@ struct mp_codec {
     int *codes = nullptr;
     size_t codes_cap = 0, audio_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // background decodes (mp_codec_set_background): a second stream confined to a share of the
-    // CUs (hipExtStreamCreateWithCUMask), for codec rounds that run beside a decode in flight
-    hipStream_t bg_stream = nullptr;
-    int bg = 0, bg_cus = 0;
     // pinned host staging of the codes in / audio out: a copy from or to pageable memory is
     // staged synchronously by the runtime and waited for the decode's queued work too
     // (configs[2]: each overlapped round's codec finished only after the decode's next chunk)
@@ -1626,8 +1622,7 @@ hipError_t launch_rb(mpc::RbP p, int nchunk, hipStream_t s) {
 }
 // the fused residual block for a stage's padded channel count (0: not fused)
 bool rb_fused(int Cp) {
-    const char *unf = getenv("MAGPIE_CODEC_UNFUSED");
-    const bool off = unf && atoi(unf) != 0;  // A/B switch (read per decode): the two-launch blocks
+    const bool off = mp::env_int("MAGPIE_CODEC_UNFUSED", 0) != 0;  // A/B switch (read per decode): the two-launch blocks
     return !off && (Cp == 224 || Cp == 128 || Cp == 64 || Cp == 32);
 }
 hipError_t run_rb(const mpc::RbP &p, int Cp, int nchunk, hipStream_t s) {
@@ -1649,8 +1644,7 @@ hipError_t run_rb(const mpc::RbP &p, int Cp, int nchunk, hipStream_t s) {
 // (rl, 4 waves x 64 columns) / 225-238 us (8 waves x 32 or 64 columns); 64 channels 274 us
 // (rb) against 340-394 us (rl: 167 VGPRs, one 8-wave workgroup per CU).
 bool rl_fused(int Cp) {
-    const char *e = getenv("MAGPIE_CODEC_RL");
-    const int mode = e ? atoi(e) : 1;
+    const int mode = mp::env_int("MAGPIE_CODEC_RL", 1);
     return (Cp == 32 && mode >= 1) || (Cp == 64 && mode >= 2);
 }
 template <int RWV, int CWV, int NT>
@@ -1680,8 +1674,7 @@ hipError_t run_conv(const mpc::ConvP &p, int BM, int mode, int nchunk, int nbran
     using namespace mpc;
     // ResLayer convs: the wide-tile kernel once a chunk fills at least half a tile
     // (per-chunk length decides, so a chunk decodes the same alone or batched)
-    static const bool v1 = getenv("MAGPIE_CODEC_V1") != nullptr;  // A/B switch: the narrow-tile kernel only
-    if (mode == IN_F16 && !v1) {
+    if (mode == IN_F16) {
         switch (p.Coutp) {
             case 448: if (p.T >= 64) return launch_conv2<2, 2, 14, true>(p, nchunk, nbranch, s); break;
             case 224: if (p.T >= 128) return launch_conv2<1, 4, 7, true>(p, nchunk, nbranch, s); break;
@@ -1841,22 +1834,10 @@ int mp_hip_codec_init(int device, const char *path, mp_codec **out) {
     return MP_OK;
 }
 
-// The stream a decode runs on: the background (CU-masked) one while set, else the codec's.
-// c->stream is swapped for the call's duration (every launch of codec_run reads it).
-struct CodecStreamScope {
-    mp_codec *c;
-    hipStream_t saved;
-    explicit CodecStreamScope(mp_codec *cc) : c(cc), saved(cc->stream) {
-        if (c->bg && c->bg_stream) c->stream = c->bg_stream;
-    }
-    ~CodecStreamScope() { c->stream = saved; }
-};
-
 int mp_hip_codec_decode_chunks(mp_codec *c, const int32_t *codes, int n_chunks, int chunk_frames, float *audio_out) {
     if (!c) return MP_ERR_ARG;
     if (!codes || !audio_out || n_chunks < 1 || chunk_frames < 1) { c->err = "invalid arguments"; return MP_ERR_ARG; }
     CHK(hipSetDevice(c->device));
-    CodecStreamScope scope(c);
     if (int rc = ensure_buffers(c, n_chunks, chunk_frames)) return rc;
     const size_t ncodes = (size_t)n_chunks * 8 * chunk_frames, nsamp = (size_t)n_chunks * chunk_frames * mpc::HOP;
     if (c->h_codes_cap < ncodes) {
@@ -1924,32 +1905,10 @@ int mp_hip_codec_decode(mp_codec *c, const int32_t *codes, int n_frames, float *
     return mp_hip_codec_decode_chunks(c, codes, 1, n_frames, audio_out);
 }
 
-// Internal (mp_hip_decode_stream): run this codec's next decodes in the background, i.e. on a
-// stream confined to `cus` of the device's CUs (0: back to the codec's own stream), so a decode
-// in flight on the model's stream keeps the rest of the chip; every decode computes the same bits
-// on either stream (the kernels do not depend on where their workgroups run).
-extern "C" int mp_codec_set_background(mp_codec *c, int cus) {
-    if (!c) return MP_ERR_ARG;
-    if (cus <= 0) { c->bg = 0; return MP_OK; }
-    CHK(hipSetDevice(c->device));
-    if (!c->bg_stream || c->bg_cus != cus) {
-        if (c->bg_stream) { CHK(hipStreamSynchronize(c->bg_stream)); hipStreamDestroy(c->bg_stream); c->bg_stream = nullptr; }
-        int ncu = 0;
-        CHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-        if (cus >= ncu) { c->bg = 0; return MP_OK; }
-        const std::vector<uint32_t> mask = mp::cu_share_mask(ncu, cus, false);
-        CHK(hipExtStreamCreateWithCUMask(&c->bg_stream, (uint32_t)mask.size(), mask.data()));
-        c->bg_cus = cus;
-    }
-    c->bg = 1;
-    return MP_OK;
-}
-
 void mp_hip_codec_free(mp_codec *c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->bg_stream) { hipStreamSynchronize(c->bg_stream); hipStreamDestroy(c->bg_stream); }
     if (c->h_codes_pin) hipHostFree(c->h_codes_pin);
     if (c->h_audio_pin) hipHostFree(c->h_audio_pin);
     for (void *p : c->weight_allocs) hipFree(p);

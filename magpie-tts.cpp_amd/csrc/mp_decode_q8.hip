@@ -616,7 +616,7 @@ hipError_t pack_q4(const signed char *q, int N, int K, unsigned char *oq, hipStr
 constexpr int XQ8_ROWS = 64;  // o_net rows per workgroup
 
 // xa_text_attention_q / xa_text_attention (the text attention itself): mp_xa.hpp, shared
-// with the preamble's cross-attention rows (mp_prefill.hip row_xa_kernel).
+// with the preamble's cross-attention rows (mp_prefill.hip row_xa_wg_kernel).
 
 // a (LDS, [128]) -> Q8_0 blocks aq / ad (ggml quantises the o_net operand), wave 0
 __device__ __forceinline__ void xa_quantize_a(const float *a_s, signed char *aq, float *ad) {

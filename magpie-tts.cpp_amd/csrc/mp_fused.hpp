@@ -196,29 +196,6 @@ __device__ __forceinline__ int wave_pick_rows(float (&lv)[QPR], int w, bool forb
     return wave_min_u(first);
 }
 
-// A logit as an ordered 64-bit key: the float's bits mapped to an unsigned order (high word)
-// and 0xFFFFFFFF - index (low word), so the largest key is the largest value at the lowest
-// index: the masked first-max argmax of wave_pick_rows / sample_top_k's greedy branch. 0 is
-// below every real key (a forbidden id).
-__device__ __forceinline__ unsigned long long lt_cand_key(float v, int i) {
-    const unsigned u = __float_as_uint(v);
-    const unsigned o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)o << 32) | (0xFFFFFFFFu - (unsigned)i);
-}
-__device__ __forceinline__ float lt_cand_value(unsigned long long k) {
-    const unsigned o = (unsigned)(k >> 32);
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
-__device__ __forceinline__ int lt_cand_index(unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)k); }
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)k, off), hi = __shfl_xor((unsigned)(k >> 32), off);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        k = o > k ? o : k;
-    }
-    return k;
-}
 // Whether logit i is forbidden (sample_top_k's mask, magpie.cpp:1237-1248): the 8 special
 // audio ids except EOS, and EOS too while forbid_eos.
 __device__ __forceinline__ bool lt_forbidden(int i, bool forbid_eos, int audio_bos, int audio_eos) {
@@ -611,7 +588,6 @@ struct PreRows<NB, K, PRO_LN> {
 // register arrays of these structs hold native 4-float vectors (an array of HIP's
 // float4 struct in a struct member was kept in scratch memory)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 to_v4(float4 a) { return f32x4{a.x, a.y, a.z, a.w}; }
 __device__ __forceinline__ float4 to_f4(f32x4 a) { return make_float4(a.x, a.y, a.z, a.w); }
 // Plain rows (PRO_PLAIN) while they fit in 12 float4 per thread
 template <int NB, int K>

@@ -19,7 +19,6 @@ constexpr int VCB = 2024;     // vocab per codebook           (magpie.h:63)
 #ifndef MP_RW_LTE
 #define MP_RW_LTE 2  // f32 LT head rows per wave at batch 1 (253 workgroups at 2)
 #endif
-constexpr int LT_HEAD_WGS = (VCB + 4 * MP_RW_LTE - 1) / (4 * MP_RW_LTE);  // its workgroups = candidates
 constexpr int CTX = 110;      // baked context frames         (magpie.h:67)
 constexpr int SA_CHUNK = 64;  // cache rows are allocated in whole 64-key chunks
 constexpr int NCH_MAX = 16;   // -> max_seq <= 1024 (reference: 626, magpie.cpp:4077)
@@ -147,9 +146,6 @@ struct LtFfn2P {
     unsigned long long *gh;
     const int *iter;
     int *hx_err;
-    // f32 batch 1, greedy: the previous head's workgroup candidates (GemvP::cand), ncand of them
-    const unsigned long long *cand;
-    int ncand;
 };
 
 // f32 mode at batch 1: the LT's front in ONE launch (lt_front_kernel) instead of three
@@ -172,23 +168,6 @@ struct LtFrontP {
     unsigned long long *gh;    // [2][256] granules: in_proj output, vo_0
     const int *iter;
     int *hx_err;
-};
-
-// f32 mode at batch 1, greedy: the whole LT of a frame in ONE launch (lt_all_kernel, 64
-// workgroups): the front as lt_front_kernel (k_0 handed over too), then per codebook the
-// FFN-down partial sums as {tag, value} granules gp[64][256] (tag iter * 64 + 48 + cb), each
-// workgroup merging 4 of the 256 outputs in partial order into y2 granules gy[256] (+ 56 + cb),
-// every workgroup 32 head rows on the swept y2 and its masked first-max logit as one ordered
-// key gc[wg] (EOS's own key in gc[64]; the low 21 bits a per-codebook tag), and every
-// workgroup the next code from the 65 keys, that position's y and its 16 FFN units. Per row,
-// output and step the arithmetic of lt_ffn2_kernel<1> and the batch-1 head (same bits).
-struct LtAllP {
-    LtFrontP f;                  // the front; f.l: tables, FFN weights, y, codes, step, logits (read)
-    const float *w_out, *b_out;  // heads [8][2024][256], biases [8][2024]
-    float *logits;               // [2024] each codebook's logits (codebook 7's: the finalize's pick)
-    unsigned long long *gp;      // [LT_FFN_P][256]
-    unsigned long long *gy;      // [256]
-    unsigned long long *gc;      // [LT_FFN_P + 1]
 };
 
 // Frame embedding of every slot (layer 0's residual input, magpie.cpp:2746-2787,
@@ -356,10 +335,6 @@ struct GemvP {
     // activation rows [NB][K], their Q8_0 blocks (int8 [NB][K], fp16 d as f32 [NB][K/32])
     // and every integer block dot [N][K/32][NB] (int32), as the kernel's operands give them
     void *q8dump;
-    // f32 LT head at batch 1, greedy (nullable): every workgroup also publishes its masked
-    // first-max logit as one ordered 64-bit key cand[blockIdx.x] (lt_cand_key), so the next
-    // LT step picks the code from the head's ~253 workgroup candidates instead of its 2024 logits
-    unsigned long long *cand;
 };
 
 // Q8_0 weight mode: the LT step of codebook cb as LTQ_P workgroups per slot

@@ -409,49 +409,15 @@ __global__ __launch_bounds__(RLN_T) void gemm_reduce_ln_kernel(GemmP p, int spli
     ln_row768(x, p.ln_w, p.ln_out + (size_t)m * p.ln_ld, p.ln_eps);
 }
 
-// Causal multi-head attention for every (row, head): one wave per pair.
+// Causal multi-head attention for every (row, head).
 // Keys for row (b, t) are rows j <= t of the same utterance, read through
 // (kbase, vbase) + b * utt_stride + j * row_stride + h * 64.
-
-template <bool KV16>
-__global__ __launch_bounds__(256) void row_attn_kernel(RowAttnP p) {
-    __shared__ float pr[4][TMAX_LIMIT];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int pair = blockIdx.x * 4 + w;
-    if (pair >= p.M * p.heads) return;
-    const int m = pair / p.heads, h = pair % p.heads;
-    const int b = m / p.rows_per_utt, t = m % p.rows_per_utt;
-    const int nk = t + 1;
-    const float *q = p.Q + (size_t)m * p.ldq + h * DH;
-    const size_t kb0 = b * p.utt_stride + h * DH;
-    float mx = -INFINITY;
-    for (int j = lane; j < nk; j += 64) {
-        const size_t k = kb0 + (size_t)j * p.row_stride;
-        float s = 0.f;
-        for (int d = 0; d < DH; d += 4) s += dotv(*(const float4 *)(q + d), kv_load4<KV16>(p.Kb, k + d));
-        s *= 0.125f;
-        pr[w][j] = s;
-        mx = fmaxf(mx, s);
-    }
-    mx = wave_max(mx);
-    float l = 0.f;
-    for (int j = lane; j < nk; j += 64) { const float e = expf(pr[w][j] - mx); pr[w][j] = e; l += e; }
-    l = wave_sum(l);
-    __builtin_amdgcn_wave_barrier();
-    float o = 0.f;
-    for (int j = 0; j < nk; ++j) {
-        const size_t vi = kb0 + (size_t)j * p.row_stride + lane;
-        o += pr[w][j] * (KV16 ? __uint_as_float((unsigned)((const unsigned short *)p.Vb)[vi] << 16) : p.Vb[vi]);
-    }
-    p.O[(size_t)m * D + h * DH + lane] = o / l;
-}
-
-// The same causal attention, one workgroup per (row, head), in the direct-form pattern of
+// One workgroup per (row, head), in the direct-form pattern of
 // the decode's text attention (xa_text_attention, mp_xa.hpp): keys in rounds of 64, 4 lanes
 // per key (16 dims each, one chain, the quad summed by DPP), every key's K row of a round
 // issued at once, one exp per key by its own thread, the values summed by 4 waves (keys
-// w, w + 4, ...; lane = dim) and the wave partials added in wave order. round 5's wave per
-// (row, head) made a dependent memory round trip per key of its value loop.
+// w, w + 4, ...; lane = dim) and the wave partials added in wave order (a wave per
+// (row, head) made a dependent memory round trip per key of its value loop).
 template <bool KV16>
 __global__ __launch_bounds__(MP_BLOCK) void row_attn_wg_kernel(RowAttnP p) {
     __shared__ float pr[TMAX_LIMIT];
@@ -518,53 +484,8 @@ __global__ __launch_bounds__(MP_BLOCK) void row_attn_wg_kernel(RowAttnP p) {
     }
 }
 
-// Cross-attention for a block of rows: 1 head x 128 over the utterance's T[b]
-// text positions (no mask).
-
-__global__ __launch_bounds__(256) void row_xa_kernel(RowXaP p) {
-    __shared__ float pr[4][TMAX_LIMIT];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int m = blockIdx.x * 4 + w;
-    if (m >= p.M) return;
-    const int b = m / p.rows_per_utt, Tb = p.T[b];
-    const float *q = p.Q + (size_t)m * DXA;
-    const float *Kb = p.xak + ((size_t)(b * p.nlayers + p.layer) * p.Tmax) * DXA;
-    const float *Vb = p.xav + ((size_t)(b * p.nlayers + p.layer) * p.Tmax) * DXA;
-    const float scale = 1.0f / sqrtf((float)DXA);
-    float mx = -INFINITY;
-    for (int j = lane; j < Tb; j += 64) {
-        float s = 0.f;
-        for (int d = 0; d < DXA; d += 4) s += dotv(*(const float4 *)(q + d), *(const float4 *)(Kb + (size_t)j * DXA + d));
-        s *= scale;
-        pr[w][j] = s;
-        mx = fmaxf(mx, s);
-    }
-    mx = wave_max(mx);
-    float l = 0.f;
-    for (int j = lane; j < Tb; j += 64) { const float e = expf(pr[w][j] - mx); pr[w][j] = e; l += e; }
-    l = wave_sum(l);
-    __builtin_amdgcn_wave_barrier();
-    float o0 = 0.f, o1 = 0.f;
-    for (int j0 = 0; j0 < Tb; j0 += 8) {  // 8 keys' V rows in flight, summed in key order
-        float v0[8], v1[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int j = min(j0 + u, Tb - 1);
-            v0[u] = Vb[(size_t)j * DXA + lane];
-            v1[u] = Vb[(size_t)j * DXA + 64 + lane];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (j0 + u < Tb) {
-                o0 += pr[w][j0 + u] * v0[u];
-                o1 += pr[w][j0 + u] * v1[u];
-            }
-    }
-    p.O[(size_t)m * DXA + lane] = o0 / l;
-    p.O[(size_t)m * DXA + 64 + lane] = o1 / l;
-}
-
-// The same cross-attention, one workgroup per row, on the decode's direct-form text
+// Cross-attention, 1 head x 128 over the utterance's T[b] text positions (no mask):
+// one workgroup per row, on the decode's direct-form text
 // attention (xa_text_attention, mp_xa.hpp: 4 lanes per key, the first 64 keys' K and V
 // rows issued at entry, one exp per key, wave partials summed in wave order): a row's
 // attention is one memory round trip and a few DPP steps instead of a wave's serial
@@ -620,10 +541,7 @@ __global__ void round_bf16_kernel(const float *src, float *dst, size_t n) {
 // ---------------------------------------------------------------- launchers
 // MAGPIE_PRE_VALU=1 runs the preamble GEMMs on the f32 VALU kernel (A/B, and the test
 // that both give the same bits; read at every launch, a few per preamble layer)
-static bool gemm_mfma() {
-    const char *e = getenv("MAGPIE_PRE_VALU");
-    return !(e && *e == '1');
-}
+static bool gemm_mfma() { return env_int("MAGPIE_PRE_VALU", 0) != 1; }
 // GemmP::ln_w: the rows this GEMM completes are normalised next (LN(C) * ln_w -> ln_out):
 // in the split reduction when there is one (gemm_reduce_ln_kernel), else as ln_rows_kernel
 static hipError_t launch_ln_after(const GemmP &p, hipStream_t s) {
@@ -728,23 +646,12 @@ hipError_t pre_round_bf16(const float *src, float *dst, size_t n, hipStream_t s)
     return hipGetLastError();
 }
 hipError_t pre_row_attn(const RowAttnP &p, hipStream_t s) {
-    static const bool old = getenv("MAGPIE_PRE_ROWATTN_OLD") != nullptr;  // A/B: a wave per (row, head)
-    if (!old) {
-        if (p.kv16) hipLaunchKernelGGL(row_attn_wg_kernel<true>, dim3(p.M, p.heads), dim3(MP_BLOCK), 0, s, p);
-        else hipLaunchKernelGGL(row_attn_wg_kernel<false>, dim3(p.M, p.heads), dim3(MP_BLOCK), 0, s, p);
-        return hipGetLastError();
-    }
-    if (p.kv16) hipLaunchKernelGGL(row_attn_kernel<true>, dim3((p.M * p.heads + 3) / 4), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(row_attn_kernel<false>, dim3((p.M * p.heads + 3) / 4), dim3(256), 0, s, p);
+    if (p.kv16) hipLaunchKernelGGL(row_attn_wg_kernel<true>, dim3(p.M, p.heads), dim3(MP_BLOCK), 0, s, p);
+    else hipLaunchKernelGGL(row_attn_wg_kernel<false>, dim3(p.M, p.heads), dim3(MP_BLOCK), 0, s, p);
     return hipGetLastError();
 }
 hipError_t pre_row_xa(const RowXaP &p, hipStream_t s) {
-    static const bool old = getenv("MAGPIE_PRE_ROWXA_OLD") != nullptr;  // A/B: a wave per row (round 5)
-    if (!old) {
-        hipLaunchKernelGGL(row_xa_wg_kernel, dim3(p.M), dim3(MP_BLOCK), 0, s, p);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(row_xa_kernel, dim3((p.M + 3) / 4), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(row_xa_wg_kernel, dim3(p.M), dim3(MP_BLOCK), 0, s, p);
     return hipGetLastError();
 }
 hipError_t pre_embed_text(const int *tok, const int *T, int B, int Tmax, const float *te, const float *ep, float *X,

@@ -114,7 +114,6 @@ hipError_t op_lt_merge(const LtFfnP &, int, hipStream_t);
 hipError_t op_lt_ffn2(const LtFfn2P &, int, hipStream_t);
 hipError_t op_lt_slot(const LtFfn2P &, int, hipStream_t);
 hipError_t op_lt_front(const LtFrontP &, hipStream_t);
-hipError_t op_lt_all(const LtAllP &, hipStream_t);
 hipError_t op_lt_slot_q8(const LtSlotQ8P &, int, hipStream_t);
 hipError_t op_lt_kvo(const GemvP &, int, hipStream_t);
 hipError_t op_sa_attn(const AttnP &, int, hipStream_t);
@@ -238,11 +237,9 @@ struct Model {
 };
 
 enum OpKind { K_GEMV = 0, K_ATTN = 1, K_FIN = 2, K_XA = 3, K_XAQ8 = 5, K_LTFFN = 6, K_LTMERGE = 7, K_LTPICK = 8, K_EMBED = 9,
-              K_LTFFN2 = 10, K_LTKVO = 11, K_LTSLOT = 12, K_LTFRONT = 13, K_LTSLOTQ8 = 14, K_LTALL = 15 };
-// the f32 batch-1 LT's granules (one zeroed buffer): the front's in_proj / vo_0 / k_0, then
-// lt_all_kernel's FFN-down partials, y2 and workgroup keys
-constexpr size_t LTFG_GP = 3 * 256, LTFG_GY = LTFG_GP + (size_t)LT_FFN_P * 256, LTFG_GC = LTFG_GY + 256,
-                 LTFG_TOTAL = LTFG_GC + 128;
+              K_LTFFN2 = 10, K_LTKVO = 11, K_LTSLOT = 12, K_LTFRONT = 13, K_LTSLOTQ8 = 14 };
+// the f32 batch-1 LT front's granules (one zeroed buffer, LtFrontP::gh): in_proj output, vo_0
+constexpr size_t LTFG_TOTAL = 2 * 256;
 struct OpRec {
     std::string name;
     int kind;
@@ -255,7 +252,6 @@ struct OpRec {
     LtFfnP lf;
     LtFfn2P l2;
     LtFrontP lf3;
-    LtAllP la;
     LtSlotQ8P lq8;
     EmbP e;
     int B;
@@ -270,8 +266,7 @@ struct LtIo {
     float *lt_s, *ltX, *ltY, *lty2, *ltq, *ltk, *ltv, *ltf, *logits;
     float *ltp;  // [NB][LT_FFN_P][256] partial FFN-down sums (lt_ffn_kernel; lt_slot_kernel: [NB][LTS_P][256])
     unsigned long long *ltgh;  // [NB][LTS_P or LTQ_P][256] lt_slot(_q8)_kernel's partial-sum granules
-    unsigned long long *ltfg;  // lt_front / lt_all_kernel's hand-off granules (f32, batch 1; LTFG_* below)
-    unsigned long long *ltcand;  // [256] the f32 batch-1 head's workgroup candidates (GemvP::cand; null: off)
+    unsigned long long *ltfg;  // [LTFG_TOTAL] lt_front_kernel's hand-off granules (f32, batch 1)
     unsigned long long *ltyg;  // [NB][256] lt_slot_q8_kernel's y granules (Q8_0 mode)
     int *iter, *hx_err;        // decode iteration counter (hand-off tags), hand-off error bits
     int *codes_cur, *codes_prev, *codes_out, *step, *pos, *done, *nframes, *ndone, *argeos, *amax;
@@ -314,14 +309,14 @@ struct mp_dev {
     float *kc = nullptr, *vc = nullptr, *xak = nullptr, *xav = nullptr;
     float *lt_s = nullptr, *ltX = nullptr, *ltY = nullptr, *lty2 = nullptr, *ltq = nullptr, *ltk = nullptr,
           *ltv = nullptr, *ltf = nullptr, *logits = nullptr, *trace = nullptr, *ltp = nullptr;
-    unsigned long long *ltgh = nullptr, *ltfg = nullptr, *ltyg = nullptr, *ltcand = nullptr;
+    unsigned long long *ltgh = nullptr, *ltfg = nullptr, *ltyg = nullptr;
     int *T = nullptr, *spk = nullptr, *pos = nullptr, *step = nullptr, *done = nullptr, *nframes = nullptr,
         *ndone = nullptr, *codes_cur = nullptr, *codes_prev = nullptr, *codes_out = nullptr, *tok = nullptr,
         *argeos = nullptr, *amax = nullptr;
     mp::SmpCfg *smpcfg = nullptr;
     int lt_calls = 0;
     // magpie_local_transformer_sample_all scratch (batch 1, independent of any batch)
-    std::vector<void *> lt_allocs;
+    std::vector<void *> ltio_allocs;
     mp::LtIo lt_io{};
     // preamble scratch
     float *pX = nullptr, *pH = nullptr, *pQKV = nullptr, *pATT = nullptr, *pF = nullptr, *pXQ = nullptr,
@@ -337,10 +332,6 @@ struct mp_dev {
     // per-call hipFree would synchronise the whole device, stalling other streams' work)
     char *enc_ws = nullptr;
     size_t enc_ws_bytes = 0;
-    // streaming rounds overlapped with a background codec: the frame loop on the CUs the
-    // codec's background stream leaves (cu_share_mask complement), created on first use
-    hipStream_t stream_fg = nullptr;
-    int stream_fg_cus = 0;
     // diagnostics (MAGPIE_Q8DUMP=1 at mp_hip_begin_batch, Q8_0 weights): one dump slot per
     // int8-MFMA decode GEMM launch of the iteration (GemvP::q8dump), records in q8dump_index
     char *q8dump = nullptr;
@@ -632,15 +623,6 @@ static unsigned short bf16_bits(float x) {
 // f32 mode's LT (lt_ffn2_kernel) needs o_net applied to v rows ahead of time:
 // VO[c][v] = W_o V[c][v] for every table row, and [W_k ; W_o W_v] for position 0.
 bool f32_lt_mode(const mp::Model &m) { return m.weight_mode == MP_WEIGHTS_AS_STORED; }
-// MAGPIE_LT_ALL=1: the whole f32 batch-1 greedy LT of a frame in one launch (lt_all_kernel)
-// instead of the front + 7 x {lt_ffn2, lt_e} + lt_e launches (the same bits). Off by default:
-// its three granule edges per codebook (FFN-down partials -> 4-output merges -> y2 -> head
-// keys -> pick) cost ~9 us per codebook against 2 launches' ~9.2: 73.5 vs 76.7 us per frame
-// in the per-op timing, 2,967 vs 3,070 frames/s graph-replayed (gpurun_out/r06t_ops_f32_b1*)
-bool lt_all_mode() {
-    const char *e = getenv("MAGPIE_LT_ALL");
-    return e && atoi(e) != 0;
-}
 // the LT attention through the load-time q|k|vo tables in f32: the f32 mode, and the bf16
 // mode (whose LT FFN and heads are bf16: lt_slot_kernel + the bf16 head)
 bool lt_table_attn(const mp::Model &m) { return m.weight_mode == MP_WEIGHTS_AS_STORED || m.weight_mode == MP_WEIGHTS_BF16; }
@@ -763,8 +745,7 @@ int load_q8(mp_dev *dev, const char *path) {
     struct Item { const mp::GgufTensor *t; mp::QW *dst; int group; };
     // a Q4_0 tensor's decode fragments stream its nibbles (MAGPIE_Q4_AS_Q8=1: as int8 q - 8,
     // the same integers at 34 B per 32 weights; both compute the same bits)
-    const char *q4e = getenv("MAGPIE_Q4_AS_Q8");
-    const bool q4_nib = !(q4e && atoi(q4e) != 0);
+    const bool q4_nib = mp::env_int("MAGPIE_Q4_AS_Q8", 0) == 0;
     std::vector<Item> items;
     auto want = [&](const std::string &name, mp::QW *dst) {
         const mp::GgufTensor *t = g.find(name);
@@ -959,7 +940,6 @@ int alloc_batch(mp_dev *dev, int B, int Tmax, int max_steps, bool trace) {
     A(lt_s, NB * 9 * 256); A(ltX, NB * 256); A(ltY, NB * 256); A(lty2, NB * 256); A(ltq, NB * 256);
     A(ltk, NB * 8 * 256); A(ltv, NB * 8 * 256); A(ltf, NB * 1024); A(logits, NB * 2024);
     A(ltp, (size_t)NB * std::max({mp::LT_FFN_P, mp::LTS_P, mp::LTQ_P}) * 256); A(ltgh, (size_t)NB * std::max(mp::LTS_P, mp::LTQ_P) * 256); A(ltfg, mp::LTFG_TOTAL); A(ltyg, (size_t)NB * 256);
-    A(ltcand, 256);  // zeroed: slots past the head's workgroups + EOS slot stay 0
     if (trace) A(trace, (size_t)NB * (max_steps + 1) * D);
     A(T, NB); A(spk, NB); A(pos, NB); A(step, NB); A(done, NB); A(nframes, NB); A(ndone, 4);  // ndone: [done count, iteration, hand-off timeout, -]
     A(argeos, NB); A(amax, NB * 8); A(smpcfg, 1);
@@ -975,7 +955,7 @@ int alloc_batch(mp_dev *dev, int B, int Tmax, int max_steps, bool trace) {
         need(Me, 256 * L, 768);  // the XA K/V GEMMs batched over layers
         A(gpart, cap);
     }
-    if (const char *qd = getenv("MAGPIE_Q8DUMP"); qd && atoi(qd) != 0 && dev->m.weight_mode == MP_WEIGHTS_Q8) {
+    if (mp::env_int("MAGPIE_Q8DUMP", 0) != 0 && dev->m.weight_mode == MP_WEIGHTS_Q8) {
         // the largest launch: K = 768, N = 2304 (QKV): rows, blocks, d, dots
         const size_t slot = ((size_t)NB * 768 * 5 + (size_t)NB * 24 * 4 + (size_t)2304 * 24 * NB * 4 + 255) / 256 * 256;
         dev->q8dump_cap = 4 * L + 16;
@@ -1005,7 +985,6 @@ mp::GemvP gemv_base(mp_dev *dev) {
 
 int enqueue_lt(mp_dev *dev, const mp::LtIo &io, int NB, hipStream_t s, std::vector<mp::OpRec> *ops);
 bool q8_unfused();
-bool lt_cand_mode();
 bool sa16_fused(int weight_mode);
 int split_merge8();
 
@@ -1198,7 +1177,6 @@ int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record) {
     io.lt_s = dev->lt_s; io.ltX = dev->ltX; io.ltY = dev->ltY; io.lty2 = dev->lty2; io.ltq = dev->ltq;
     io.ltk = dev->ltk; io.ltv = dev->ltv; io.ltf = dev->ltf; io.logits = dev->logits; io.ltp = dev->ltp;
     io.ltgh = dev->ltgh; io.ltfg = dev->ltfg; io.ltyg = dev->ltyg; io.iter = dev->ndone + 1; io.hx_err = dev->ndone + 2;
-    io.ltcand = lt_cand_mode() ? dev->ltcand : nullptr;
     io.codes_cur = dev->codes_cur; io.codes_prev = dev->codes_prev; io.codes_out = dev->codes_out; io.step = dev->step;
     io.pos = dev->pos; io.done = dev->done; io.nframes = dev->nframes; io.ndone = dev->ndone; io.argeos = dev->argeos;
     io.amax = dev->amax; io.cfg = dev->smpcfg;
@@ -1213,50 +1191,25 @@ int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record) {
 // MAGPIE_EAGER=1: launch the iteration's kernels directly instead of replaying
 // the captured graph (identical kernels and arguments; used under rocprofv3,
 // whose kernel tracer crashes on graph replays on this image).
-bool eager_mode() {
-    const char *e = getenv("MAGPIE_EAGER");
-    return e && atoi(e) != 0;
-}
+bool eager_mode() { return mp::env_int("MAGPIE_EAGER", 0) != 0; }
 // MAGPIE_Q8_UNFUSED=1: the Q8_0 mode's SA and XA as separate launches (the fused forms
 // compute the same bits; tests/test_q8_fused_gpu.py compares them)
-// MAGPIE_LT_CAND=1 (f32 batch 1, greedy): the LT head publishes a masked first-max
-// candidate per workgroup and the next LT step picks from those (GemvP::cand) instead of
-// scanning the head's 2024 logits. Both pick the same code (same bits). Off by default:
-// measured 1.6 % slower at f32 B=1 (2,985 vs 3,034 frames/s, three alternating pairs on one
-// box, profiles/r06b_ab_lt_cand.txt): the head's workgroup barrier and 64-bit reduction cost
-// more than the step saves, whose pick waits on the logits' memory round trip either way.
-bool lt_cand_mode() {
-    const char *e = getenv("MAGPIE_LT_CAND");
-    return e && atoi(e) != 0;
-}
+bool q8_unfused() { return mp::env_int("MAGPIE_Q8_UNFUSED", 0) != 0; }
 // The SA in the QKV launch at 16 slots: MAGPIE_SA16 unset = the bf16 mode's, 1 = every
 // mode's, 0 = none (A/B; both forms compute the same bits). Round 3 kept it separate (bf16
 // B=16 20.1k vs 21.5k frames/s then); since round 4's single pollers the fused form is
 // faster: 31,891 -> 32,620 / 32,893 frames/s (qkv 4.54 + sa_attn 7.34 -> qkv_sa 11.05 us
 // per layer; gpurun_out/r06l_ops_bf16_b16*)
-bool sa16_fused(int weight_mode) {
-    const char *e = getenv("MAGPIE_SA16");
-    return e ? atoi(e) != 0 : weight_mode == MP_WEIGHTS_BF16;
-}
+bool sa16_fused(int weight_mode) { return mp::env_int("MAGPIE_SA16", weight_mode == MP_WEIGHTS_BF16) != 0; }
 // At 8 bf16 slots, which split states the split workgroups merge themselves (bit 0: SA, in
 // the QKV launch; bit 1: XA, in the O-projection's) rather than the consumers' prologues
 // (PRO_SA_MERGE, PRO_XA_LN): MAGPIE_MERGE8, default 3 (A/B; every setting the same bits)
-int split_merge8() {
-    const char *e = getenv("MAGPIE_MERGE8");
-    return e ? atoi(e) : 3;
-}
-bool q8_unfused() {
-    const char *e = getenv("MAGPIE_Q8_UNFUSED");
-    return e && atoi(e) != 0;
-}
+int split_merge8() { return mp::env_int("MAGPIE_MERGE8", 3); }
 // MAGPIE_LTQ8 (Q8_0 LT step, lt_slot_q8_kernel): 0 = o_net rows split over the workgroups
 // (y hand-off) and the FFN merge in the launch; 1 = every workgroup all o_net rows (no y
 // hand-off); 2 (default) = that up to 4 slots, and at batch 1 the FFN merge deferred to
 // the head's prologue. Every setting computes the same bits (tests/test_q8_fused_gpu.py).
-int ltq8_mode() {
-    const char *e = getenv("MAGPIE_LTQ8");
-    return e ? atoi(e) : 2;
-}
+int ltq8_mode() { return mp::env_int("MAGPIE_LTQ8", 2); }
 
 // Diagnostics (MAGPIE_EAGER=1 and MAGPIE_DUMP_LT=file): after every launch of
 // the local transformer, slot 0's LT state is appended to the file as f32
@@ -1406,32 +1359,12 @@ int enqueue_lt(mp_dev *dev, const mp::LtIo &io, int NB, hipStream_t s, std::vect
             l2.codes_cur = io.codes_cur; l2.step = io.step; l2.ignore_eos = io.ignore_eos;
             l2.audio_bos = m.audio_bos; l2.audio_eos = m.audio_eos;
             l2.smp = mp::Sampling{io.sampling, io.cfg, io.argeos, io.amax};
-            // greedy batch 1: the pick from the previous head's workgroup candidates
-            const bool cand = NB == 1 && !io.sampling && io.ltcand && !io.lt_only;
-            if (cand && cb > 0) { l2.cand = io.ltcand; l2.ncand = (2024 + 4 * MP_RW_LTE - 1) / (4 * MP_RW_LTE); }
             if (front && cb == 0) {
                 mp::LtFrontP fp{};
                 fp.l = l2; fp.x = io.x; fp.norm_out = m.dec_norm_out; fp.w_in = m.lt_in_w; fp.b_in = m.lt_in_b;
                 fp.lt_s = io.lt_s; fp.hidden_out = io.hidden; fp.lt_pos = m.lt_pos; fp.norm_self = m.lt_norm_self;
                 fp.w_kvo = m.lt_kvo; fp.gh = io.ltfg; fp.iter = io.iter; fp.hx_err = io.hx_err;
                 if (io.trace) { fp.trace = io.trace; fp.trace_steps = io.trace_steps; }
-                if (!io.sampling && lt_all_mode()) {
-                    // the whole LT in one launch (lt_all_kernel): the front, then every codebook's
-                    // FFN merge, head and greedy pick through granules; codebook 7's pick is the finalize's
-                    mp::LtAllP la{};
-                    la.f = fp; la.w_out = m.lt_out_w; la.b_out = m.lt_out_b; la.logits = io.logits;
-                    la.gp = io.ltfg + mp::LTFG_GP; la.gy = io.ltfg + mp::LTFG_GY; la.gc = io.ltfg + mp::LTFG_GC;
-                    if (ops) {
-                        mp::OpRec r{};
-                        r.name = "lt_all"; r.kind = mp::K_LTALL; r.la = la; r.B = NB;
-                        r.bytes = A * (256.0 * 768 + 512.0 * 256 + 1024.0 * 256 * 2 + 8.0 * 2024 * 256 + 8.0 * 2024) +
-                                  A * (768 * 2 + 256 * 4) + A * 7.0 * (3 * 256 + 2 * 256);
-                        ops->push_back(r);
-                    }
-                    HIPCHK(mp::op_lt_all(la, s));
-                    dump_lt(io, s);
-                    break;
-                }
                 if (ops) {
                     mp::OpRec r{};
                     r.name = "lt_front"; r.kind = mp::K_LTFRONT; r.lf3 = fp; r.B = NB;
@@ -1468,7 +1401,6 @@ int enqueue_lt(mp_dev *dev, const mp::LtIo &io, int NB, hipStream_t s, std::vect
             if (NB == 1) {  // the FFN merge is the head's prologue
                 g.part = io.ltp; g.addsrc = io.ltY;
                 efn = mp::op_lt_em_1;
-                if (cand && cb < 7) g.cand = io.ltcand;  // (codebook 7's code is the finalize's pick)
             }
             if ((rc = run("lt_e", efn, g, A * (2024.0 * 256) + A * 2024 + A * act * ((256 + 2024)))) != MP_OK)
                 return rc;
@@ -1850,8 +1782,7 @@ int mp_hip_init(int device, mp_dev **out) {
     // frame loop's workgroups first and the codec (least priority, mp_hip_codec_init) fills in
     // (MAGPIE_STREAM_PRIO=0: the default priority, A/B)
     int least = 0, greatest = 0;
-    const char *pe = getenv("MAGPIE_STREAM_PRIO");
-    const bool prio = !pe || atoi(pe) != 0;
+    const bool prio = mp::env_int("MAGPIE_STREAM_PRIO", 1) != 0;
     if (hipSetDevice(device) != hipSuccess || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
         hipStreamCreateWithPriority(&dev->stream, hipStreamNonBlocking, prio ? greatest : 0) != hipSuccess ||
         hipHostMalloc((void **)&dev->h_ndone, 64, 0) != hipSuccess) {
@@ -1959,14 +1890,13 @@ void mp_hip_free(mp_dev *dev) {
     if (dev->m.pk_arena) hipFree(dev->m.pk_arena);
     if (dev->m.q8_arena) hipFree(dev->m.q8_arena);
     if (dev->m.q8p_arena) hipFree(dev->m.q8p_arena);
-    for (void *p : dev->lt_allocs) hipFree(p);
+    for (void *p : dev->ltio_allocs) hipFree(p);
     if (!dev->m.xq_t.empty() && dev->m.xq_t[0]) hipFree(dev->m.xq_t[0]);  // one allocation (load_model)
     if (dev->h_ndone) hipHostFree(dev->h_ndone);
     for (hipEvent_t e : dev->sev)
         if (e) hipEventDestroy(e);
     if (dev->h_codes) hipHostFree(dev->h_codes);
     if (dev->enc_ws) hipFree(dev->enc_ws);
-    if (dev->stream_fg) { hipStreamSynchronize(dev->stream_fg); hipStreamDestroy(dev->stream_fg); }
     if (dev->stream) hipStreamDestroy(dev->stream);
     delete dev;
 }
@@ -2207,27 +2137,14 @@ int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames) {
 // Every full chunk of a round goes through the codec in one launch sequence
 // (chunks are independent, magpie.cpp:4739-4742: the audio is the same); the
 // frames reach the host through a pinned mirror filled on the decode stream.
-extern "C" int mp_codec_set_background(mp_codec *c, int cus);  // mp_codec.hip (internal)
 // MAGPIE_STREAM_ASYNC=0: queue each chunk from the calling thread (default 1: a helper thread)
-static bool stream_async() {
-    const char *e = getenv("MAGPIE_STREAM_ASYNC");
-    return !(e && atoi(e) == 0);
-}
+static bool stream_async() { return mp::env_int("MAGPIE_STREAM_ASYNC", 1) != 0; }
 // MAGPIE_STREAM_TRACE=1: host-side timeline of the streaming loop on stderr (diagnostics)
-static bool stream_trace() {
-    const char *e = getenv("MAGPIE_STREAM_TRACE");
-    return e && atoi(e) != 0;
-}
-// MAGPIE_CODEC_BG_CUS: CUs of the codec's background stream while a decode is in flight
-// (default 64 of 256; 0 = the codec's own stream, the whole chip, for every round)
-static int codec_bg_cus() {
-    const char *e = getenv("MAGPIE_CODEC_BG_CUS");
-    return e ? atoi(e) : 0;
-}
-// codec rounds of at least this many frames go to the background stream while the decode
-// continues (throughput: configs[2]'s 16 slots x 32-frame chunks); smaller rounds (a stream's
-// 4-frame chunks, whose first chunk is the time to first audio) keep the whole chip
-constexpr int CODEC_BG_MIN_FRAMES = 256;
+static bool stream_trace() { return mp::env_int("MAGPIE_STREAM_TRACE", 0) != 0; }
+// rounds of at least this many frames queue the next chunk from the helper thread
+// (throughput: configs[2]'s 16 slots x 32-frame chunks); smaller rounds (a stream's 4-frame
+// chunks, whose first chunk is the time to first audio) queue it from the calling thread
+constexpr int STREAM_ASYNC_MIN_FRAMES = 256;
 
 int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_audio_cb on_audio, void *user,
                          int32_t *codes_out, int32_t *n_frames, int64_t *total_samples) {
@@ -2260,9 +2177,8 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
     int it = 0;
     bool first = true;
     dev->timing = mp_timing{dev->timing.preamble_ms, 0.0, 0, 0, 0.0};
-    // the stream the last chunk was queued on (the stop writes below follow it)
-    hipStream_t cur = dev->stream;
-    auto enqueue_chunk = [&](int slot, hipStream_t st) -> int {
+    auto enqueue_chunk = [&](int slot) -> int {
+        const hipStream_t st = dev->stream;
         const int n_it = std::min(fpc, S - it);
         for (int i = 0; i < n_it; ++i)
             if (int rc = launch_iteration(dev, st)) return rc;
@@ -2278,24 +2194,10 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
         HIPCHK(hipEventRecord(dev->sev[slot], st));
         return MP_OK;
     };
-    // rounds whose codec runs in the background: the decode on the complementary CUs. Every
-    // chunk is queued after the previous one landed (the host waited for its event), so
-    // moving between the two streams needs no other ordering.
-    const int bg_cus = codec_bg_cus();
-    const bool split_cus = B * fpc >= CODEC_BG_MIN_FRAMES && bg_cus > 0 && stream_async();
-    if (split_cus && (!dev->stream_fg || dev->stream_fg_cus != bg_cus)) {
-        if (dev->stream_fg) { HIPCHK(hipStreamSynchronize(dev->stream_fg)); hipStreamDestroy(dev->stream_fg); dev->stream_fg = nullptr; }
-        int ncu = 0, least = 0, greatest = 0;
-        HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev->device));
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        const std::vector<uint32_t> mask = mp::cu_share_mask(ncu, bg_cus, true);
-        HIPCHK(hipExtStreamCreateWithCUMask(&dev->stream_fg, (uint32_t)mask.size(), mask.data()));
-        dev->stream_fg_cus = bg_cus;
-    }
     struct Job { int b, f0, n; };
     std::vector<Job> jobs;
     int slot = 0;
-    if (int rc = enqueue_chunk(0, dev->stream)) return rc;
+    if (int rc = enqueue_chunk(0)) return rc;
     for (;;) {
         HIPCHK(hipEventSynchronize(dev->sev[slot]));
         const int *h_step = snap + (size_t)slot * 3 * NB, *h_done = h_step + NB, *h_nf = h_step + 2 * NB;
@@ -2314,11 +2216,14 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
         // helper touches only the decode stream and its pinned snapshot)
         const double t_wait = ms_since(t0);
         std::future<int> queued;
-        const bool async_q = more && stream_async() && B * fpc >= CODEC_BG_MIN_FRAMES;  // (a thread per round)
-        if (more) {
-            cur = async_q && split_cus ? dev->stream_fg : dev->stream;
-            if (async_q) queued = std::async(std::launch::async, [&, sl = slot ^ 1, st = cur]() { return enqueue_chunk(sl, st); });
-            else if (int rc = enqueue_chunk(slot ^ 1, cur)) return rc;
+        const bool async_q = more && stream_async() && B * fpc >= STREAM_ASYNC_MIN_FRAMES;  // (a thread per round)
+        if (async_q) {
+            queued = std::async(std::launch::async, [&, sl = slot ^ 1]() -> int {
+                HIPCHK(hipSetDevice(dev->device));  // the current device is per thread
+                return enqueue_chunk(sl);
+            });
+        } else if (more) {
+            if (int rc = enqueue_chunk(slot ^ 1)) return rc;
         }
         if (stream_trace()) fprintf(stderr, "[stream] round at %.3f ms: chunk landed, next queued %s at %.3f ms\n", t_wait,
                                     async_q ? "(async)" : "", ms_since(t0));
@@ -2351,17 +2256,9 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
             for (int t = 0; t < j.n; ++t)  // frame-major -> codebook-major (decode_frames_to_audio, 4468-4473)
                 for (int c = 0; c < 8; ++c) dst[(size_t)c * j.n + t] = fm[(size_t)t * 8 + c];
         }
-        if (nfull) {
-            // beside a decode still in flight, large rounds run on the codec's CU-masked
-            // background stream: the frame loop keeps most of the chip (with the whole chip the
-            // codec's long workgroups held the CUs the decode's next launches waited for, and
-            // overlapping bought nothing: 27.2k vs 27.5k frames/s serial, round 6 r06c)
-            const int bg = more && (int)nfull * fpc >= CODEC_BG_MIN_FRAMES ? codec_bg_cus() : 0;
-            if (int rc = mp_codec_set_background(codec, bg)) return fail(dev, rc, "codec background stream");
-            const int rc = mp_hip_codec_decode_chunks(codec, cbm.data(), (int)nfull, fpc, audio.data());
-            mp_codec_set_background(codec, 0);
-            if (rc) return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-        }
+        if (nfull)
+            if (int rc = mp_hip_codec_decode_chunks(codec, cbm.data(), (int)nfull, fpc, audio.data()))
+                return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
         for (size_t q = 0; q < jobs.size(); ++q)
             if (jobs[q].n != fpc)
                 if (int rc = mp_hip_codec_decode(codec, cbm.data() + at[q] * 8 * fpc, jobs[q].n,
@@ -2384,8 +2281,8 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
                     // the callback asked to stop (4820-4824): the utterance ends here
                     stopped[b] = 1;
                     const int one = 1;
-                    HIPCHK(hipMemcpyAsync(dev->done + b, &one, 4, hipMemcpyHostToDevice, cur));
-                    HIPCHK(hipStreamSynchronize(cur));
+                    HIPCHK(hipMemcpyAsync(dev->done + b, &one, 4, hipMemcpyHostToDevice, dev->stream));
+                    HIPCHK(hipStreamSynchronize(dev->stream));
                 }
             }
             if ((h_done[b] != 0 || stopped[b]) && !ended[b]) {  // end-of-utterance notice: (utt, NULL, 0)
@@ -2397,7 +2294,6 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
         slot ^= 1;
     }
     HIPCHK(hipStreamSynchronize(dev->stream));
-    if (dev->stream_fg) HIPCHK(hipStreamSynchronize(dev->stream_fg));
     if (int rc = check_handoff(dev)) return rc;
     dev->timing.decode_ms = ms_since(t0);
     dev->timing.iterations = it;
@@ -2419,12 +2315,12 @@ int mp_hip_lt_sample(mp_dev *dev, const float *hidden, float temperature, int to
     if (temperature >= 0.01f && (top_k < 1 || top_k > mp::VCB)) return fail(dev, MP_ERR_ARG, "top_k must be in 1..2024");
     HIPCHK(hipSetDevice(dev->device));
     mp::LtIo &io = dev->lt_io;
-    if (dev->lt_allocs.empty()) {
+    if (dev->ltio_allocs.empty()) {
         auto al = [&](auto **p, size_t n) -> int {
             void *v = nullptr;
             HIPCHK(hipMalloc(&v, n * 4 + 256));
             HIPCHK(hipMemset(v, 0, n * 4 + 256));
-            dev->lt_allocs.push_back(v);
+            dev->ltio_allocs.push_back(v);
             *p = (std::remove_reference_t<decltype(**p)> *)v;
             return MP_OK;
         };
@@ -2531,7 +2427,6 @@ static hipError_t launch_rec(const mp::OpRec &r, hipStream_t s) {
     case mp::K_LTFFN2: return mp::op_lt_ffn2(r.l2, r.B, s);
     case mp::K_LTSLOT: return mp::op_lt_slot(r.l2, r.B, s);
     case mp::K_LTFRONT: return mp::op_lt_front(r.lf3, s);
-    case mp::K_LTALL: return mp::op_lt_all(r.la, s);
     case mp::K_LTSLOTQ8: return mp::op_lt_slot_q8(r.lq8, r.B, s);
     case mp::K_LTKVO: return mp::op_lt_kvo(r.g, r.B, s);
     case mp::K_EMBED: return mp::op_embed(r.e, r.B, s);
@@ -2676,7 +2571,7 @@ int mp_hip_time_op(mp_dev *dev, int op, int reps, float *avg_us) {
     // iteration counter: relaunched with the same tag, its consumers would find the previous
     // launch's granules and not wait for their producers (a different, shorter critical path)
     const bool handoff = (r.kind == mp::K_GEMV && r.g.iter) || (r.kind == mp::K_LTSLOT && r.l2.gh) ||
-                         r.kind == mp::K_LTFRONT || r.kind == mp::K_LTALL || r.kind == mp::K_LTSLOTQ8 ||
+                         r.kind == mp::K_LTFRONT || r.kind == mp::K_LTSLOTQ8 ||
                          (r.kind == mp::K_ATTN && r.a.gh);
     if (handoff)
         return fail(dev, MP_ERR_ARG, "op carries an in-launch hand-off: back-to-back timing would not wait for it");
