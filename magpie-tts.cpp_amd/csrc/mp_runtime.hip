@@ -240,6 +240,12 @@ enum OpKind { K_GEMV = 0, K_ATTN = 1, K_FIN = 2, K_XA = 3, K_XAQ8 = 5, K_LTFFN =
               K_LTFFN2 = 10, K_LTKVO = 11, K_LTSLOT = 12, K_LTFRONT = 13, K_LTSLOTQ8 = 14 };
 // the f32 batch-1 LT front's granules (one zeroed buffer, LtFrontP::gh): in_proj output, vo_0
 constexpr size_t LTFG_TOTAL = 2 * 256;
+// MAGPIE_DUMP_LT: the LT buffers of slot 0 a state record is read from after a launch
+// (logits null: no record after this launch)
+struct LtDumpP {
+    const float *logits, *ltX, *ltY, *lty2, *ltq;
+    const int *codes_cur;
+};
 struct OpRec {
     std::string name;
     int kind;
@@ -257,6 +263,7 @@ struct OpRec {
     int B;
     double bytes;
     bool add_sa = false;  // the launch also runs the SA (EPI_QKV_SA): its live-cache bytes are added
+    LtDumpP dump;
 };
 
 // Buffers of the local-transformer + bookkeeping part of an iteration
@@ -337,7 +344,6 @@ struct mp_dev {
     char *q8dump = nullptr;
     size_t q8dump_slot = 0;
     int q8dump_cap = 0, q8dump_n = 0;
-    bool q8dump_live = false;  // set while enqueue_iteration runs (not for mp_hip_lt_sample)
     std::vector<int> q8dump_index;
 };
 
@@ -387,8 +393,7 @@ void free_batch(mp_dev *dev) {
 // [N, K, NB, layer, cb, byte offset, name (40 bytes)] (16 ints)
 constexpr int Q8DUMP_REC = 16;
 void q8dump_assign(mp_dev *dev, const char *name, mp::GemvP &g) {
-    g.q8dump = nullptr;
-    if (!dev->q8dump || !dev->q8dump_live || !g.Wq || dev->q8dump_n >= dev->q8dump_cap) return;
+    if (!dev->q8dump || !g.Wq || dev->q8dump_n >= dev->q8dump_cap) return;
     const int n = dev->q8dump_n++;
     g.q8dump = dev->q8dump + (size_t)n * dev->q8dump_slot;
     const int K = strncmp(name, "lt_in", 5) == 0 ? 768 : (strncmp(name, "lt_", 3) == 0 ? 256 : 768);
@@ -966,41 +971,313 @@ int alloc_batch(mp_dev *dev, int B, int Tmax, int max_steps, bool trace) {
     return MP_OK;
 }
 
-mp::GemvP gemv_base(mp_dev *dev) {
+// ------------------------------------------------------------------ the iteration's launch list
+// A decode iteration is a list of OpRec. build_iteration / build_lt decide which kernels it
+// consists of for the weight mode, batch size and knobs and fill their parameter structs;
+// launch_ops launches a list; the profiling API (mp_hip_profile_ops*, mp_hip_time_op)
+// replays the decode's own. The list is invariant per batch configuration: every varying
+// quantity (position, step, iteration counter, sampling settings) lives in device memory,
+// so it is built once per batch and one captured graph serves every frame.
+
+// MAGPIE_EAGER=1: launch the iteration's kernels directly instead of replaying
+// the captured graph (identical kernels and arguments; used under rocprofv3,
+// whose kernel tracer crashes on graph replays on this image).
+bool eager_mode() { return mp::env_int("MAGPIE_EAGER", 0) != 0; }
+// The knobs below are read when a list is built (the first decode of a batch
+// configuration), in eager mode as in graph mode.
+// MAGPIE_Q8_UNFUSED=1: the Q8_0 mode's SA and XA as separate launches (the fused forms
+// compute the same bits; tests/test_q8_fused_gpu.py compares them)
+bool q8_unfused() { return mp::env_int("MAGPIE_Q8_UNFUSED", 0) != 0; }
+// The SA in the QKV launch at 16 slots: MAGPIE_SA16 unset = the bf16 mode's, 1 = every
+// mode's, 0 = none (A/B; both forms compute the same bits). Round 3 kept it separate (bf16
+// B=16 20.1k vs 21.5k frames/s then); since round 4's single pollers the fused form is
+// faster: 31,891 -> 32,620 / 32,893 frames/s (qkv 4.54 + sa_attn 7.34 -> qkv_sa 11.05 us
+// per layer; gpurun_out/r06l_ops_bf16_b16*)
+bool sa16_fused(int weight_mode) { return mp::env_int("MAGPIE_SA16", weight_mode == MP_WEIGHTS_BF16) != 0; }
+// At 8 bf16 slots, which split states the split workgroups merge themselves (bit 0: SA, in
+// the QKV launch; bit 1: XA, in the O-projection's) rather than the consumers' prologues
+// (PRO_SA_MERGE, PRO_XA_LN): MAGPIE_MERGE8, default 3 (A/B; every setting the same bits)
+int split_merge8() { return mp::env_int("MAGPIE_MERGE8", 3); }
+// MAGPIE_LTQ8 (Q8_0 LT step, lt_slot_q8_kernel): 0 = o_net rows split over the workgroups
+// (y hand-off) and the FFN merge in the launch; 1 = every workgroup all o_net rows (no y
+// hand-off); 2 (default) = that up to 4 slots, and at batch 1 the FFN merge deferred to
+// the head's prologue. Every setting computes the same bits (tests/test_q8_fused_gpu.py).
+int ltq8_mode() { return mp::env_int("MAGPIE_LTQ8", 2); }
+
+// a quantised tensor's decode bytes per weight: Q8_0 34/32, Q4_0 nibble fragments 18/32
+double Fq(const mp::QW &w) { return w.nib ? 18.0 / 32.0 : 34.0 / 32.0; }
+
+// a zeroed GemvP with the model's constants and its slots' step and sampling state
+mp::GemvP gemv_base(const mp::Model &m, int NB, int *step, const mp::Sampling &smp, bool ignore_eos) {
     mp::GemvP g;
     memset(&g, 0, sizeof g);
-    g.eps = dev->m.eps;
-    g.nlayers = dev->m.dec_layers;
-    g.max_seq = dev->max_seq;
-    g.pos = dev->pos;
-    g.step = dev->step;
-    g.ndone = dev->ndone;
-    g.smp = mp::Sampling{dev->params.temperature >= 0.01f, dev->smpcfg, dev->argeos};
-    g.nslots = dev->NB;
-    g.ignore_eos = dev->params.ignore_eos;
-    g.audio_bos = dev->m.audio_bos;
-    g.audio_eos = dev->m.audio_eos;
+    g.eps = m.eps;
+    g.step = step;
+    g.smp = smp;
+    g.nslots = NB;
+    g.ignore_eos = ignore_eos;
+    g.audio_bos = m.audio_bos;
+    g.audio_eos = m.audio_eos;
     return g;
 }
 
-int enqueue_lt(mp_dev *dev, const mp::LtIo &io, int NB, hipStream_t s, std::vector<mp::OpRec> *ops);
-bool q8_unfused();
-bool sa16_fused(int weight_mode);
-int split_merge8();
+// Appends records to a launch list. q8dump: the GEMVs take MAGPIE_Q8DUMP slots (a decode
+// iteration's do, mp_hip_lt_sample's do not). dump: noted on every record added; build_lt
+// clears it on the records no MAGPIE_DUMP_LT state record follows.
+struct Emit {
+    mp_dev *dev;
+    std::vector<mp::OpRec> &out;
+    int NB;
+    bool q8dump;
+    mp::LtDumpP dump;
+    // one record: its kind, the kind's parameter struct (OpRec's member `par`), the
+    // algorithmic bytes (weights at their stored width, Q8_0: 34 B per 32; activations f32)
+    template <class P> mp::OpRec &add(const char *name, int kind, P mp::OpRec::*par, const P &p, double bytes) const {
+        mp::OpRec r{};
+        r.name = name; r.kind = kind; r.*par = p; r.B = NB; r.bytes = bytes; r.dump = dump;
+        out.push_back(r);
+        return out.back();
+    }
+    // a GEMV from the op table: a null entry is a batch size / weight mode without a kernel
+    int gemv(const char *name, mp::GemvFn fn, mp::GemvP g, double bytes) const {
+        if (!fn) return fail(dev, MP_ERR_UNSUPPORTED, std::string(name) + ": no kernel for this batch size / weight mode");
+        if (q8dump) q8dump_assign(dev, name, g);
+        add(name, mp::K_GEMV, &mp::OpRec::g, g, bytes).fn = fn;
+        return MP_OK;
+    }
+};
 
-// Enqueue one decode iteration: decoder step at pos (embedding codes_prev), LT
-// over 8 codebooks, finalize. When `record` is set, the op list is rebuilt for
-// measurement (mp_hip_time_op).
-int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record);
-int enqueue_iteration(mp_dev *dev, hipStream_t s, bool record) {
-    dev->q8dump_n = 0;
-    dev->q8dump_index.clear();
-    dev->q8dump_live = true;
-    const int rc = enqueue_iteration_body(dev, s, record);
-    dev->q8dump_live = false;
-    return rc;
+// The local transformer over one frame (magpie_local_transformer_sample_all,
+// magpie.cpp:1113-1317) + the frame bookkeeping (4320-4358), for NB slots whose
+// buffers `io` names. lt_only: in_proj of a given normalised hidden, codes only.
+int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &out, bool q8dump = false) {
+    const mp::Model &m = dev->m;
+    const bool b16 = mp::h16_mode(m.weight_mode);
+    const mp::OpTable &tb = mp::table_for(NB, m.weight_mode);
+    const mp::OpTableQ8 &tq = mp::table_q8(NB);
+    const double F = b16 ? 2.0 : 4.0, A = 4.0, act = (double)NB;
+    const mp::Sampling smp{io.sampling, io.cfg, io.argeos, io.amax};
+    const Emit e{dev, out, NB, q8dump, mp::LtDumpP{io.logits, io.ltX, io.ltY, io.lty2, io.ltq, io.codes_cur}};
+    auto base = [&](int cb) {
+        mp::GemvP g = gemv_base(m, NB, io.step, smp, io.ignore_eos);
+        g.cb = cb;
+        return g;
+    };
+    // position 0 of the f32 and bf16 modes: LN + [k_0 | vo_0]
+    auto kvo = [&]() {
+        mp::GemvP g = base(0);
+        g.W = m.lt_kvo; g.N = 512; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX; g.lnw = m.lt_norm_self;
+        g.lk = io.ltk; g.lv = io.ltv;
+        e.add("lt_kvo", mp::K_LTKVO, &mp::OpRec::g, g, A * (512.0 * 256) + A * act * (256 * 4));
+    };
+    // codebook cb's LT step in one launch (lt_ffn2_kernel, lt_slot_kernel) on FFN f
+    auto step2 = [&](int cb, const mp::LtFfnP &f) {
+        mp::LtFfn2P l2{};
+        l2.f = f;
+        l2.cb = cb; l2.ltX = io.ltX; l2.ltk = io.ltk; l2.ltv = io.ltv; l2.qkvtab = m.lt_qkvtab;
+        l2.votab = m.lt_votab; l2.ptab = m.lt_ptab; l2.lt_pos = m.lt_pos; l2.logits = io.logits;
+        l2.codes_cur = io.codes_cur; l2.step = io.step; l2.ignore_eos = io.ignore_eos;
+        l2.audio_bos = m.audio_bos; l2.audio_eos = m.audio_eos;
+        l2.smp = smp;
+        return l2;
+    };
+    // the one-workgroup merge of the FFN's partial sums (batches; at batch 1 the head's
+    // prologue merges them)
+    auto merge = [&](const mp::LtFfnP &lf) {
+        if (NB > 1) e.add("lt_merge", mp::K_LTMERGE, &mp::OpRec::lf, lf, A * act * (mp::LT_FFN_P * 256 + 512)).dump = {};
+    };
+    // codebook cb's head on y2. merged: the FFN merge is its prologue, y2 = y + the
+    // partial sums (src_elems of them per slot)
+    auto head = [&](int cb, mp::GemvFn fn, bool merged, int src_elems) {
+        mp::GemvP g = base(cb);
+        g.W = m.lt_out_w + (size_t)cb * 2024 * 256; g.N = 2024; g.bias = m.lt_out_b + (size_t)cb * 2024;
+        g.Wb = b16 ? m.pk_lt_out + (size_t)cb * pk_elems(2024, 256) : nullptr;
+        g.src = io.lty2; g.src_ld = 256; g.out = io.logits; g.out_ld = 2024;
+        if (m.lt_out8) {
+            g.Wq = m.lt_out8.pq + (size_t)cb * m.lt_out8.head_q; g.q4 = m.lt_out8.nib;
+            g.Wd = (const unsigned short *)((const char *)m.lt_out8.pd + (size_t)cb * q8p_head_d());
+        }
+        if (merged) { g.part = io.ltp; g.addsrc = io.ltY; }
+        return e.gemv("lt_e", fn, g,
+                      (m.lt_out8 ? Fq(m.lt_out8) : F) * (2024.0 * 256) + A * 2024 + A * act * (src_elems + 2024));
+    };
+    // f32 mode at batch 1: final LN + in_proj + position 0 + codebook 0's FFN step in one
+    // launch (lt_front_kernel: the same rows, the same arithmetic; 2 in-launch granule edges)
+    const bool front = f32_lt_mode(m) && NB == 1 && !io.lt_only && io.ltfg && io.iter;
+    if (!front) {
+        mp::GemvP g = base(0);
+        g.W = m.lt_in_w; g.N = 256; g.bias = m.lt_in_b; g.out = io.lt_s; g.out_ld = 9 * 256;
+        g.Wq = m.lt_in8.pq; g.Wd = m.lt_in8.pd; g.q4 = m.lt_in8.nib; g.Wb = m.pk_lt_in;  // pk_lt_in: F16 mode only
+        const double Fi = m.lt_in8 ? Fq(m.lt_in8) : m.pk_lt_in ? 2.0 : A;
+        if (io.lt_only) {
+            // in_proj of the caller's (already normalised) hidden (1161-1163)
+            g.src = io.hidden; g.src_ld = 768;
+            if (int rc = e.gemv("lt_inh", m.lt_in8 ? mp::q8_lt_inh_1 : m.pk_lt_in ? mp::f16_lt_inh_1 : mp::op_lt_inh_1, g,
+                                Fi * 256.0 * 768 + A * 256 + A * (768 + 256)))
+                return rc;
+        } else {
+            // final LN -> hidden (4394) fused into LT in_proj (1162-1163)
+            g.lnw = m.dec_norm_out; g.src = io.x; g.src_ld = 768; g.hidden_out = io.hidden;
+            if (io.trace) { g.trace = io.trace; g.trace_steps = io.trace_steps; g.step = io.step; }
+            if (int rc = e.gemv("lt_in0", m.lt_in8 ? tq.lt_in0 : tb.lt_in0, g,
+                                Fi * 256.0 * 768 + A * 256 + A * act * ((768 + 768 + 256))))
+                return rc;
+        }
+    }
+    if (m.weight_mode == MP_WEIGHTS_BF16) {
+        // bf16 mode: the f32 mode's position 0 (LN + [k_0 | vo_0]), then per codebook the
+        // LT step as LTS_P workgroups per slot (lt_slot_kernel: pick, f32 attention
+        // through the tables, bf16 FFN, partial sums merged by the slot's last
+        // workgroup) and the bf16 head: 2 launches per codebook at every batch size
+        kvo();
+        for (int cb = 0; cb < 8; ++cb) {
+            mp::LtFfn2P l2 = step2(cb, mp::LtFfnP{io.ltY, m.lt_norm_ff, nullptr, nullptr, m.eps, io.ltp, io.lty2});
+            // the partial sums merged by the head's prologue at batch 1 (32 KiB per head
+            // workgroup; 4 slots' 128 KiB took 11.5 us), through granules by the LT step
+            // itself above (the standalone LT API is batch 1: no iteration counter needed)
+            const bool head_merge = NB == 1;
+            l2.w1h = m.lt_ff1h; l2.w2h = m.lt_ff2h;
+            if (!head_merge) { l2.gh = io.ltgh; l2.iter = io.iter; l2.hx_err = io.hx_err; }
+            e.add("lt_slot", mp::K_LTSLOT, &mp::OpRec::l2, l2,
+                  F * (1024.0 * 256 * 2) + A * act * (cb ? 2024 + 4 * 256 + 2 * 256 * cb : 512) +
+                      A * act * (mp::LTS_P * 256 + 256));
+            if (int rc = head(cb, head_merge ? tb.lt_em : tb.lt_es, head_merge, head_merge ? mp::LTS_P * 256 : 256))
+                return rc;
+        }
+    } else if (f32_lt_mode(m)) {
+        // f32 mode: LN + [k_0 | vo_0] for position 0, then per codebook ONE launch for
+        // pick + attention + o_net + residual + FFN (lt_ffn2_kernel) and the head
+        if (!front) kvo();
+        for (int cb = 0; cb < 8; ++cb) {
+            const mp::LtFfn2P l2 = step2(cb, mp::LtFfnP{io.ltY, m.lt_norm_ff, m.lt_ff1, m.lt_ff2s, m.eps, io.ltp, io.lty2});
+            if (front && cb == 0) {
+                // lt_front_kernel: the final LN, in_proj, position 0 and codebook 0's FFN step
+                mp::LtFrontP fp{};
+                fp.l = l2; fp.x = io.x; fp.norm_out = m.dec_norm_out; fp.w_in = m.lt_in_w; fp.b_in = m.lt_in_b;
+                fp.lt_s = io.lt_s; fp.hidden_out = io.hidden; fp.lt_pos = m.lt_pos; fp.norm_self = m.lt_norm_self;
+                fp.w_kvo = m.lt_kvo; fp.gh = io.ltfg; fp.iter = io.iter; fp.hx_err = io.hx_err;
+                if (io.trace) { fp.trace = io.trace; fp.trace_steps = io.trace_steps; }
+                e.add("lt_front", mp::K_LTFRONT, &mp::OpRec::lf3, fp,
+                      A * (256.0 * 768 + 512.0 * 256 + 1024.0 * 256 * 2) + A * (768 * 2 + 256 * 4) +
+                          A * (mp::LT_FFN_P * 256));
+            } else {
+                e.add("lt_ffn2", mp::K_LTFFN2, &mp::OpRec::l2, l2,
+                      A * (1024.0 * 256 * 2) + A * act * (cb ? 2024 + 4 * 256 + 2 * 256 * cb : 512) +
+                          A * act * (mp::LT_FFN_P * 256 + 256));
+            }
+            merge(l2.f);
+            if (int rc = head(cb, NB == 1 ? mp::op_lt_em_1 : tb.lt_e, NB == 1, 256)) return rc;
+        }
+    } else if (m.weight_mode == MP_WEIGHTS_Q8 && m.lt_o8 && m.lt_out8 && m.lt_ff2q && !io.lt_only && io.ltyg) {
+        // Q8_0 mode: position 0's q|k|v (the Q8_0 GEMV), then per codebook the LT step as
+        // LTQ_P workgroups per slot (lt_slot_q8_kernel: pick, attention, Q8_0 o_net, F32
+        // FFN, partial sums merged through granules) and the Q8_0 head on its output
+        mp::GemvP g = base(0);
+        g.W = m.lt_qkv; g.N = 768; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX;
+        g.Wq = m.lt_qkv8.pq; g.Wd = m.lt_qkv8.pd; g.q4 = m.lt_qkv8.nib;
+        g.lnw = m.lt_norm_self; g.lq = io.ltq; g.lk = io.ltk; g.lv = io.ltv;
+        if (int rc = e.gemv("lt_a", tq.lt_a, g, Fq(m.lt_qkv8) * (768.0 * 256) + A * act * (256 * 3 + 768 + 256)))
+            return rc;
+        const int lm = ltq8_mode();
+        for (int cb = 0; cb < 8; ++cb) {
+            mp::LtSlotQ8P sp{};
+            sp.g = base(cb);
+            sp.g.logits = io.logits; sp.g.codes_cur = io.codes_cur; sp.g.qkvtab = m.lt_qkvtab; sp.g.ptab = m.lt_ptab;
+            sp.g.lt_pos = m.lt_pos; sp.g.ltk = io.ltk; sp.g.ltv = io.ltv; sp.g.lk = io.ltk; sp.g.lv = io.ltv;
+            sp.g.ltX = io.ltX;
+            sp.woq = m.lt_o8.q; sp.wod = m.lt_o8.d; sp.lnw = m.lt_norm_ff; sp.eps = m.eps; sp.w1 = m.lt_ff1;
+            sp.w2s = m.lt_ff2q; sp.y = io.ltY; sp.y2 = io.lty2; sp.gy = io.ltyg; sp.gp = io.ltgh;
+            sp.iter = io.iter; sp.hx_err = io.hx_err;
+            if (lm == 1 || (lm >= 2 && NB <= 4)) sp.wot = m.lt_o8t;  // (8+ slots: 512+ workgroups, the split rows)
+            if (lm >= 2 && NB == 1 && sp.wot) sp.part = io.ltp;
+            e.add("lt_slot_q8", mp::K_LTSLOTQ8, &mp::OpRec::lq8, sp,
+                  (34.0 / 32.0) * (256.0 * 256) + A * (1024.0 * 256 * 2) +
+                      A * act * (cb ? 2024 + 4 * 256 + 2 * 256 * cb : 512) + A * act * (mp::LTQ_P * 256 + 512));
+            // (sp.part: the FFN merge is the head's prologue)
+            if (int rc = head(cb, sp.part ? mp::q8_lt_em_1 : tq.lt_e, sp.part != nullptr, 256)) return rc;
+        }
+    } else
+    for (int cb = 0; cb < 8; ++cb) {
+        mp::GemvP g;
+        if (cb == 0) {
+            // position 0 (the hidden's in_proj): LN + q|k|v GEMV, then attention + o_net
+            g = base(0);
+            g.W = m.lt_qkv; g.Wb = m.pk_lt_qkv; g.N = 768; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX;
+            g.Wq = m.lt_qkv8.pq; g.Wd = m.lt_qkv8.pd; g.q4 = m.lt_qkv8.nib;
+            g.lnw = m.lt_norm_self; g.lq = io.ltq; g.lk = io.ltk; g.lv = io.ltv;
+            if (int rc = e.gemv("lt_a", m.lt_qkv8 ? tq.lt_a : tb.lt_a, g,
+                                (m.lt_qkv8 ? Fq(m.lt_qkv8) : F) * (768.0 * 256) + A * act * (256 * 3 + 768 + 256)))
+                return rc;
+            g = base(0);
+            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.ltq = io.ltq; g.ltk = io.ltk; g.ltv = io.ltv; g.out = io.ltY;
+            g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
+            g.out_ld = 256; g.addsrc = io.ltX;
+            if (int rc = e.gemv("lt_b", m.lt_o8 ? tq.lt_b : tb.lt_b, g,
+                                (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) + A * act * (256 * 5)))
+                return rc;
+        } else if (NB >= 8) {
+            // large batches: the per-slot pick + gathers + attention as one wave per slot
+            // (lt_pick_kernel), then o_net + residual; the same arithmetic as lt_bg
+            g = base(cb);
+            g.logits = io.logits; g.codes_cur = io.codes_cur; g.qkvtab = m.lt_qkvtab; g.ptab = m.lt_ptab;
+            g.lt_pos = m.lt_pos; g.ltk = io.ltk; g.ltv = io.ltv; g.lk = io.ltk; g.lv = io.ltv; g.ltX = io.ltX;
+            g.out = io.ltq;
+            e.add("lt_pick", mp::K_LTPICK, &mp::OpRec::g, g, A * act * (2024 + 4 * 256 + 2 * 256 * cb + 4 * 256));
+            g = base(cb);
+            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.src = io.ltq; g.src_ld = 256; g.out = io.ltY; g.out_ld = 256;
+            g.addsrc = io.ltX; g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
+            const bool f16 = m.weight_mode == MP_WEIGHTS_F16;
+            const mp::GemvFn bo = m.lt_o8 ? (NB == 16 ? mp::q8_lt_bo_16 : mp::q8_lt_bo_8)
+                                  : f16   ? (NB == 16 ? mp::f16_lt_bo_16 : mp::f16_lt_bo_8)
+                                  : b16   ? (NB == 16 ? mp::b16_lt_bo_16 : mp::b16_lt_bo_8)
+                                          : mp::op_lt_bo_8;
+            if (int rc = e.gemv("lt_bo", bo, g, (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) + A * act * (256 * 3))) return rc;
+        } else {
+            // position cb: codebook cb-1's pick, its q|k|v row gathered from the load-time
+            // table (no q|k|v GEMV), attention + o_net + residual, one launch
+            g = base(cb);
+            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.out = io.ltY; g.out_ld = 256;
+            g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
+            g.logits = io.logits; g.codes_cur = io.codes_cur; g.qkvtab = m.lt_qkvtab; g.ptab = m.lt_ptab;
+            g.lt_pos = m.lt_pos; g.ltk = io.ltk; g.ltv = io.ltv; g.lk = io.ltk; g.lv = io.ltv;
+            if (int rc = e.gemv("lt_bg", m.lt_o8 ? tq.lt_bg : tb.lt_bg, g,
+                                (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) +
+                                    A * act * (2024 + 3 * 256 + 2 * 256 * cb + 2 * 256 + 256)))
+                return rc;
+        }
+        // FFN up + GELU + FFN down: one launch of partial sums (f32 FFN weights), merged by
+        // the head's prologue at batch 1 or by a one-workgroup merge; bf16 mode: two GEMVs
+        const bool ffn1 = !b16;
+        if (ffn1) {
+            const mp::LtFfnP lf{io.ltY, m.lt_norm_ff, m.lt_ff1, m.lt_ff2s, m.eps, io.ltp, io.lty2};
+            e.add("lt_ffn", mp::K_LTFFN, &mp::OpRec::lf, lf, A * (1024.0 * 256 * 2) + A * act * (256 + mp::LT_FFN_P * 256)).dump = {};
+            merge(lf);
+        } else {
+            g = base(cb);
+            g.W = m.lt_ff1; g.Wb = m.pk_lt_ff1; g.N = 1024; g.lnw = m.lt_norm_ff; g.src = io.ltY; g.src_ld = 256;
+            g.out = io.ltf; g.out_ld = 1024;
+            if (int rc = e.gemv("lt_c", tb.lt_c, g, F * (1024.0 * 256) + A * act * ((256 + 1024)))) return rc;
+            g = base(cb);
+            g.W = m.lt_ff2; g.Wb = m.pk_lt_ff2; g.N = 256; g.src = io.ltf; g.src_ld = 1024; g.out = io.lty2;
+            g.out_ld = 256; g.addsrc = io.ltY;
+            if (int rc = e.gemv("lt_d", tb.lt_d, g, F * (256.0 * 1024) + A * act * ((1024 + 512)))) return rc;
+        }
+        // (batch 1: the FFN merge, lt_ffn_kernel's interleaved partials, is the head's prologue)
+        const bool em = ffn1 && NB == 1;
+        if (int rc = head(cb, em ? (m.lt_out8 ? mp::q8_lt_emf_1 : mp::op_lt_em_1) : (m.lt_out8 ? tq.lt_e : tb.lt_e), em, 256))
+            return rc;
+    }
+    mp::FinP f{io.logits, io.codes_cur, io.codes_prev, io.codes_out, io.step, io.pos, io.done, io.nframes, io.ndone,
+               io.max_steps, io.ignore_eos, m.audio_bos, m.audio_eos, NB, smp, io.emit_eos, io.lt_only,
+               io.lt_only ? nullptr : io.ndone + 1};
+    if (!io.lt_only) { f.emb = m.audio_emb; f.pos_emb = m.dec_pos; f.x = io.x; f.pos_rows = m.dec_pos_rows; }  // the next frame's input
+    e.add("finalize", mp::K_FIN, &mp::OpRec::f, f, A * act * 2024).dump = {};
+    return MP_OK;
 }
-int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record) {
+
+// One decode iteration: decoder step at pos (embedding codes_prev), LT over 8 codebooks,
+// finalize. Assigns the MAGPIE_Q8DUMP slots of its Q8_0 GEMVs.
+int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     const mp::Model &m = dev->m;
     const int NB = dev->NB, L = m.dec_layers;
     const bool b16 = mp::h16_mode(m.weight_mode);  // 16-bit MFMA family (bf16 or F16 weights)
@@ -1008,26 +1285,32 @@ int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record) {
     const mp::OpTableQ8 &tq = mp::table_q8(NB);
     // algorithmic bytes: weights at their stored width (Q8_0: 34 B per 32), activations f32
     const double F = b16 ? 2.0 : 4.0, A = 4.0, act = (double)NB;
-    // a quantised tensor's decode bytes per weight: Q8_0 34/32, Q4_0 nibble fragments 18/32
-    auto Fq = [](const mp::QW &w) { return w.nib ? 18.0 / 32.0 : 34.0 / 32.0; };
-    if (record) dev->ops.clear();
-    auto run = [&](const char *name, mp::GemvFn fn, const mp::GemvP &g0, double bytes) -> int {
-        mp::GemvP g = g0;
-        q8dump_assign(dev, name, g);
-        if (record) {
-            mp::OpRec r{};
-            r.name = name; r.kind = mp::K_GEMV; r.fn = fn; r.g = g; r.B = NB; r.bytes = bytes;
-            dev->ops.push_back(r);
-        }
-        if (!fn) return fail(dev, MP_ERR_UNSUPPORTED, std::string(name) + ": no kernel for this batch size / weight mode");
-        HIPCHK(fn(g, s));
-        return MP_OK;
+    const bool sampling = dev->params.temperature >= 0.01f;
+    const mp::Sampling smp{sampling, dev->smpcfg, dev->argeos};
+    const Emit e{dev, out, NB, true, mp::LtDumpP{}};
+    dev->q8dump_n = 0;
+    dev->q8dump_index.clear();
+    auto base = [&](int l) {
+        mp::GemvP g = gemv_base(m, NB, dev->step, smp, dev->params.ignore_eos);
+        g.layer = l; g.nlayers = L; g.max_seq = dev->max_seq; g.pos = dev->pos; g.ndone = dev->ndone;
+        return g;
     };
-    int rc;
+    // bf16 mode at 8 and 16 slots: the SA and XA split states are merged once, by the split
+    // workgroups themselves through granules (sa_merge_split, xa_merge_split: each merges
+    // 1 / SPLITS of its head's / slot's outputs), not by every O-projection / FFN-up
+    // workgroup's prologue (196 / 245 KiB each at 16 slots); the same arithmetic, so
+    // batches still reproduce single runs (at 8 slots the SA merge runs in the QKV launch)
+    const bool mb16 = m.weight_mode == MP_WEIGHTS_BF16 && !dev->xa_direct;
+    const bool merge_sa = mb16 && (NB >= 16 || (NB == 8 && (split_merge8() & 1)));
+    const bool merge_xa = mb16 && (NB >= 16 || (NB == 8 && (split_merge8() & 2)));
+    // (Q8_0: the same hand-off in the int8 MFMA launch, mp_decode_q8.hip; MAGPIE_Q8_UNFUSED=1
+    // keeps the separate launches, which compute the same bits)
+    const bool q8_fuse = !q8_unfused();
+    // (at 16 slots too unless MAGPIE_SA16=0, sa16_fused; both forms compute the same bits)
+    const bool sa16 = NB < 16 || sa16_fused(m.weight_mode);
     for (int l = 0; l < L; ++l) {
         const mp::DecLayerW &W = m.dec[l];
-        mp::GemvP g = gemv_base(dev);
-        g.layer = l;
+        mp::GemvP g = base(l);
         // LN + QKV (+ frame embedding on layer 0) + KV append   (3415-3442)
         g.W = W.qkv; g.Wb = b16 ? m.pk_qkv[l] : nullptr; g.N = 2304; g.lnw = W.norm_self; g.src = dev->x; g.src_ld = 768; g.out = dev->q;
         g.Wq = W.qkv8.pq; g.Wd = W.qkv8.pd; g.q4 = W.qkv8.nib;
@@ -1037,41 +1320,19 @@ int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record) {
         // self-attention over the cache, split over keys (3457-3476); the f32 family runs
         // it in the QKV launch on a hand-off of q|k|v (EPI_QKV_SA), the others separately
         mp::AttnP a{dev->q, dev->kc, dev->vc, l, L, dev->max_seq, dev->pos, dev->kv16, dev->sa_part};
-        // bf16 mode at 8 and 16 slots: the SA and XA split states are merged once, by the split
-        // workgroups themselves through granules (sa_merge_split, xa_merge_split: each merges
-        // 1 / SPLITS of its head's / slot's outputs), not by every O-projection / FFN-up
-        // workgroup's prologue (196 / 245 KiB each at 16 slots); the same arithmetic, so
-        // batches still reproduce single runs (at 8 slots the SA merge runs in the QKV launch)
-        const bool mb16 = m.weight_mode == MP_WEIGHTS_BF16 && !dev->xa_direct;
-        const bool merge_sa = mb16 && (NB >= 16 || (NB == 8 && (split_merge8() & 1)));
-        const bool merge_xa = mb16 && (NB >= 16 || (NB == 8 && (split_merge8() & 2)));
         if (merge_sa) { a.merged = dev->sa_out; a.gh = dev->sagh; a.iter = dev->ndone + 1; a.hx_err = dev->ndone + 2; }
-        // (at 16 slots too unless MAGPIE_SA16=0, sa16_fused; both forms compute the same bits)
-        // (Q8_0: the same hand-off in the int8 MFMA launch, mp_decode_q8.hip; MAGPIE_Q8_UNFUSED=1
-        // keeps the separate launches, which compute the same bits)
-        const bool q8_fuse = !q8_unfused();
-        const bool sa_in_qkv = (W.qkv8 ? q8_fuse && tq.qkv_sa : tb.qkv_sa != nullptr) && (NB < 16 || sa16_fused(m.weight_mode));
-        {
-            mp::GemvFn fn = W.qkv8 ? tq.qkv : tb.qkv;
-            if (sa_in_qkv) {
-                fn = W.qkv8 ? tq.qkv_sa : tb.qkv_sa;
-                g.sa = a; g.qh = dev->qh; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
-            }
-            if ((rc = run(sa_in_qkv ? "qkv_sa" : "qkv", fn, g,
-                          (W.qkv8 ? Fq(W.qkv8) : F) * (2304.0 * 768) + A * act * ((768 + 2304)))) != MP_OK) return rc;
-            if (sa_in_qkv && record) dev->ops.back().add_sa = true;
-        }
-        if (!sa_in_qkv) {
-        if (record) {
-            mp::OpRec r{};
-            r.name = "sa_attn"; r.kind = mp::K_ATTN; r.a = a; r.B = NB;
-            r.bytes = -1;  // depends on the live cache length; computed at timing time
-            dev->ops.push_back(r);
-        }
-        HIPCHK(mp::op_sa_attn(a, NB, s));
+        const bool sa_in_qkv = (W.qkv8 ? q8_fuse && tq.qkv_sa : tb.qkv_sa != nullptr) && sa16;
+        const double qkv_bytes = (W.qkv8 ? Fq(W.qkv8) : F) * (2304.0 * 768) + A * act * ((768 + 2304));
+        if (sa_in_qkv) {
+            g.sa = a; g.qh = dev->qh; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
+            if (int rc = e.gemv("qkv_sa", W.qkv8 ? tq.qkv_sa : tb.qkv_sa, g, qkv_bytes)) return rc;
+            out.back().add_sa = true;
+        } else {
+            if (int rc = e.gemv("qkv", W.qkv8 ? tq.qkv : tb.qkv, g, qkv_bytes)) return rc;
+            e.add("sa_attn", mp::K_ATTN, &mp::OpRec::a, a, -1);  // bytes: the live cache length's, computed at timing time
         }
         // O-proj + residual (3479, 3509)
-        g = gemv_base(dev); g.layer = l;
+        g = base(l);
         g.W = W.o; g.Wb = b16 ? m.pk_o[l] : nullptr; g.N = 768; g.resid = dev->x; g.part = dev->sa_part;
         g.Wq = W.o8.pq; g.Wd = W.o8.pd; g.q4 = W.o8.nib;
         // split-K partial tiles (MP_OPROJ_KS > 1 builds only): the plain O-projection then
@@ -1097,9 +1358,9 @@ int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record) {
             xq.wq = W.xq8.q; xq.wqd = W.xq8.d; xq.lnw = W.norm_xq; xq.eps = m.eps; xq.qg = dev->xqh;
             xq.qin = NB <= mp::XQ8_QIN_NB;  // small batches: q in the attention workgroups (one hand-off)
             g.xq8 = xq; g.xh = dev->xh; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
-            if ((rc = run("oproj_xa_q8", tq.oproj_xq, g,
-                          Fq(W.o8) * (768.0 * 768) + A * act * (768 * 3) + (34.0 / 32.0) * (2.0 * 128 * 768) +
-                              A * act * (768 + 2.0 * 128 * dev->Tmax))) != MP_OK)
+            if (int rc = e.gemv("oproj_xa_q8", tq.oproj_xq, g,
+                                Fq(W.o8) * (768.0 * 768) + A * act * (768 * 3) + (34.0 / 32.0) * (2.0 * 128 * 768) +
+                                    A * act * (768 + 2.0 * 128 * dev->Tmax)))
                 return rc;
         } else if (xa_in_oproj) {
             // f32: the fused XA rides in the O-projection's launch on a hand-off of x1
@@ -1110,67 +1371,53 @@ int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record) {
             }
             if (merge_xa) { xp.x2 = dev->x2; xp.gh = dev->xagh; }  // x2 merged by the XA workgroups
             g.xa = xp; g.xh = dev->xh; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
-            if ((rc = run("oproj_xa", fn, g, F * (768.0 * 768) + A * act * (768 * 3) + xa_bytes)) != MP_OK)
-                return rc;
-        } else if ((rc = run("oproj", W.o8 ? tq.oproj : tb.oproj, g,
-                             (W.o8 ? Fq(W.o8) : F) * (768.0 * 768) + A * act * (768 * 3))) != MP_OK) {
+            if (int rc = e.gemv("oproj_xa", fn, g, F * (768.0 * 768) + A * act * (768 * 3) + xa_bytes)) return rc;
+        } else if (int rc = e.gemv("oproj", W.o8 ? tq.oproj : tb.oproj, g,
+                                   (W.o8 ? Fq(W.o8) : F) * (768.0 * 768) + A * act * (768 * 3))) {
             return rc;
         }
         if (xa_dir && !xq8_in_oproj) {
             // cross-attention as ggml computes it (1713-1767): q = q_net LN(x) (GEMV), then
             // x2 = x + o_net attn(q, K, V) (xa_q8_kernel / xa_f32_kernel); Q8_0 q_net / o_net
             // quantise their activations, else f32 (the bf16 mode keeps XA f32)
-            g = gemv_base(dev); g.layer = l;
+            g = base(l);
             g.W = W.xq; g.Wq = W.xq8.pq; g.Wd = W.xq8.pd; g.q4 = W.xq8.nib; g.N = 128; g.lnw = W.norm_xq; g.src = dev->x; g.src_ld = 768;
             g.out = dev->xqb; g.out_ld = 128;
             const double Fx = W.xq8 ? Fq(W.xq8) : A;
-            if ((rc = run("xq", W.xq8 ? tq.xq : tb.xq, g, Fx * (128.0 * 768) + A * act * (768 + 128))) != MP_OK)
-                return rc;
+            if (int rc = e.gemv("xq", W.xq8 ? tq.xq : tb.xq, g, Fx * (128.0 * 768) + A * act * (768 + 128))) return rc;
             mp::XaQ8P xq{};
             xq.x = dev->x; xq.x2 = dev->x2; xq.q = dev->xqb; xq.xak = dev->xak; xq.xav = dev->xav; xq.T = dev->T;
             xq.Tmax = dev->Tmax; xq.layer = l; xq.nlayers = L;
             if (W.xq8) { xq.wo = W.xo8.q; xq.wod = W.xo8.d; }
             else xq.wof = W.xo;
-            if (record) {
-                mp::OpRec r{};
-                r.name = W.xq8 ? "xa_q8" : "xa_dir"; r.kind = mp::K_XAQ8; r.xq = xq; r.B = NB;
-                r.bytes = Fx * (768.0 * 128) + A * act * (128.0 + 768 * 2 + 2.0 * 128 * dev->Tmax);
-                dev->ops.push_back(r);
-            }
-            HIPCHK(mp::op_xa_q8(xq, NB, s));
+            e.add(W.xq8 ? "xa_q8" : "xa_dir", mp::K_XAQ8, &mp::OpRec::xq, xq,
+                  Fx * (768.0 * 128) + A * act * (128.0 + 768 * 2 + 2.0 * 128 * dev->Tmax));
         } else if (!xa_in_oproj && !xq8_in_oproj) {
             // cross-attention, fused (1713-1767, 3513-3519): x2 = x + o_net(attn(q_net(LN(x))))
-            if (record) {
-                mp::OpRec r{};
-                r.name = "xa"; r.kind = mp::K_XA; r.x = xp; r.B = NB;
-                r.bytes = xa_bytes;
-                dev->ops.push_back(r);
-            }
-            HIPCHK(mp::op_xa(xp, NB, s));
+            e.add("xa", mp::K_XA, &mp::OpRec::x, xp, xa_bytes);
         }
         // LN + FFN up + GELU (1796-1799)
-        g = gemv_base(dev); g.layer = l;
+        g = base(l);
         g.W = W.ff1; g.Wb = b16 ? m.pk_ff1[l] : nullptr; g.N = 3072; g.lnw = W.norm_ff; g.out = dev->h; g.out_ld = 3072;
+        if (b16) g.out_b16 = dev->h_b16;  // GELU output stored bf16 / f16 (what FFN down rounds it to)
         if (xa_dir || merge_xa) {  // x2 materialised by the direct XA / the XA tail's merge
             g.src = dev->x2; g.src_ld = 768;
-            if (b16) g.out_b16 = dev->h_b16;
-            if ((rc = run("ff1", tb.ff1, g, F * (3072.0 * 768) + A * act * ((768 + 3072)))) != MP_OK) return rc;
+            if (int rc = e.gemv("ff1", tb.ff1, g, F * (3072.0 * 768) + A * act * ((768 + 3072)))) return rc;
         } else {      // x2 = x + merged XA split states, stored by block 0 for the FFN residual
             g.src = dev->x; g.src_ld = 768; g.part = dev->xa_part; g.xres = dev->x2;
-            if (b16) g.out_b16 = dev->h_b16;  // GELU output stored bf16 / f16 (what FFN down rounds it to)
-            if ((rc = run("ff1", tb.ff1x, g,
-                          F * (3072.0 * 768) + A * act * (768 * 2 + 3072 + mp::XA_SPLITS * mp::XA_PART))) != MP_OK)
+            if (int rc = e.gemv("ff1", tb.ff1x, g,
+                                F * (3072.0 * 768) + A * act * (768 * 2 + 3072 + mp::XA_SPLITS * mp::XA_PART)))
                 return rc;
         }
         // FFN down + residual (1805, 3525): x = x2 + W2 h
-        g = gemv_base(dev); g.layer = l;
+        g = base(l);
         g.W = W.ff2; g.Wb = b16 ? m.pk_ff2[l] : nullptr; g.N = 768; g.src = dev->h; g.src_ld = 3072; g.out = dev->x; g.out_ld = 768; g.addsrc = dev->x2;
         if (b16) {
             g.src = nullptr; g.src_b16 = dev->h_b16;
             // split-K partial tiles (the FFN-down half of kgh: each op its own granules)
             g.kgh = dev->kgh + (size_t)(768 / 16) * mp::KGH_MAX_KS * 256; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
         }
-        if ((rc = run("ff2", tb.ff2, g, F * (768.0 * 3072) + A * act * ((3072 + 2 * 768)))) != MP_OK) return rc;
+        if (int rc = e.gemv("ff2", tb.ff2, g, F * (768.0 * 3072) + A * act * ((3072 + 2 * 768)))) return rc;
     }
     mp::LtIo io{};
     io.x = dev->x; io.hidden = dev->hidden; io.trace = dev->trace; io.trace_steps = dev->max_steps + 1;
@@ -1180,390 +1427,56 @@ int enqueue_iteration_body(mp_dev *dev, hipStream_t s, bool record) {
     io.codes_cur = dev->codes_cur; io.codes_prev = dev->codes_prev; io.codes_out = dev->codes_out; io.step = dev->step;
     io.pos = dev->pos; io.done = dev->done; io.nframes = dev->nframes; io.ndone = dev->ndone; io.argeos = dev->argeos;
     io.amax = dev->amax; io.cfg = dev->smpcfg;
-    io.sampling = dev->params.temperature >= 0.01f; io.ignore_eos = dev->params.ignore_eos;
+    io.sampling = sampling; io.ignore_eos = dev->params.ignore_eos;
     io.emit_eos = dev->params.emit_eos_frame; io.max_steps = dev->max_steps; io.lt_only = false;
-    return enqueue_lt(dev, io, NB, s, record ? &dev->ops : nullptr);
+    return build_lt(dev, io, NB, out, true);
 }
 
-// The local transformer over one frame (magpie_local_transformer_sample_all,
-// magpie.cpp:1113-1317) + the frame bookkeeping (4320-4358), for NB slots whose
-// buffers `io` names. lt_only: in_proj of a given normalised hidden, codes only.
-// MAGPIE_EAGER=1: launch the iteration's kernels directly instead of replaying
-// the captured graph (identical kernels and arguments; used under rocprofv3,
-// whose kernel tracer crashes on graph replays on this image).
-bool eager_mode() { return mp::env_int("MAGPIE_EAGER", 0) != 0; }
-// MAGPIE_Q8_UNFUSED=1: the Q8_0 mode's SA and XA as separate launches (the fused forms
-// compute the same bits; tests/test_q8_fused_gpu.py compares them)
-bool q8_unfused() { return mp::env_int("MAGPIE_Q8_UNFUSED", 0) != 0; }
-// The SA in the QKV launch at 16 slots: MAGPIE_SA16 unset = the bf16 mode's, 1 = every
-// mode's, 0 = none (A/B; both forms compute the same bits). Round 3 kept it separate (bf16
-// B=16 20.1k vs 21.5k frames/s then); since round 4's single pollers the fused form is
-// faster: 31,891 -> 32,620 / 32,893 frames/s (qkv 4.54 + sa_attn 7.34 -> qkv_sa 11.05 us
-// per layer; gpurun_out/r06l_ops_bf16_b16*)
-bool sa16_fused(int weight_mode) { return mp::env_int("MAGPIE_SA16", weight_mode == MP_WEIGHTS_BF16) != 0; }
-// At 8 bf16 slots, which split states the split workgroups merge themselves (bit 0: SA, in
-// the QKV launch; bit 1: XA, in the O-projection's) rather than the consumers' prologues
-// (PRO_SA_MERGE, PRO_XA_LN): MAGPIE_MERGE8, default 3 (A/B; every setting the same bits)
-int split_merge8() { return mp::env_int("MAGPIE_MERGE8", 3); }
-// MAGPIE_LTQ8 (Q8_0 LT step, lt_slot_q8_kernel): 0 = o_net rows split over the workgroups
-// (y hand-off) and the FFN merge in the launch; 1 = every workgroup all o_net rows (no y
-// hand-off); 2 (default) = that up to 4 slots, and at batch 1 the FFN merge deferred to
-// the head's prologue. Every setting computes the same bits (tests/test_q8_fused_gpu.py).
-int ltq8_mode() { return mp::env_int("MAGPIE_LTQ8", 2); }
+// one record, launched on s
+hipError_t launch_rec(const mp::OpRec &r, hipStream_t s) {
+    switch (r.kind) {
+    case mp::K_GEMV: return r.fn(r.g, s);
+    case mp::K_ATTN: return mp::op_sa_attn(r.a, r.B, s);
+    case mp::K_XA: return mp::op_xa(r.x, r.B, s);
+    case mp::K_XAQ8: return mp::op_xa_q8(r.xq, r.B, s);
+    case mp::K_LTFFN: return mp::op_lt_ffn(r.lf, r.B, s);
+    case mp::K_LTMERGE: return mp::op_lt_merge(r.lf, r.B, s);
+    case mp::K_LTPICK: return mp::op_lt_pick(r.g, r.B, s);
+    case mp::K_LTFFN2: return mp::op_lt_ffn2(r.l2, r.B, s);
+    case mp::K_LTSLOT: return mp::op_lt_slot(r.l2, r.B, s);
+    case mp::K_LTFRONT: return mp::op_lt_front(r.lf3, s);
+    case mp::K_LTSLOTQ8: return mp::op_lt_slot_q8(r.lq8, r.B, s);
+    case mp::K_LTKVO: return mp::op_lt_kvo(r.g, r.B, s);
+    case mp::K_EMBED: return mp::op_embed(r.e, r.B, s);
+    case mp::K_FIN: return mp::op_finalize(r.f, r.B, s);
+    }
+    return hipErrorInvalidValue;
+}
 
 // Diagnostics (MAGPIE_EAGER=1 and MAGPIE_DUMP_LT=file): after every launch of
 // the local transformer, slot 0's LT state is appended to the file as f32
 // records [logits 2024 | codes_cur 8 (int bits) | ltX | ltY | lty2 | ltq 256 each].
-void dump_lt(const mp::LtIo &io, hipStream_t s) {
-    const char *path = getenv("MAGPIE_DUMP_LT");
-    if (!path || !eager_mode() || hipStreamSynchronize(s) != hipSuccess) return;
+void dump_lt(const mp::LtDumpP &d, const char *path, hipStream_t s) {
+    if (hipStreamSynchronize(s) != hipSuccess) return;
     std::vector<float> rec(2024 + 8 + 4 * 256);
     float *p = rec.data();
     auto get = [&](const void *src, size_t n) {
         if (hipMemcpy(p, src, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return;
         p += n;
     };
-    get(io.logits, 2024); get(io.codes_cur, 8); get(io.ltX, 256); get(io.ltY, 256); get(io.lty2, 256); get(io.ltq, 256);
+    get(d.logits, 2024); get(d.codes_cur, 8); get(d.ltX, 256); get(d.ltY, 256); get(d.lty2, 256); get(d.ltq, 256);
     if (FILE *fp = fopen(path, "ab")) { fwrite(rec.data(), 4, rec.size(), fp); fclose(fp); }
 }
 
-int enqueue_lt(mp_dev *dev, const mp::LtIo &io, int NB, hipStream_t s, std::vector<mp::OpRec> *ops) {
-    const mp::Model &m = dev->m;
-    const bool b16 = mp::h16_mode(m.weight_mode);
-    const mp::OpTable &tb = mp::table_for(NB, m.weight_mode);
-    const mp::OpTableQ8 &tq = mp::table_q8(NB);
-    const double F = b16 ? 2.0 : 4.0, A = 4.0, act = (double)NB;
-    // a quantised tensor's decode bytes per weight: Q8_0 34/32, Q4_0 nibble fragments 18/32
-    auto Fq = [](const mp::QW &w) { return w.nib ? 18.0 / 32.0 : 34.0 / 32.0; };
-    auto run = [&](const char *name, mp::GemvFn fn, const mp::GemvP &g0, double bytes) -> int {
-        mp::GemvP g = g0;
-        q8dump_assign(dev, name, g);
-        if (ops) {
-            mp::OpRec r{};
-            r.name = name; r.kind = mp::K_GEMV; r.fn = fn; r.g = g; r.B = NB; r.bytes = bytes;
-            ops->push_back(r);
-        }
-        if (!fn) return fail(dev, MP_ERR_UNSUPPORTED, std::string(name) + ": no kernel for this batch size / weight mode");
-        HIPCHK(fn(g, s));
-        dump_lt(io, s);
-        return MP_OK;
-    };
-    auto base = [&]() {
-        mp::GemvP g;
-        memset(&g, 0, sizeof g);
-        g.eps = m.eps;
-        g.step = io.step;
-        g.smp = mp::Sampling{io.sampling, io.cfg, io.argeos, io.amax};
-        g.nslots = NB;
-        g.ignore_eos = io.ignore_eos;
-        g.audio_bos = m.audio_bos;
-        g.audio_eos = m.audio_eos;
-        return g;
-    };
-    int rc;
-    // f32 mode at batch 1: final LN + in_proj + position 0 + codebook 0's FFN step in one
-    // launch (lt_front_kernel: the same rows, the same arithmetic; 2 in-launch granule edges)
-    const bool front = f32_lt_mode(m) && NB == 1 && !io.lt_only && io.ltfg && io.iter;
-    {
-        mp::GemvP g = base();
-        g.W = m.lt_in_w; g.N = 256; g.bias = m.lt_in_b; g.out = io.lt_s; g.out_ld = 9 * 256;
-        g.Wq = m.lt_in8.pq; g.Wd = m.lt_in8.pd; g.q4 = m.lt_in8.nib; g.Wb = m.pk_lt_in;  // pk_lt_in: F16 mode only
-        const double Fi = m.lt_in8 ? Fq(m.lt_in8) : m.pk_lt_in ? 2.0 : A;
-        if (io.lt_only) {
-            // in_proj of the caller's (already normalised) hidden (1161-1163)
-            g.src = io.hidden; g.src_ld = 768;
-            if ((rc = run("lt_inh", m.lt_in8 ? mp::q8_lt_inh_1 : m.pk_lt_in ? mp::f16_lt_inh_1 : mp::op_lt_inh_1, g,
-                          Fi * 256.0 * 768 + A * 256 + A * (768 + 256))) != MP_OK)
-                return rc;
-        } else if (front) {
-            // f32, batch 1: lt_front_kernel below runs the final LN, in_proj, position 0 and
-            // codebook 0's FFN step in one launch
-        } else {
-            // final LN -> hidden (4394) fused into LT in_proj (1162-1163)
-            g.lnw = m.dec_norm_out; g.src = io.x; g.src_ld = 768; g.hidden_out = io.hidden;
-            if (io.trace) { g.trace = io.trace; g.trace_steps = io.trace_steps; g.step = io.step; }
-            if ((rc = run("lt_in0", m.lt_in8 ? tq.lt_in0 : tb.lt_in0, g,
-                          Fi * 256.0 * 768 + A * 256 + A * act * ((768 + 768 + 256)))) != MP_OK)
-                return rc;
-        }
+// Launch a list on s: the only place outside the profiling functions that launches a
+// decode kernel.
+int launch_ops(mp_dev *dev, const std::vector<mp::OpRec> &ops, hipStream_t s) {
+    const char *dump = eager_mode() ? getenv("MAGPIE_DUMP_LT") : nullptr;
+    for (const mp::OpRec &r : ops) {
+        const hipError_t err = launch_rec(r, s);
+        if (err != hipSuccess) return fail(dev, MP_ERR_HIP, r.name + " failed: " + hipGetErrorString(err));
+        if (dump && r.dump.logits) dump_lt(r.dump, dump, s);
     }
-    if (m.weight_mode == MP_WEIGHTS_BF16) {
-        // bf16 mode: the f32 mode's position 0 (LN + [k_0 | vo_0]), then per codebook the
-        // LT step as LTS_P workgroups per slot (lt_slot_kernel: pick, f32 attention
-        // through the tables, bf16 FFN, partial sums merged by the slot's last
-        // workgroup) and the bf16 head: 2 launches per codebook at every batch size
-        mp::GemvP g = base(); g.cb = 0;
-        g.W = m.lt_kvo; g.N = 512; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX; g.lnw = m.lt_norm_self;
-        g.lk = io.ltk; g.lv = io.ltv;
-        if (ops) {
-            mp::OpRec r{};
-            r.name = "lt_kvo"; r.kind = mp::K_LTKVO; r.g = g; r.B = NB;
-            r.bytes = A * (512.0 * 256) + A * act * (256 * 4);
-            ops->push_back(r);
-        }
-        HIPCHK(mp::op_lt_kvo(g, NB, s));
-        dump_lt(io, s);
-        for (int cb = 0; cb < 8; ++cb) {
-            mp::LtFfn2P l2{};
-            l2.f = mp::LtFfnP{io.ltY, m.lt_norm_ff, nullptr, nullptr, m.eps, io.ltp, io.lty2};
-            // the partial sums merged by the head's prologue at batch 1 (32 KiB per head
-            // workgroup; 4 slots' 128 KiB took 11.5 us), through granules by the LT step
-            // itself above (the standalone LT API is batch 1: no iteration counter needed)
-            const bool head_merge = NB == 1;
-            l2.w1h = m.lt_ff1h; l2.w2h = m.lt_ff2h;
-            if (!head_merge) { l2.gh = io.ltgh; l2.iter = io.iter; l2.hx_err = io.hx_err; }
-            l2.cb = cb; l2.ltX = io.ltX; l2.ltk = io.ltk; l2.ltv = io.ltv; l2.qkvtab = m.lt_qkvtab;
-            l2.votab = m.lt_votab; l2.ptab = m.lt_ptab; l2.lt_pos = m.lt_pos; l2.logits = io.logits;
-            l2.codes_cur = io.codes_cur; l2.step = io.step; l2.ignore_eos = io.ignore_eos;
-            l2.audio_bos = m.audio_bos; l2.audio_eos = m.audio_eos;
-            l2.smp = mp::Sampling{io.sampling, io.cfg, io.argeos, io.amax};
-            if (ops) {
-                mp::OpRec r{};
-                r.name = "lt_slot"; r.kind = mp::K_LTSLOT; r.l2 = l2; r.B = NB;
-                r.bytes = F * (1024.0 * 256 * 2) + A * act * (cb ? 2024 + 4 * 256 + 2 * 256 * cb : 512) +
-                          A * act * (mp::LTS_P * 256 + 256);
-                ops->push_back(r);
-            }
-            HIPCHK(mp::op_lt_slot(l2, NB, s));
-            dump_lt(io, s);
-            g = base(); g.cb = cb;
-            g.W = m.lt_out_w + (size_t)cb * 2024 * 256; g.N = 2024; g.bias = m.lt_out_b + (size_t)cb * 2024;
-            g.Wb = m.pk_lt_out + (size_t)cb * pk_elems(2024, 256);
-            g.src = io.lty2; g.src_ld = 256; g.out = io.logits; g.out_ld = 2024;
-            if (head_merge) { g.part = io.ltp; g.addsrc = io.ltY; }
-            if ((rc = run("lt_e", head_merge ? tb.lt_em : tb.lt_es, g,
-                          F * (2024.0 * 256) + A * 2024 + A * act * ((head_merge ? mp::LTS_P * 256 : 256) + 2024))) != MP_OK)
-                return rc;
-        }
-    } else if (f32_lt_mode(m)) {
-        // f32 mode: LN + [k_0 | vo_0] for position 0, then per codebook ONE launch for
-        // pick + attention + o_net + residual + FFN (lt_ffn2_kernel) and the head
-        mp::GemvP g = base(); g.cb = 0;
-        g.W = m.lt_kvo; g.N = 512; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX; g.lnw = m.lt_norm_self;
-        g.lk = io.ltk; g.lv = io.ltv;
-        if (!front) {
-            if (ops) {
-                mp::OpRec r{};
-                r.name = "lt_kvo"; r.kind = mp::K_LTKVO; r.g = g; r.B = NB;
-                r.bytes = A * (512.0 * 256) + A * act * (256 * 4);
-                ops->push_back(r);
-            }
-            HIPCHK(mp::op_lt_kvo(g, NB, s));
-            dump_lt(io, s);
-        }
-        for (int cb = 0; cb < 8; ++cb) {
-            mp::LtFfn2P l2{};
-            l2.f = mp::LtFfnP{io.ltY, m.lt_norm_ff, m.lt_ff1, m.lt_ff2s, m.eps, io.ltp, io.lty2};
-            l2.cb = cb; l2.ltX = io.ltX; l2.ltk = io.ltk; l2.ltv = io.ltv; l2.qkvtab = m.lt_qkvtab;
-            l2.votab = m.lt_votab; l2.ptab = m.lt_ptab; l2.lt_pos = m.lt_pos; l2.logits = io.logits;
-            l2.codes_cur = io.codes_cur; l2.step = io.step; l2.ignore_eos = io.ignore_eos;
-            l2.audio_bos = m.audio_bos; l2.audio_eos = m.audio_eos;
-            l2.smp = mp::Sampling{io.sampling, io.cfg, io.argeos, io.amax};
-            if (front && cb == 0) {
-                mp::LtFrontP fp{};
-                fp.l = l2; fp.x = io.x; fp.norm_out = m.dec_norm_out; fp.w_in = m.lt_in_w; fp.b_in = m.lt_in_b;
-                fp.lt_s = io.lt_s; fp.hidden_out = io.hidden; fp.lt_pos = m.lt_pos; fp.norm_self = m.lt_norm_self;
-                fp.w_kvo = m.lt_kvo; fp.gh = io.ltfg; fp.iter = io.iter; fp.hx_err = io.hx_err;
-                if (io.trace) { fp.trace = io.trace; fp.trace_steps = io.trace_steps; }
-                if (ops) {
-                    mp::OpRec r{};
-                    r.name = "lt_front"; r.kind = mp::K_LTFRONT; r.lf3 = fp; r.B = NB;
-                    r.bytes = A * (256.0 * 768 + 512.0 * 256 + 1024.0 * 256 * 2) + A * (768 * 2 + 256 * 4) +
-                              A * (mp::LT_FFN_P * 256);
-                    ops->push_back(r);
-                }
-                HIPCHK(mp::op_lt_front(fp, s));
-                dump_lt(io, s);
-            } else {
-                if (ops) {
-                    mp::OpRec r{};
-                    r.name = "lt_ffn2"; r.kind = mp::K_LTFFN2; r.l2 = l2; r.B = NB;
-                    r.bytes = A * (1024.0 * 256 * 2) + A * act * (cb ? 2024 + 4 * 256 + 2 * 256 * cb : 512) +
-                              A * act * (mp::LT_FFN_P * 256 + 256);
-                    ops->push_back(r);
-                }
-                HIPCHK(mp::op_lt_ffn2(l2, NB, s));
-                dump_lt(io, s);
-            }
-            if (NB > 1) {
-                if (ops) {
-                    mp::OpRec r{};
-                    r.name = "lt_merge"; r.kind = mp::K_LTMERGE; r.lf = l2.f; r.B = NB;
-                    r.bytes = A * act * (mp::LT_FFN_P * 256 + 512);
-                    ops->push_back(r);
-                }
-                HIPCHK(mp::op_lt_merge(l2.f, NB, s));
-            }
-            g = base(); g.cb = cb;
-            g.W = m.lt_out_w + (size_t)cb * 2024 * 256; g.N = 2024; g.bias = m.lt_out_b + (size_t)cb * 2024;
-            g.src = io.lty2; g.src_ld = 256; g.out = io.logits; g.out_ld = 2024;
-            mp::GemvFn efn = tb.lt_e;
-            if (NB == 1) {  // the FFN merge is the head's prologue
-                g.part = io.ltp; g.addsrc = io.ltY;
-                efn = mp::op_lt_em_1;
-            }
-            if ((rc = run("lt_e", efn, g, A * (2024.0 * 256) + A * 2024 + A * act * ((256 + 2024)))) != MP_OK)
-                return rc;
-        }
-    } else if (m.weight_mode == MP_WEIGHTS_Q8 && m.lt_o8 && m.lt_out8 && m.lt_ff2q && !io.lt_only && io.ltyg) {
-        // Q8_0 mode: position 0's q|k|v (the Q8_0 GEMV), then per codebook the LT step as
-        // LTQ_P workgroups per slot (lt_slot_q8_kernel: pick, attention, Q8_0 o_net, F32
-        // FFN, partial sums merged through granules) and the Q8_0 head on its output
-        mp::GemvP g = base(); g.cb = 0;
-        g.W = m.lt_qkv; g.N = 768; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX;
-        g.Wq = m.lt_qkv8.pq; g.Wd = m.lt_qkv8.pd; g.q4 = m.lt_qkv8.nib;
-        g.lnw = m.lt_norm_self; g.lq = io.ltq; g.lk = io.ltk; g.lv = io.ltv;
-        if ((rc = run("lt_a", tq.lt_a, g, Fq(m.lt_qkv8) * (768.0 * 256) + A * act * (256 * 3 + 768 + 256))) != MP_OK)
-            return rc;
-        for (int cb = 0; cb < 8; ++cb) {
-            mp::LtSlotQ8P sp{};
-            sp.g = base(); sp.g.cb = cb;
-            sp.g.logits = io.logits; sp.g.codes_cur = io.codes_cur; sp.g.qkvtab = m.lt_qkvtab; sp.g.ptab = m.lt_ptab;
-            sp.g.lt_pos = m.lt_pos; sp.g.ltk = io.ltk; sp.g.ltv = io.ltv; sp.g.lk = io.ltk; sp.g.lv = io.ltv;
-            sp.g.ltX = io.ltX;
-            sp.woq = m.lt_o8.q; sp.wod = m.lt_o8.d; sp.lnw = m.lt_norm_ff; sp.eps = m.eps; sp.w1 = m.lt_ff1;
-            sp.w2s = m.lt_ff2q; sp.y = io.ltY; sp.y2 = io.lty2; sp.gy = io.ltyg; sp.gp = io.ltgh;
-            sp.iter = io.iter; sp.hx_err = io.hx_err;
-            const int lm = ltq8_mode();
-            if (lm == 1 || (lm >= 2 && NB <= 4)) sp.wot = m.lt_o8t;  // (8+ slots: 512+ workgroups, the split rows)
-            if (lm >= 2 && NB == 1 && sp.wot) sp.part = io.ltp;
-            if (ops) {
-                mp::OpRec r{};
-                r.name = "lt_slot_q8"; r.kind = mp::K_LTSLOTQ8; r.lq8 = sp; r.B = NB;
-                r.bytes = (34.0 / 32.0) * (256.0 * 256) + A * (1024.0 * 256 * 2) +
-                          A * act * (cb ? 2024 + 4 * 256 + 2 * 256 * cb : 512) + A * act * (mp::LTQ_P * 256 + 512);
-                ops->push_back(r);
-            }
-            HIPCHK(mp::op_lt_slot_q8(sp, NB, s));
-            dump_lt(io, s);
-            g = base(); g.cb = cb;
-            g.W = m.lt_out_w + (size_t)cb * 2024 * 256; g.N = 2024; g.bias = m.lt_out_b + (size_t)cb * 2024;
-            g.src = io.lty2; g.src_ld = 256; g.out = io.logits; g.out_ld = 2024;
-            g.Wq = m.lt_out8.pq + (size_t)cb * m.lt_out8.head_q; g.q4 = m.lt_out8.nib;
-            g.Wd = (const unsigned short *)((const char *)m.lt_out8.pd + (size_t)cb * q8p_head_d());
-            mp::GemvFn efn = tq.lt_e;
-            if (sp.part) {  // the FFN merge is the head's prologue
-                g.part = io.ltp; g.addsrc = io.ltY;
-                efn = mp::q8_lt_em_1;
-            }
-            if ((rc = run("lt_e", efn, g, Fq(m.lt_out8) * (2024.0 * 256) + A * 2024 + A * act * ((256 + 2024)))) != MP_OK)
-                return rc;
-        }
-    } else
-    for (int cb = 0; cb < 8; ++cb) {
-        mp::GemvP g;
-        if (cb == 0) {
-            // position 0 (the hidden's in_proj): LN + q|k|v GEMV, then attention + o_net
-            g = base(); g.cb = 0;
-            g.W = m.lt_qkv; g.Wb = m.pk_lt_qkv; g.N = 768; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX;
-            g.Wq = m.lt_qkv8.pq; g.Wd = m.lt_qkv8.pd; g.q4 = m.lt_qkv8.nib;
-            g.lnw = m.lt_norm_self; g.lq = io.ltq; g.lk = io.ltk; g.lv = io.ltv;
-            if ((rc = run("lt_a", m.lt_qkv8 ? tq.lt_a : tb.lt_a, g,
-                          (m.lt_qkv8 ? Fq(m.lt_qkv8) : F) * (768.0 * 256) + A * act * (256 * 3 + 768 + 256))) != MP_OK)
-                return rc;
-            g = base(); g.cb = 0;
-            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.ltq = io.ltq; g.ltk = io.ltk; g.ltv = io.ltv; g.out = io.ltY;
-            g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
-            g.out_ld = 256; g.addsrc = io.ltX;
-            if ((rc = run("lt_b", m.lt_o8 ? tq.lt_b : tb.lt_b, g,
-                          (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) + A * act * (256 * 5))) != MP_OK)
-                return rc;
-        } else if (NB >= 8) {
-            // large batches: the per-slot pick + gathers + attention as one wave per slot
-            // (lt_pick_kernel), then o_net + residual; the same arithmetic as lt_bg
-            g = base(); g.cb = cb;
-            g.logits = io.logits; g.codes_cur = io.codes_cur; g.qkvtab = m.lt_qkvtab; g.ptab = m.lt_ptab;
-            g.lt_pos = m.lt_pos; g.ltk = io.ltk; g.ltv = io.ltv; g.lk = io.ltk; g.lv = io.ltv; g.ltX = io.ltX;
-            g.out = io.ltq;
-            if (ops) {
-                mp::OpRec r{};
-                r.name = "lt_pick"; r.kind = mp::K_LTPICK; r.g = g; r.B = NB;
-                r.bytes = A * act * (2024 + 4 * 256 + 2 * 256 * cb + 4 * 256);
-                ops->push_back(r);
-            }
-            HIPCHK(mp::op_lt_pick(g, NB, s));
-            dump_lt(io, s);
-            g = base(); g.cb = cb;
-            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.src = io.ltq; g.src_ld = 256; g.out = io.ltY; g.out_ld = 256;
-            g.addsrc = io.ltX; g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
-            const bool f16 = m.weight_mode == MP_WEIGHTS_F16;
-            const mp::GemvFn bo = m.lt_o8 ? (NB == 16 ? mp::q8_lt_bo_16 : mp::q8_lt_bo_8)
-                                  : f16   ? (NB == 16 ? mp::f16_lt_bo_16 : mp::f16_lt_bo_8)
-                                  : b16   ? (NB == 16 ? mp::b16_lt_bo_16 : mp::b16_lt_bo_8)
-                                          : mp::op_lt_bo_8;
-            if ((rc = run("lt_bo", bo, g, (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) + A * act * (256 * 3))) != MP_OK) return rc;
-        } else {
-            // position cb: codebook cb-1's pick, its q|k|v row gathered from the load-time
-            // table (no q|k|v GEMV), attention + o_net + residual, one launch
-            g = base(); g.cb = cb;
-            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.out = io.ltY; g.out_ld = 256;
-            g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
-            g.logits = io.logits; g.codes_cur = io.codes_cur; g.qkvtab = m.lt_qkvtab; g.ptab = m.lt_ptab;
-            g.lt_pos = m.lt_pos; g.ltk = io.ltk; g.ltv = io.ltv; g.lk = io.ltk; g.lv = io.ltv;
-            if ((rc = run("lt_bg", m.lt_o8 ? tq.lt_bg : tb.lt_bg, g,
-                          (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) +
-                              A * act * (2024 + 3 * 256 + 2 * 256 * cb + 2 * 256 + 256))) != MP_OK)
-                return rc;
-        }
-        // FFN up + GELU + FFN down: one launch of partial sums (f32 FFN weights), merged by
-        // the head's prologue at batch 1 or by a one-workgroup merge; bf16 mode: two GEMVs
-        const bool ffn1 = !b16;
-        if (ffn1) {
-            mp::LtFfnP lf{io.ltY, m.lt_norm_ff, m.lt_ff1, m.lt_ff2s, m.eps, io.ltp, io.lty2};
-            if (ops) {
-                mp::OpRec r{};
-                r.name = "lt_ffn"; r.kind = mp::K_LTFFN; r.lf = lf; r.B = NB;
-                r.bytes = A * (1024.0 * 256 * 2) + A * act * (256 + mp::LT_FFN_P * 256);
-                ops->push_back(r);
-            }
-            HIPCHK(mp::op_lt_ffn(lf, NB, s));
-            if (NB > 1) {
-                if (ops) {
-                    mp::OpRec r{};
-                    r.name = "lt_merge"; r.kind = mp::K_LTMERGE; r.lf = lf; r.B = NB;
-                    r.bytes = A * act * (mp::LT_FFN_P * 256 + 512);
-                    ops->push_back(r);
-                }
-                HIPCHK(mp::op_lt_merge(lf, NB, s));
-            }
-        } else {
-            g = base(); g.cb = cb;
-            g.W = m.lt_ff1; g.Wb = m.pk_lt_ff1; g.N = 1024; g.lnw = m.lt_norm_ff; g.src = io.ltY; g.src_ld = 256;
-            g.out = io.ltf; g.out_ld = 1024;
-            if ((rc = run("lt_c", tb.lt_c, g, F * (1024.0 * 256) + A * act * ((256 + 1024)))) != MP_OK) return rc;
-            g = base(); g.cb = cb;
-            g.W = m.lt_ff2; g.Wb = m.pk_lt_ff2; g.N = 256; g.src = io.ltf; g.src_ld = 1024; g.out = io.lty2;
-            g.out_ld = 256; g.addsrc = io.ltY;
-            if ((rc = run("lt_d", tb.lt_d, g, F * (256.0 * 1024) + A * act * ((1024 + 512)))) != MP_OK) return rc;
-        }
-        g = base(); g.cb = cb;
-        g.W = m.lt_out_w + (size_t)cb * 2024 * 256; g.N = 2024;
-        g.Wb = b16 ? m.pk_lt_out + (size_t)cb * pk_elems(2024, 256) : nullptr; g.bias = m.lt_out_b + (size_t)cb * 2024;
-        g.src = io.lty2; g.src_ld = 256; g.out = io.logits; g.out_ld = 2024;
-        if (m.lt_out8) {
-            g.Wq = m.lt_out8.pq + (size_t)cb * m.lt_out8.head_q; g.q4 = m.lt_out8.nib;
-            g.Wd = (const unsigned short *)((const char *)m.lt_out8.pd + (size_t)cb * q8p_head_d());
-        }
-        mp::GemvFn efn = m.lt_out8 ? tq.lt_e : tb.lt_e;
-        if (ffn1 && NB == 1) {  // the FFN merge (lt_ffn_kernel's interleaved partials) is the head's prologue
-            g.part = io.ltp; g.addsrc = io.ltY;
-            efn = m.lt_out8 ? mp::q8_lt_emf_1 : mp::op_lt_em_1;
-        }
-        if ((rc = run("lt_e", efn, g,
-                      (m.lt_out8 ? Fq(m.lt_out8) : F) * (2024.0 * 256) + A * 2024 + A * act * ((256 + 2024)))) != MP_OK)
-            return rc;
-    }
-    mp::FinP f{io.logits, io.codes_cur, io.codes_prev, io.codes_out, io.step, io.pos, io.done, io.nframes, io.ndone,
-               io.max_steps, io.ignore_eos, m.audio_bos, m.audio_eos, NB,
-               mp::Sampling{io.sampling, io.cfg, io.argeos, io.amax}, io.emit_eos, io.lt_only,
-               io.lt_only ? nullptr : io.ndone + 1};
-    if (!io.lt_only) { f.emb = m.audio_emb; f.pos_emb = m.dec_pos; f.x = io.x; f.pos_rows = m.dec_pos_rows; }  // the next frame's input
-    if (ops) {
-        mp::OpRec r{};
-        r.name = "finalize"; r.kind = mp::K_FIN; r.f = f; r.B = NB; r.bytes = A * act * 2024;
-        ops->push_back(r);
-    }
-    HIPCHK(mp::op_finalize(f, NB, s));
     return MP_OK;
 }
 
@@ -2039,17 +1952,24 @@ int reset_decode_state(mp_dev *dev) {
 }
 
 
-// Capture the iteration graph (or, eager, record the op list) once per batch
-// configuration; leaves the decode state reset.
+// Build the iteration's launch list and capture it into the graph (or, eager, launch it
+// once) once per batch configuration; leaves the decode state reset.
 int prepare_iteration(mp_dev *dev) {
+    const bool fresh = dev->ops.empty();
+    if (fresh) {
+        if (int rc = build_iteration(dev, dev->ops)) { dev->ops.clear(); return rc; }
+    }
     if (eager_mode()) {
-        if (dev->ops.empty()) {
-            if (int rc = enqueue_iteration(dev, dev->stream, true)) return rc;  // a real first iteration
+        if (fresh) {
+            // a real first iteration, on a reset state: at a fresh batch's zeroed position
+            // it would append its K/V over row 0 of the prefilled cache
+            if (int rc = reset_decode_state(dev)) return rc;
+            if (int rc = launch_ops(dev, dev->ops, dev->stream)) return rc;
             HIPCHK(hipStreamSynchronize(dev->stream));
         }
     } else if (!dev->exec) {
         HIPCHK(hipStreamBeginCapture(dev->stream, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_iteration(dev, dev->stream, true);
+        int rc = launch_ops(dev, dev->ops, dev->stream);
         hipGraph_t g = nullptr;
         hipError_t e = hipStreamEndCapture(dev->stream, &g);
         if (rc != MP_OK) { if (g) hipGraphDestroy(g); return rc; }
@@ -2062,7 +1982,7 @@ int prepare_iteration(mp_dev *dev) {
 
 int launch_iteration(mp_dev *dev, hipStream_t s = nullptr) {
     if (!s) s = dev->stream;
-    if (eager_mode()) return enqueue_iteration(dev, s, false);
+    if (eager_mode()) return launch_ops(dev, dev->ops, s);
     HIPCHK(hipGraphLaunch(dev->exec, s));
     return MP_OK;
 }
@@ -2344,7 +2264,9 @@ int mp_hip_lt_sample(mp_dev *dev, const float *hidden, float temperature, int to
     HIPCHK(hipMemcpyAsync(io.step, &step, 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(io.cfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemsetAsync(io.argeos, 0, 4, dev->stream));
-    if (int rc = enqueue_lt(dev, io, 1, dev->stream, nullptr)) return rc;
+    std::vector<mp::OpRec> ops;  // sampling / ignore_eos vary per call: a list per call
+    if (int rc = build_lt(dev, io, 1, ops)) return rc;
+    if (int rc = launch_ops(dev, ops, dev->stream)) return rc;
     HIPCHK(hipMemcpyAsync(sampled, io.codes_cur, 32, hipMemcpyDeviceToHost, dev->stream));
     HIPCHK(hipMemcpyAsync(argmax, io.amax, 32, hipMemcpyDeviceToHost, dev->stream));
     HIPCHK(hipStreamSynchronize(dev->stream));
@@ -2412,27 +2334,6 @@ double mp_hip_op_bytes(mp_dev *dev, int op) {
                dev->NB * ((double)(pos + 1) * 768 * 2 * kvb + 4.0 * mp::NH * mp::SA_SPLITS * mp::SA_PART);
     }
     return r.bytes;
-}
-
-// one recorded op, launched on s (profiling and standalone timing)
-static hipError_t launch_rec(const mp::OpRec &r, hipStream_t s) {
-    switch (r.kind) {
-    case mp::K_GEMV: return r.fn(r.g, s);
-    case mp::K_ATTN: return mp::op_sa_attn(r.a, r.B, s);
-    case mp::K_XA: return mp::op_xa(r.x, r.B, s);
-    case mp::K_XAQ8: return mp::op_xa_q8(r.xq, r.B, s);
-    case mp::K_LTFFN: return mp::op_lt_ffn(r.lf, r.B, s);
-    case mp::K_LTMERGE: return mp::op_lt_merge(r.lf, r.B, s);
-    case mp::K_LTPICK: return mp::op_lt_pick(r.g, r.B, s);
-    case mp::K_LTFFN2: return mp::op_lt_ffn2(r.l2, r.B, s);
-    case mp::K_LTSLOT: return mp::op_lt_slot(r.l2, r.B, s);
-    case mp::K_LTFRONT: return mp::op_lt_front(r.lf3, s);
-    case mp::K_LTSLOTQ8: return mp::op_lt_slot_q8(r.lq8, r.B, s);
-    case mp::K_LTKVO: return mp::op_lt_kvo(r.g, r.B, s);
-    case mp::K_EMBED: return mp::op_embed(r.e, r.B, s);
-    case mp::K_FIN: return mp::op_finalize(r.f, r.B, s);
-    }
-    return hipErrorInvalidValue;
 }
 
 int mp_hip_profile_ops(mp_dev *dev, int iters, float *avg_us) { return mp_hip_profile_ops_ex(dev, iters, avg_us, nullptr); }
