@@ -31,19 +31,33 @@ namespace mp {
 #ifndef MP_GEMV_WSN
 #define MP_GEMV_WSN 1  // the GEMV family's wave sums advanced together (0: one after another)
 #endif
+// Leading scalar arguments (every decode kernel, the 16-bit and Q8_0 families' too): gfx950's command
+// processor places the first kernel-argument dwords in SGPRs at wave start (kernarg
+// preload, the Makefile's -amdgpu-kernarg-preload-count; at most 14 dwords beside the
+// kernarg pointer, and scalar arguments only: a by-value struct is never preloaded).
+// The scalars a kernel's entry path reads before its first stream is issued therefore
+// lead the argument list and overwrite their fields of the kernel's copy of the struct,
+// so the first loads wait for no scalar load; everything read later stays in the struct
+// (the launchers pass the struct's own fields: the values are the same).
+// gemv_kernel: W, the pointers pre_load reads (src, lnw, part, addsrc), ts, src_ld and
+// nn = N | nrow_blocks << 16.
 template <int NB, int RW, int K, int PRO, int EPI>
-__global__ __launch_bounds__(MP_BLOCK) void gemv_kernel(GemvP p) {
+__global__ __launch_bounds__(MP_BLOCK) void gemv_kernel(const float *W, const float *src, const float *lnw,
+                                                        const float *part, const float *addsrc,
+                                                        unsigned long long *ts, int src_ld, unsigned nn, GemvP p) {
+    p.W = W; p.src = src; p.lnw = lnw; p.part = part; p.addsrc = addsrc; p.ts = ts; p.src_ld = src_ld;
+    p.N = (int)(nn & 0xffffu); p.nrow_blocks = (int)(nn >> 16);
     const unsigned long long t_start = ts_begin(p.ts);
     if constexpr (EPI == EPI_RESID_XA) {
         // the launch's last XA_SPLITS x NB workgroups: cross-attention on this launch's x1
-        if ((int)blockIdx.x >= p.nrow_blocks) {
+        if (__builtin_expect((int)blockIdx.x >= p.nrow_blocks, 0)) {  // laid out behind the rows' path
             xa_tail(p, t_start);
             return;
         }
     }
     if constexpr (EPI == EPI_QKV_SA) {
         // the launch's last NH x SA_SPLITS x NB workgroups: self-attention on this launch's q|k|v
-        if ((int)blockIdx.x >= p.nrow_blocks) {
+        if (__builtin_expect((int)blockIdx.x >= p.nrow_blocks, 0)) {
             sa_tail(p, t_start);
             return;
         }
@@ -199,9 +213,29 @@ hipError_t op_xa(const XaP &p, int B, hipStream_t s) {
 // keeps embed_kernel's order (codebooks 0..7 in sequence, / 8, + position): the
 // same bits.
 constexpr int FIN_THREADS = 256;
-__global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(FinP p) {
+// Leading arguments (gemv_kernel's note): the pick's logits and step, which head the
+// kernel's dependent chain and are loaded first, the sampling switch, and the iteration
+// counter, the done flags and ts, which the entry reads next.
+__global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *logits, int *step, int *iter, int *done_flags,
+                                                                  unsigned long long *ts, int smp_on, FinP p) {
+    p.logits = logits; p.step = step; p.iter = iter; p.done = done_flags; p.ts = ts; p.smp.on = smp_on;
     const unsigned long long t_start = ts_begin(p.ts);
     const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+    // greedy: codebook 7's pick split over the 4 waves (lt_step_body's split pick: each
+    // wave scans PICK_R / 4 logit rows, the pairs meet in LDS; the same code); its loads first
+    static_assert(FIN_THREADS / 64 == MP_NWAVES, "the split pick's rows per wave");
+    const bool quad = !p.smp.on;
+    float lq[QPR];
+    int stp_q = 0;
+    if (quad) {
+        const float *lg = p.logits + (size_t)b * VCB + ts_dep(t_start);
+#pragma unroll
+        for (int q = 0; q < QPR; ++q) {
+            const int i = (tid & 63) + 64 * (w * QPR + q);
+            lq[q] = i < VCB ? lg[i] : -INFINITY;
+        }
+        stp_q = p.step[b];
+    }
     if (p.iter && b == 0 && tid == 0) p.iter[0] += 1;  // the next iteration's hand-off tags
     // a finished slot keeps running with the batch: it gets its frozen input again
     // (codes_prev / pos no longer advance), so every later iteration recomputes the
@@ -230,21 +264,6 @@ __global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(FinP p) {
     if (embed && w >= 1) {
         if (done) gather(p.codes_prev + b * NCB, p.pos[b], NCB, s, pe);
         else gather(p.codes_cur + b * NCB, p.pos[b] + 1, NCB - 1, s, pe);
-    }
-    // greedy: codebook 7's pick split over the 4 waves (lt_step_body's split pick: each
-    // wave scans PICK_R / 4 logit rows, the pairs meet in LDS; the same code)
-    static_assert(FIN_THREADS / 64 == MP_NWAVES, "the split pick's rows per wave");
-    const bool quad = !p.smp.on;
-    float lq[QPR];
-    int stp_q = 0;
-    if (quad) {
-        const float *lg = p.logits + (size_t)b * VCB + ts_dep(t_start);
-#pragma unroll
-        for (int q = 0; q < QPR; ++q) {
-            const int i = (tid & 63) + 64 * (w * QPR + q);
-            lq[q] = i < VCB ? lg[i] : -INFINITY;
-        }
-        stp_q = p.step[b];
     }
     __shared__ int sh_adv, sh_code, sh_stop;
     __syncthreads();  // every read of pos / codes / step above precedes wave 0's updates
@@ -366,8 +385,10 @@ static hipError_t launch_gemv(const GemvP &p, hipStream_t s) {
     const int rows_per_block = MP_NWAVES * RW;
     GemvP q = p;
     q.nrow_blocks = (p.N + rows_per_block - 1) / rows_per_block;
+    if (p.N > 0xffff || q.nrow_blocks > 0xffff) return hipErrorInvalidValue;  // nn's two 16-bit halves
     const int grid = q.nrow_blocks + (EPI == EPI_RESID_XA ? XA_SPLITS * NB : EPI == EPI_QKV_SA ? NH * SA_SPLITS * NB : 0);
-    mp::launch((gemv_kernel<NB, RW, K, PRO, EPI>), dim3(grid), dim3(MP_BLOCK), 0, s, q);
+    mp::launch((gemv_kernel<NB, RW, K, PRO, EPI>), dim3(grid), dim3(MP_BLOCK), 0, s, q.W, q.src, q.lnw, q.part, q.addsrc,
+               q.ts, q.src_ld, (unsigned)q.N | (unsigned)q.nrow_blocks << 16, q);
     return hipGetLastError();
 }
 
@@ -395,7 +416,6 @@ constexpr int RW_QKV = MP_RW_QKV, RW_FF1 = MP_RW_FF1;
     hipError_t op_ff2_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, DFF, PRO_PLAIN, EPI_ADD_STORE>(p, s); }  \
     hipError_t op_lt_in0_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, D, PRO_LN, EPI_BIAS>(p, s); }         \
     hipError_t op_lt_a_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTD, PRO_LTX_LN, EPI_LTQKV>(p, s); }    \
-    hipError_t op_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); } \
     hipError_t op_lt_b_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTD, PRO_LT_ATTN, EPI_ADD_STORE>(p, s); } \
     hipError_t op_lt_c_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTD, PRO_LN, EPI_GELU>(p, s); }         \
     hipError_t op_lt_d_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTF, PRO_PLAIN, EPI_ADD_STORE>(p, s); } \
@@ -406,6 +426,13 @@ MP_DECODE_OPS(1)
 MP_DECODE_OPS(2)
 MP_DECODE_OPS(4)
 MP_DECODE_OPS(8)
+// the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots the runtime
+// launches lt_pick_kernel + lt_bo instead (the fused prologue would run a wave's slots'
+// picks in sequence), so the op table's entry for 8 is never launched and holds no kernel
+hipError_t op_lt_bg_1(const GemvP &p, hipStream_t s) { return launch_gemv<1, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); }
+hipError_t op_lt_bg_2(const GemvP &p, hipStream_t s) { return launch_gemv<2, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); }
+hipError_t op_lt_bg_4(const GemvP &p, hipStream_t s) { return launch_gemv<4, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); }
+hipError_t op_lt_bg_8(const GemvP &, hipStream_t) { return hipErrorInvalidValue; }
 // LT in_proj of a caller-supplied (already normalised) hidden vector, batch 1
 // (magpie_local_transformer_sample_all, magpie.cpp:1161-1163)
 hipError_t op_lt_inh_1(const GemvP &p, hipStream_t s) { return launch_gemv<1, 1, D, PRO_PLAIN, EPI_BIAS>(p, s); }
@@ -813,8 +840,16 @@ __device__ __forceinline__ void lt_step_body(const LtFfn2P &p, int pb, int dep, 
         accs[b] = acc;
     }
 }
+// Leading arguments (gemv_kernel's note): what the step's first loads read, which head its
+// dependent chain (logits, step -> pick -> gathers -> y) -- the logits, the earlier
+// positions' rows, the step, the LN weights, cb and the sampling switch -- and ts. The FFN
+// weights' pointers stay in the struct: 14 dwords hold no more, and the weights are not
+// needed before y.
 template <int NB>
-__global__ __launch_bounds__(MP_BLOCK) void lt_ffn2_kernel(LtFfn2P p) {
+__global__ __launch_bounds__(MP_BLOCK) void lt_ffn2_kernel(const float *logits, float *ltk, float *ltv, const int *step,
+                                                           const float *lnw, unsigned long long *ts, int cb, int smp_on,
+                                                           LtFfn2P p) {
+    p.logits = logits; p.ltk = ltk; p.ltv = ltv; p.step = step; p.f.lnw = lnw; p.f.ts = ts; p.cb = cb; p.smp.on = smp_on;
     const unsigned long long t_start = ts_begin(p.f.ts);
     float accs[NB];
     lt_step_body<NB>(p, blockIdx.x, ts_dep(t_start), accs, nullptr);
@@ -828,13 +863,15 @@ hipError_t op_lt_ffn2(const LtFfn2P &p, int NB, hipStream_t s) {
         !p.votab || !p.ptab || !p.lt_pos || !p.logits || !p.codes_cur || !p.step || !p.smp.cfg || !p.smp.argeos ||
         p.cb < 0 || p.cb >= NCB)
         return hipErrorInvalidValue;
+#define LT_FFN2_ARGS p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts, p.cb, p.smp.on, p
     switch (NB) {
-    case 1: mp::launch(lt_ffn2_kernel<1>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, p); break;
-    case 2: mp::launch(lt_ffn2_kernel<2>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, p); break;
-    case 4: mp::launch(lt_ffn2_kernel<4>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, p); break;
-    case 8: mp::launch(lt_ffn2_kernel<8>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, p); break;
+    case 1: mp::launch(lt_ffn2_kernel<1>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
+    case 2: mp::launch(lt_ffn2_kernel<2>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
+    case 4: mp::launch(lt_ffn2_kernel<4>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
+    case 8: mp::launch(lt_ffn2_kernel<8>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
     default: return hipErrorInvalidValue;
     }
+#undef LT_FFN2_ARGS
     return hipGetLastError();
 }
 
@@ -855,7 +892,11 @@ constexpr int LTS_U = LTF / LTS_P, LTS_UPW = LTS_U / MP_NWAVES;
 __device__ __forceinline__ float bf16_round(float v) { return __uint_as_float((unsigned)f32_to_bf16_rne(v) << 16); }
 __device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-__global__ __launch_bounds__(MP_BLOCK) void lt_slot_kernel(LtFfn2P p) {
+// (leading arguments: lt_ffn2_kernel's)
+__global__ __launch_bounds__(MP_BLOCK) void lt_slot_kernel(const float *logits, float *ltk, float *ltv, const int *step,
+                                                           const float *lnw, unsigned long long *ts, int cb, int smp_on,
+                                                           LtFfn2P p) {
+    p.logits = logits; p.ltk = ltk; p.ltv = ltv; p.step = step; p.f.lnw = lnw; p.f.ts = ts; p.cb = cb; p.smp.on = smp_on;
     const unsigned long long t_start = ts_begin(p.f.ts);
     static_assert(LTD == MP_BLOCK && LTS_U % 8 == 0 && LTS_U % MP_NWAVES == 0, "unit split");
     __shared__ __attribute__((aligned(16))) float xs[LTD];
@@ -969,7 +1010,8 @@ hipError_t op_lt_slot(const LtFfn2P &p, int NB, hipStream_t s) {
         !p.qkvtab || !p.votab || !p.ptab || !p.lt_pos || !p.logits || !p.codes_cur || !p.step || !p.smp.cfg ||
         !p.smp.argeos || p.cb < 0 || p.cb >= NCB || NB < 1 || NB > 16)
         return hipErrorInvalidValue;
-    mp::launch(lt_slot_kernel, dim3(LTS_P, NB), dim3(MP_BLOCK), 0, s, p);
+    mp::launch(lt_slot_kernel, dim3(LTS_P, NB), dim3(MP_BLOCK), 0, s, p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts, p.cb,
+               p.smp.on, p);
     return hipGetLastError();
 }
 
@@ -1140,7 +1182,14 @@ __device__ __forceinline__ void lt_front_weights(const LtFrontP &p, int pb, int 
 #pragma unroll
     for (int i = 0; i < LTF_U / 4; ++i) a2[i] = ld_ltffn((const float4 *)(p.l.f.w2 + (size_t)j0 * LTD + tid * LTF_U + 4 * i));
 }
-__global__ __launch_bounds__(MP_BLOCK) void lt_front_kernel(LtFrontP p) {
+// Leading arguments (gemv_kernel's note): the decoder row, the LN weights and the small
+// operands loaded ahead of the weights (lt_front_pre), and ts; the weights' pointers stay in
+// the struct (14 dwords hold no more)
+__global__ __launch_bounds__(MP_BLOCK) void lt_front_kernel(const float *x, const float *norm_out, const float *b_in,
+                                                            const float *lt_pos, const float *norm_self,
+                                                            const float *lnw, unsigned long long *ts, LtFrontP p) {
+    p.x = x; p.norm_out = norm_out; p.b_in = b_in; p.lt_pos = lt_pos; p.norm_self = norm_self; p.l.f.lnw = lnw;
+    p.l.f.ts = ts;
     const unsigned long long t_start = ts_begin(p.l.f.ts);
     static_assert(LTF_U % MP_NWAVES == 0 && LTD == MP_BLOCK && LT_FFN_P <= LTFR_G, "unit split");
     __shared__ __attribute__((aligned(16))) float act[D];
@@ -1173,7 +1222,8 @@ hipError_t op_lt_front(const LtFrontP &p, hipStream_t s) {
         !p.iter || !p.hx_err || !p.l.f.y || !p.l.f.lnw || !p.l.f.w1 || !p.l.f.w2 || !p.l.f.part || !p.l.ltX ||
         !p.l.ltk || !p.l.ltv || !p.l.step || p.l.cb != 0)
         return hipErrorInvalidValue;
-    mp::launch(lt_front_kernel, dim3(LTFR_G), dim3(MP_BLOCK), 0, s, p);
+    mp::launch(lt_front_kernel, dim3(LTFR_G), dim3(MP_BLOCK), 0, s, p.x, p.norm_out, p.b_in, p.lt_pos, p.norm_self,
+               p.l.f.lnw, p.l.f.ts, p);
     return hipGetLastError();
 }
 
@@ -1194,7 +1244,7 @@ hipError_t op_lt_kvo(const GemvP &p, int NB, hipStream_t s) {
 hipError_t op_finalize(const FinP &p, int B, hipStream_t s) {
     if (!p.smp.cfg || !p.smp.argeos) return hipErrorInvalidValue;
     if (p.x && (!p.emb || !p.pos_emb || p.pos_rows < 1)) return hipErrorInvalidValue;
-    mp::launch(lt_finalize_kernel, dim3(B), dim3(FIN_THREADS), 0, s, p);
+    mp::launch(lt_finalize_kernel, dim3(B), dim3(FIN_THREADS), 0, s, p.logits, p.step, p.iter, p.done, p.ts, p.smp.on, p);
     return hipGetLastError();
 }
 

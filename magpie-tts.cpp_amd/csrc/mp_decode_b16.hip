@@ -71,7 +71,14 @@ __device__ __forceinline__ floatx4 mfma16(uint4 a, uint4 b, floatx4 c) {
 // added in slice order, then runs the epilogue. KS is a function of the op (K) only,
 // never of NB, so every batch size computes the same bits.
 template <int NB, int K, int PRO, int EPI, bool F16 = false, int KS = 1>
-__global__ __launch_bounds__(MP_BLOCK) void gemm_b16_kernel(GemvP p) {
+__global__ __launch_bounds__(MP_BLOCK) void gemm_b16_kernel(const unsigned short *Wb, const void *rows, const float *lnw,
+                                                            const float *parts, const float *addsrc,
+                                                            unsigned long long *ts, int src_ld, int nrow_blocks, GemvP p) {
+    // leading arguments (mp_decode.hip, gemv_kernel's note): the weights, the pointers the rows'
+    // loads read ahead of them (rows: src_b16 for PRO_PLAIN_B16, else src), ts, src_ld, nrow_blocks
+    p.Wb = Wb; p.lnw = lnw; p.part = parts; p.addsrc = addsrc; p.ts = ts; p.src_ld = src_ld; p.nrow_blocks = nrow_blocks;
+    if constexpr (PRO == PRO_PLAIN_B16) p.src_b16 = (const unsigned short *)rows;
+    else p.src = (const float *)rows;
     const unsigned long long t_start = ts_begin(p.ts);
     static_assert(NB >= 1 && NB <= 16, "one 16-column MFMA tile of utterances");
     static_assert(K % (128 * KS) == 0, "K splits into KS slices of 4 waves x 32-wide chunks");
@@ -91,14 +98,14 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_b16_kernel(GemvP p) {
     __shared__ float sc[SC];
     if constexpr (EPI == EPI_RESID_XA) {
         // the launch's last XA_SPLITS x NB workgroups: cross-attention on this launch's x1 (mp_xa.hpp)
-        if ((int)blockIdx.x >= p.nrow_blocks) {
+        if (__builtin_expect((int)blockIdx.x >= p.nrow_blocks, 0)) {  // laid out behind the rows' path
             xa_tail(p, t_start);
             return;
         }
     }
     if constexpr (EPI == EPI_QKV_SA) {
         // the launch's last NH x SA_SPLITS x NB workgroups: self-attention on this launch's q|k|v
-        if ((int)blockIdx.x >= p.nrow_blocks) {
+        if (__builtin_expect((int)blockIdx.x >= p.nrow_blocks, 0)) {
             sa_tail(p, t_start);
             return;
         }
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_b16_kernel(GemvP p) {
         const int rq = KS == 1 ? tid >> 4 : ks * (16 / KS) + (tid >> 4), cq = tid & 15, nq = rt * 16 + rq;
         if (cq < NB && nq < p.N && (KS == 1 || tid < (16 / KS) * 16)) eop = epi_operand<EPI>(p, nq, cq);
     }
-    if constexpr (PRE || PLB || PLF || epi_has_operand<EPI>()) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);  // the weight stream is issued before anything the prologue reads
 
     // activation rows -> bf16 in LDS; row NB is zero and feeds MFMA columns NB..15
     if constexpr (LNB) {
@@ -408,7 +415,9 @@ static hipError_t launch_b16(const GemvP &p, hipStream_t s) {
     GemvP q = p;
     q.nrow_blocks = (p.N + 15) / 16 * KS;  // row workgroups (KS per 16-row tile)
     const int grid = q.nrow_blocks + (EPI == EPI_RESID_XA ? XA_SPLITS * NB : EPI == EPI_QKV_SA ? NH * SA_SPLITS * NB : 0);
-    mp::launch((gemm_b16_kernel<NB, K, PRO, EPI, F16, KS>), dim3(grid), dim3(MP_BLOCK), 0, s, q);
+    mp::launch((gemm_b16_kernel<NB, K, PRO, EPI, F16, KS>), dim3(grid), dim3(MP_BLOCK), 0, s, q.Wb,
+               PRO == PRO_PLAIN_B16 ? (const void *)q.src_b16 : (const void *)q.src, q.lnw, q.part, q.addsrc, q.ts, q.src_ld,
+               q.nrow_blocks, q);
     return hipGetLastError();
 }
 // split-K of the FFN-down projection (K = 3072, 48 row tiles): a function of the op only.
@@ -427,6 +436,14 @@ constexpr int FF2_KS = MP_FF2_KS;
 constexpr int OPROJ_KS = MP_OPROJ_KS;
 int b16_oproj_ks() { return OPROJ_KS; }
 
+// the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots the runtime
+// launches lt_pick_kernel + lt_bo instead, so the op tables' entries for 8 and 16 are never
+// launched and hold no kernel
+template <int NB, bool F16>
+static hipError_t launch_lt_bg(const GemvP &p, hipStream_t s) {
+    if constexpr (NB >= 8) return hipErrorInvalidValue;
+    else return launch_b16<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD, F16>(p, s);
+}
 #define MP_B16_OPS(NB)                                                                                                  \
     hipError_t b16_qkv_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_LN, EPI_QKV>(p, s); }             \
     hipError_t b16_qkv_sa_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_LN, EPI_QKV_SA>(p, s); }       \
@@ -438,7 +455,7 @@ int b16_oproj_ks() { return OPROJ_KS; }
     hipError_t b16_ff1p_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_LN, EPI_GELU_B16>(p, s); }       \
     hipError_t b16_ff2_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, DFF, PRO_PLAIN_B16, EPI_ADD_STORE, false, FF2_KS>(p, s); }  \
     hipError_t b16_lt_a_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LTX_LN, EPI_LTQKV>(p, s); }    \
-    hipError_t b16_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); } \
+    hipError_t b16_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_lt_bg<NB, false>(p, s); } \
     hipError_t b16_lt_b_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE>(p, s); } \
     hipError_t b16_lt_c_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LN, EPI_GELU>(p, s); }         \
     hipError_t b16_lt_d_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTF, PRO_PLAIN, EPI_ADD_STORE>(p, s); } \
@@ -456,7 +473,7 @@ int b16_oproj_ks() { return OPROJ_KS; }
     hipError_t f16_ff1_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_XA_LN, EPI_GELU_F16, true>(p, s); }     \
     hipError_t f16_ff2_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, DFF, PRO_PLAIN_B16, EPI_ADD_STORE, true, FF2_KS>(p, s); }  \
     hipError_t f16_lt_a_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LTX_LN, EPI_LTQKV, true>(p, s); }    \
-    hipError_t f16_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD, true>(p, s); } \
+    hipError_t f16_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_lt_bg<NB, true>(p, s); } \
     hipError_t f16_lt_b_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE, true>(p, s); } \
     hipError_t f16_lt_c_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LN, EPI_GELU, true>(p, s); }         \
     hipError_t f16_lt_d_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTF, PRO_PLAIN, EPI_ADD_STORE, true>(p, s); } \

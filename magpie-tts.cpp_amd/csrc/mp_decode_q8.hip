@@ -57,7 +57,16 @@ __device__ __forceinline__ void xq8qa_tail(const GemvP &p, float *act, signed ch
 constexpr int XQG = 8;  // q_net workgroups per slot in EPI_RESID_XQ8 (16 rows each)
 
 template <int NB, int K, int PRO, int EPI, bool Q4>
-__global__ __launch_bounds__(MP_BLOCK) void gemm_q8_kernel_dec(GemvP p) {
+__global__ __launch_bounds__(MP_BLOCK) void gemm_q8_kernel_dec(const signed char *Wq, const unsigned short *Wd,
+                                                               const float *src, const float *parts, const float *aux,
+                                                               unsigned long long *ts, int src_ld, int nrow_blocks,
+                                                               GemvP p) {
+    // leading arguments (mp_decode.hip, gemv_kernel's note): the weights and their scales, the
+    // pointers pre_load reads ahead of them (aux: addsrc for the LT head's merge prologues, which
+    // read no LN weights, else lnw), ts, src_ld, nrow_blocks
+    p.Wq = Wq; p.Wd = Wd; p.src = src; p.part = parts; p.ts = ts; p.src_ld = src_ld; p.nrow_blocks = nrow_blocks;
+    if constexpr (PRO == PRO_LTQ_MERGE || PRO == PRO_LTFFN_MERGE) p.addsrc = aux;
+    else p.lnw = aux;
     const unsigned long long t_start = ts_begin(p.ts);
     static_assert(NB >= 1 && NB <= 16, "one 16-column MFMA tile of utterances");
     static_assert(K % 256 == 0, "K splits into 4 waves x 64-wide block pairs");
@@ -74,7 +83,7 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_q8_kernel_dec(GemvP p) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rt = blockIdx.x;
     if constexpr (EPI == EPI_QKV_SA) {
         // the launch's last NH x SA_SPLITS x NB workgroups: self-attention on this launch's q|k|v
-        if (rt >= p.nrow_blocks) {
+        if (__builtin_expect(rt >= p.nrow_blocks, 0)) {  // laid out behind the rows' path
             sa_tail(p, t_start);
             return;
         }
@@ -82,16 +91,10 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_q8_kernel_dec(GemvP p) {
     if constexpr (EPI == EPI_RESID_XQ8) {
         // then XQG x NB workgroups: the XA's q_net on this launch's x1; then XQ8A x NB:
         // the XA's attention + o_net on that q
-        if (NB <= XQ8_QIN_NB && rt >= p.nrow_blocks && p.xq8.qin) {
-            xq8qa_tail(p, act, actq, actd, t_start);
-            return;
-        }
-        if (rt >= p.nrow_blocks + XQG * NB) {
-            xq8a_tail(p, t_start);
-            return;
-        }
-        if (rt >= p.nrow_blocks) {
-            xq8_tail(p, act, actq, actd, t_start);
+        if (__builtin_expect(rt >= p.nrow_blocks, 0)) {  // laid out behind the rows' path
+            if (NB <= XQ8_QIN_NB && p.xq8.qin) xq8qa_tail(p, act, actq, actd, t_start);
+            else if (rt >= p.nrow_blocks + XQG * NB) xq8a_tail(p, t_start);
+            else xq8_tail(p, act, actq, actd, t_start);
             return;
         }
     }
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_q8_kernel_dec(GemvP p) {
         __builtin_amdgcn_sched_barrier(0);
         pre_finish<NB, K, PRO>(p, pre, act, sc);
     } else {
-        if constexpr (epi_has_operand<EOP>()) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);  // the weight stream is issued before anything the prologue reads
         prologue<NB, K, PRO>(p, act, red, sc);
     }
 
@@ -277,8 +280,14 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_q8_kernel_dec(GemvP p) {
 constexpr int LTQ_U = LTF / LTQ_P;  // hidden units per partial sum
 // (the deferred merge at batch 1 is the Q8_0 head's PRO_LTQ_MERGE prologue: LTQ_P partials)
 template <bool RED, bool DEFER, int WP>
-__global__ __launch_bounds__(MP_BLOCK) void lt_slot_q8_kernel(LtSlotQ8P p) {
+__global__ __launch_bounds__(MP_BLOCK) void lt_slot_q8_kernel(const float *logits, const float *ltk, const float *ltv,
+                                                              const int *step, const float *lt_pos,
+                                                              unsigned long long *ts, int cb_lead, int smp_on,
+                                                              LtSlotQ8P p) {
 #pragma clang fp contract(off)
+    // leading arguments (mp_decode.hip, gemv_kernel's note): what the pick's first loads read, and ts
+    p.g.logits = logits; p.g.ltk = ltk; p.g.ltv = ltv; p.g.step = step; p.g.lt_pos = lt_pos; p.ts = ts;
+    p.g.cb = cb_lead; p.g.smp.on = smp_on;
     const unsigned long long t_start = ts_begin(p.ts);
     constexpr int PPW = LTQ_P / WP, UW = LTF / WP, UWW = UW / MP_NWAVES, RWG = LTD / WP, RWW = RWG / MP_NWAVES;
     constexpr int NPT = LTQ_P * RWG / MP_BLOCK;  // merge: partial granules per thread
@@ -536,10 +545,12 @@ hipError_t op_lt_slot_q8(const LtSlotQ8P &p, int NB, hipStream_t s) {
         (g.cb > 0 && (!g.logits || !g.codes_cur || !g.qkvtab || !g.ptab || !g.lt_pos || !g.step || !g.smp.cfg ||
                       !g.smp.argeos)))
         return hipErrorInvalidValue;
-    if (p.part) mp::launch(lt_slot_q8_kernel<true, true, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, p);
-    else if (p.wot) mp::launch(lt_slot_q8_kernel<true, false, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, p);
-    else if (NB >= 8) mp::launch(lt_slot_q8_kernel<false, false, 32>, dim3(32, NB), dim3(MP_BLOCK), 0, s, p);
-    else mp::launch(lt_slot_q8_kernel<false, false, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, p);
+#define LTQ8_ARGS p.g.logits, p.g.ltk, p.g.ltv, p.g.step, p.g.lt_pos, p.ts, p.g.cb, p.g.smp.on, p
+    if (p.part) mp::launch(lt_slot_q8_kernel<true, true, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
+    else if (p.wot) mp::launch(lt_slot_q8_kernel<true, false, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
+    else if (NB >= 8) mp::launch(lt_slot_q8_kernel<false, false, 32>, dim3(32, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
+    else mp::launch(lt_slot_q8_kernel<false, false, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
+#undef LTQ8_ARGS
     return hipGetLastError();
 }
 
@@ -1051,21 +1062,32 @@ static hipError_t launch_q8(const GemvP &p, hipStream_t s) {
     GemvP q = p;
     q.nrow_blocks = (p.N + 15) / 16;
     const int grid = q.nrow_blocks + (EPI == EPI_QKV_SA ? NH * SA_SPLITS * NB : EPI == EPI_RESID_XQ8 ? (NB <= XQ8_QIN_NB && p.xq8.qin ? XQ8A : XQG + XQ8A) * NB : 0);
-    if (p.q4) mp::launch((gemm_q8_kernel_dec<NB, K, PRO, EPI, true>), dim3(grid), dim3(MP_BLOCK), 0, s, q);
-    else mp::launch((gemm_q8_kernel_dec<NB, K, PRO, EPI, false>), dim3(grid), dim3(MP_BLOCK), 0, s, q);
+    const float *aux = (PRO == PRO_LTQ_MERGE || PRO == PRO_LTFFN_MERGE) ? q.addsrc : q.lnw;
+    if (p.q4)
+        mp::launch((gemm_q8_kernel_dec<NB, K, PRO, EPI, true>), dim3(grid), dim3(MP_BLOCK), 0, s, q.Wq, q.Wd, q.src, q.part,
+                   aux, q.ts, q.src_ld, q.nrow_blocks, q);
+    else
+        mp::launch((gemm_q8_kernel_dec<NB, K, PRO, EPI, false>), dim3(grid), dim3(MP_BLOCK), 0, s, q.Wq, q.Wd, q.src, q.part,
+                   aux, q.ts, q.src_ld, q.nrow_blocks, q);
     return hipGetLastError();
 }
 
 // Named entry points of the Q8_0 projections of one decode iteration (the
 // pos_ff conv weights stay F32 in the reference's Q8 file and run on the f32
 // GEMV family), instantiated for NB in {1, 2, 4, 8, 16}.
+// (never launched from 8 slots, where lt_pick_kernel + lt_bo run instead: no kernel there)
+template <int NB>
+static hipError_t launch_lt_bg_q8(const GemvP &p, hipStream_t s) {
+    if constexpr (NB >= 8) return hipErrorInvalidValue;
+    else return launch_q8<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s);
+}
 #define MP_Q8_OPS(NB)                                                                                                  \
     hipError_t q8_qkv_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_LN, EPI_QKV>(p, s); }             \
     hipError_t q8_oproj_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_SA_MERGE, EPI_RESID>(p, s); }      \
     hipError_t q8_xq_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_LN, EPI_STORE>(p, s); }            \
     hipError_t q8_lt_in0_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_LN, EPI_BIAS>(p, s); }         \
     hipError_t q8_lt_a_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, LTD, PRO_LTX_LN, EPI_LTQKV>(p, s); }    \
-    hipError_t q8_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); } \
+    hipError_t q8_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_lt_bg_q8<NB>(p, s); } \
     hipError_t q8_lt_b_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE>(p, s); } \
     hipError_t q8_lt_e_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, LTD, PRO_PLAIN, EPI_BIAS>(p, s); } \
     hipError_t q8_qkv_sa_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_LN, EPI_QKV_SA>(p, s); }   \

@@ -540,7 +540,6 @@ template <int K>
 struct Ln1Row {
     static constexpr int PER = K / 64;
     float v[PER], g[PER];
-    int s;  // trace row (block 0 with a trace only)
 };
 template <int K>
 __device__ __forceinline__ void ln1_load(const GemvP &p, Ln1Row<K> &r) {
@@ -548,7 +547,6 @@ __device__ __forceinline__ void ln1_load(const GemvP &p, Ln1Row<K> &r) {
 #pragma unroll
     for (int i = 0; i < Ln1Row<K>::PER; ++i) r.v[i] = p.src[lane + 64 * i];
     load_lnw<Ln1Row<K>::PER>(p.lnw, r.g);
-    r.s = (p.trace && blockIdx.x == 0) ? p.step[0] : 0;
 }
 template <int K>
 __device__ __forceinline__ void ln1_finish(const GemvP &p, Ln1Row<K> &r, float *act) {
@@ -558,7 +556,9 @@ __device__ __forceinline__ void ln1_finish(const GemvP &p, Ln1Row<K> &r, float *
     wave_meanvar<PER>(r.v, mean, var);
     const float rstd = 1.0f / sqrtf(var + p.eps);
     const bool st = p.hidden_out && blockIdx.x == 0;
-    const int s = r.s;
+    // the trace row (block 0 with a trace only), read here and not with the row: p.trace and
+    // p.step are not leading kernel arguments, and the row's loads must wait for no scalar load
+    const int s = (p.trace && blockIdx.x == 0) ? p.step[0] : 0;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
         if (i / Q != w) continue;

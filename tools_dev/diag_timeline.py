@@ -60,6 +60,14 @@ def main():
                 if okk.any():
                     v = rel[:nb, 4 + k, 1][okk]
                     line += f" | ph{k} {np.median(v):5.2f}/{v.max():5.2f}"
+        if os.environ.get("PHASES") and not ROLE_SPLIT.get(n) and ok[:nb, 4:].any():
+            # the kernel's entry: each workgroup's earliest phase stamp (GEMV: weights issued;
+            # lt_ffn2: wave 0's own loads landed) after that workgroup's own start
+            ph = np.where(ok[:nb, 4:], r[:nb, 4:, 1], np.iinfo(np.int64).max).min(axis=1)
+            own = r[:nb, 0, 0]
+            good = ok[:nb, 4:].any(axis=1) & ok[:nb, 0]
+            d = (ph - own)[good] * 0.01
+            line += f" | entry (first phase - own start) p50 {np.median(d):5.2f} min {d.min():5.2f}"
         print(line)
         # launches with two roles (row workgroups, then the attention tail): each apart
         nrow = ROLE_SPLIT.get(n)
