@@ -394,13 +394,15 @@ static hipError_t launch_gemv(const GemvP &p, hipStream_t s) {
 
 // Named entry points (one per fused op of the decode iteration), instantiated
 // for NB in {1, 2, 4, 8}.
-// rows per wave of the QKV and FFN-up GEMVs (2: 288 / 384 workgroups at 2304 / 3072 rows);
+// rows per wave of the QKV and FFN-up GEMVs (QKV 2: 288 workgroups at 2304 rows; FFN-up 4:
+// 192 workgroups at 3072 rows, at most one per CU: with 2 rows, 384 workgroups, the second
+// workgroup on a CU issued its weights up to 1.7 us late);
 // any value computes the same bits (each wave's rows are independent)
 #ifndef MP_RW_QKV
 #define MP_RW_QKV 2
 #endif
 #ifndef MP_RW_FF1
-#define MP_RW_FF1 2
+#define MP_RW_FF1 4
 #endif
 constexpr int RW_QKV = MP_RW_QKV, RW_FF1 = MP_RW_FF1;
 #define MP_DECODE_OPS(NB)                                                                                        \

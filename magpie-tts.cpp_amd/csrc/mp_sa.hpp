@@ -14,8 +14,9 @@ constexpr int SA_IF = 4;  // key rounds in flight per wave
 
 // Split sp of head h, slot b: keys [sp*chunk, (sp+1)*chunk) of L = pos + 1
 // (magpie.cpp:3412); wave w takes keys 4(w + NW r) + kk of it (16 lanes x float4
-// cover one 64-dim row, a wave does 4 keys per instruction) with SA_IF rounds'
-// K and V loads in flight, keeps an online softmax (m, l, o[64]); the NW wave
+// cover one 64-dim row, a wave does 4 keys per instruction) in batches of SA_IF
+// rounds, two batches' K and V loads in flight from entry (the second where the split
+// has one), keeps an online softmax (m, l, o[64]), one update per batch; the NW wave
 // states are merged in LDS and the split's state (m, l, unnormalised O) is
 // stored; the O-projection's PRO_SA_MERGE prologue merges the splits
 // (softmax(K q / 8) V per head, 3457-3476).
@@ -46,13 +47,24 @@ __device__ __forceinline__ void sa_part(const AttnP &p, int h, int sp, int b, co
     // keys past the split re-read its last cached row (an L1/L2 hit, no extra HBM
     // traffic); rows < max_seq are valid memory: no load waits for the mask
     const int jcap = HANDOFF ? max(min(j1, jn) - 1, 0) : max(j1 - 1, 0);
-    float4 k4[SA_IF], v4[SA_IF];
+    // Two batches (SA_IF rounds, 4 NW SA_IF keys of the split each) of registers, a ring:
+    // both are issued here, ahead of the hand-off wait, so a split of up to two batches
+    // (L <= 512) pays one memory round trip, and it overlaps the wait. The second batch
+    // goes out only where the split has one (workgroup-uniform): a split of one batch
+    // issues exactly its own loads.
+    constexpr int BK = 4 * NW * SA_IF;
+    float4 ka[SA_IF], va[SA_IF], kb[SA_IF], vb[SA_IF];
+    auto issue = [&](float4 (&k4)[SA_IF], float4 (&v4)[SA_IF], int r0) {
 #pragma unroll
-    for (int u = 0; u < SA_IF; ++u) {
-        const int j = min(j0 + 4 * (w + NW * u) + kk, jcap);
-        k4[u] = kv_load4<KV16>(p.kc, base + (size_t)j * D);
-        v4[u] = kv_load4<KV16>(p.vc, base + (size_t)j * D);
-    }
+        for (int u = 0; u < SA_IF; ++u) {
+            const int j = min(j0 + 4 * (w + NW * (r0 + u)) + kk, jcap);
+            k4[u] = kv_load4<KV16>(p.kc, base + (size_t)j * D);
+            v4[u] = kv_load4<KV16>(p.vc, base + (size_t)j * D);
+        }
+    };
+    const bool more = j0 + BK < j1;
+    issue(ka, va, 0);
+    if (more) issue(kb, vb, SA_IF);
     float4 q4, kn4 = make_float4(0.f, 0.f, 0.f, 0.f), vn4 = kn4;
     if constexpr (HANDOFF) {
         // one poller per array: wave 0 sweeps q, waves 1 and 2 the new key's k and v (when
@@ -90,15 +102,8 @@ __device__ __forceinline__ void sa_part(const AttnP &p, int h, int sp, int b, co
     }
     float m = -INFINITY, l = 0.f;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int r0 = 0; j0 + 4 * NW * r0 < j1; r0 += SA_IF) {
-        if (r0) {
-#pragma unroll
-            for (int u = 0; u < SA_IF; ++u) {
-                const int j = min(j0 + 4 * (w + NW * (r0 + u)) + kk, jcap);
-                k4[u] = kv_load4<KV16>(p.kc, base + (size_t)j * D);
-                v4[u] = kv_load4<KV16>(p.vc, base + (size_t)j * D);
-            }
-        }
+    // one online-softmax update per batch (rounds r0 .. r0 + SA_IF - 1), from its registers
+    auto consume = [&](float4 (&k4)[SA_IF], float4 (&v4)[SA_IF], int r0) {
         float sv[SA_IF];
         float mb = -INFINITY;
 #pragma unroll
@@ -110,7 +115,7 @@ __device__ __forceinline__ void sa_part(const AttnP &p, int h, int sp, int b, co
             mb = fmaxf(mb, sv[u]);
         }
         mb = wave_max(mb);
-        if (mb == -INFINITY) continue;  // nothing live for this wave in this round
+        if (mb == -INFINITY) return;  // nothing live for this wave in this batch
         const float mn = fmaxf(m, mb), c = expf(m - mn);
         l *= c;
         o.x *= c; o.y *= c; o.z *= c; o.w *= c;
@@ -122,6 +127,26 @@ __device__ __forceinline__ void sa_part(const AttnP &p, int h, int sp, int b, co
             o.z = fmaf(e, v4[u].z, o.z); o.w = fmaf(e, v4[u].w, o.w);
         }
         m = mn;
+    };
+    // While a batch is consumed (from kb, after the first) the next one is in flight, and
+    // the one after it, where the split has one, is issued into the registers the last one
+    // freed (ka) and handed to kb once its batch is done: a third and a fourth batch (L >
+    // 512, > 768) overlap their round trip with the batch before them. Nothing is issued
+    // past the split (a load nobody consumes is still waited for when its registers are
+    // reused), and an issue is never followed by a join with a path that did not issue
+    // before the batch in flight is consumed (the compiler's load count there would be
+    // the shorter path's, and that batch's wait would take in the loads just issued).
+    consume(ka, va, 0);
+    if (more) {
+        int r0 = SA_IF;
+#pragma nounroll
+        for (; j0 + 4 * NW * (r0 + SA_IF) < j1; r0 += SA_IF) {
+            issue(ka, va, r0 + SA_IF);
+            consume(kb, vb, r0);
+#pragma unroll
+            for (int u = 0; u < SA_IF; ++u) { kb[u] = ka[u]; vb[u] = va[u]; }
+        }
+        consume(kb, vb, r0);
     }
     ts_phase<1>(ts, t_start);  // profiling: this (first) wave's keys done
     // merge the 4 key groups of the wave (lanes l, l^16, l^32, l^48 share dims)

@@ -3,7 +3,10 @@
 of one decode iteration, the spread of workgroup start / intermediate mark
 (ts_mark: e.g. the bf16 kernels' staged activation tile, the fused XA's x1 seen) /
 end times, us after the op's first wave start.
-usage: diag_timeline.py WEIGHTS B [op ...]"""
+usage: diag_timeline.py WEIGHTS B [op ...]
+TS_FRAMES=N (default 128): frames decoded before the stamped iteration, which then runs
+at cache length L = 111 + N (the SA tail's second K/V batch starts at L = 257, its third
+at L = 513)."""
 import os
 import sys
 
@@ -14,7 +17,7 @@ sys.path.insert(0, os.path.join(REPO, "magpie-tts.cpp_amd"))
 import magpie_amd as ma  # noqa: E402
 
 TS_WAVES, TS_BLOCKS = 8, 1024
-ROLE_SPLIT = {}  # op name -> row workgroups (set per batch in main)
+ROLE_SPLIT = {}  # op name -> tail workgroups at the end of the launch (set per batch in main)
 
 
 def main():
@@ -28,11 +31,13 @@ def main():
     dump = os.path.join(REPO, "gpurun_out", "ts_dump.bin")
     os.makedirs(os.path.dirname(dump), exist_ok=True)
     os.environ["MAGPIE_TS_DUMP"] = dump
+    frames = int(os.environ.get("TS_FRAMES", "128"))
+    print(f"# {weights} B={B}, stamped iteration at L = {111 + frames}")
     dev = ma.Device(model, weights=weights)
     toks = [ma.synthetic_tokens(64, seed=1000 + b) for b in range(B)]
-    dev.synthesize(toks, speakers=[b % 5 for b in range(B)], max_dec_steps=128, ignore_eos=True)
+    dev.synthesize(toks, speakers=[b % 5 for b in range(B)], max_dec_steps=frames, ignore_eos=True)
     names = dev.ops()
-    ROLE_SPLIT.update({"oproj_xa": 48, "qkv_sa": 144})
+    ROLE_SPLIT.update({"oproj_xa": 4 * B, "qkv_sa": 48 * B})  # XA_SPLITS x B, NH x SA_SPLITS x B
     dev.profile_ops_ts(iters=2)
     raw = np.fromfile(dump, dtype=np.uint64).reshape(len(names), TS_BLOCKS, TS_WAVES, 2).astype(np.int64)
     seen = set()
@@ -70,8 +75,8 @@ def main():
             line += f" | entry (first phase - own start) p50 {np.median(d):5.2f} min {d.min():5.2f}"
         print(line)
         # launches with two roles (row workgroups, then the attention tail): each apart
-        nrow = ROLE_SPLIT.get(n)
-        if nrow and nb > nrow:
+        nrow = nb - ROLE_SPLIT.get(n, nb)
+        if nrow > 0:
             for lo, hi, role in ((0, nrow, "rows"), (nrow, nb, "tail")):
                 okr = ok[lo:hi, :4]
                 e2 = rel[lo:hi, :4, 1][okr]
