@@ -18,6 +18,7 @@
 
 #include "mp_device.hpp"
 #include "mp_fused.hpp"
+#include "mp_ops.hpp"
 #include "mp_params.hpp"
 #include "mp_sa.hpp"
 #include "mp_xa.hpp"
@@ -176,9 +177,10 @@ __global__ __launch_bounds__(MP_BLOCK) void gemv_kernel(const float *W, const fl
 // ---------------------------------------------------------------- SA decode attention
 // Split-K over the live cache (sa_part, mp_sa.hpp): grid (head, split, slot), 4
 // waves per workgroup; at batch 1 that is 48 workgroups of ~L/4 keys each instead
-// of one workgroup streaming a whole head. Layers >= 1 of the f32 and 16-bit
-// families run the same body in their QKV launch (EPI_QKV_SA) below 16 slots;
-// this kernel serves layer 0, 16 slots and the Q8_0 mode.
+// of one workgroup streaming a whole head. Every family runs the same body in its
+// QKV launch (EPI_QKV_SA) below 16 slots, the bf16 mode at 16 too (MAGPIE_SA16);
+// this kernel serves the other lists: 16 slots of the F16 and Q8_0 modes,
+// MAGPIE_SA16=0, and the Q8_0 tensors' unfused form (MAGPIE_Q8_UNFUSED=1).
 constexpr int SA_WAVES = MP_NWAVES, SA_THREADS = SA_WAVES * 64;
 template <bool KV16>
 __global__ __launch_bounds__(SA_THREADS) void sa_attn_kernel(AttnP p) {
@@ -348,40 +350,9 @@ __global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *l
 }
 
 // ---------------------------------------------------------------- host launchers
-// Host-side check that every pointer the (PRO, EPI) pair dereferences is set:
-// a mismatch between an op's compile-time epilogue and its arguments must fail
-// at launch, not fault on the device.
-template <int PRO, int EPI>
-static bool gemv_args_ok(const GemvP &p) {
-    if (!p.W || p.N <= 0) return false;
-    bool ok = true;
-    if constexpr (PRO == PRO_PLAIN) ok &= p.src != nullptr;
-    if constexpr (PRO == PRO_SA_MERGE) ok &= p.part != nullptr;
-    if constexpr (PRO == PRO_LTFFN_MERGE) ok &= p.part && p.addsrc;
-    if constexpr (PRO == PRO_XA_LN) ok &= p.part && p.src && p.lnw && p.xres;
-    if constexpr (PRO == PRO_LN) ok &= p.src && p.lnw;
-    if constexpr (PRO == PRO_LTX_LN) ok &= p.lt_s && p.lt_pos && p.ltX && p.lnw;
-    if constexpr (PRO == PRO_LT_ATTN) ok &= p.ltq && p.ltk && p.ltv;
-    if constexpr (PRO == PRO_LTARG_ATTN)
-        ok &= p.logits && p.codes_cur && p.qkvtab && p.lk && p.lv && p.ltk && p.ltv && p.step && p.smp.cfg && p.smp.argeos;
-    if constexpr (EPI == EPI_STORE || EPI == EPI_GELU) ok &= p.out != nullptr;
-    if constexpr (EPI == EPI_BIAS) ok &= p.out && p.bias;
-    if constexpr (EPI == EPI_RESID) ok &= p.resid != nullptr;
-    if constexpr (EPI == EPI_ADD_STORE) ok &= p.out && p.addsrc;
-    if constexpr (EPI == EPI_LTX_ADD) ok &= p.out && p.ptab && p.lt_pos && p.cb >= 1;
-    if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_SA) ok &= p.out && p.kc && p.vc && p.pos;
-    if constexpr (EPI == EPI_QKV_SA) ok &= qkv_sa_args_ok(p);
-    if constexpr (EPI == EPI_LTQKV) ok &= p.lq && p.lk && p.lv;
-    if constexpr (EPI == EPI_LTKVO) ok &= p.lk && p.lv && p.N == 2 * LTD;
-    if constexpr (EPI == EPI_RESID_XA)
-        ok &= p.resid && p.xh && p.iter && p.hx_err && p.N == D && p.xa.part && p.xa.lnw && p.xa.kp && p.xa.vp &&
-              p.xa.T && p.xa.Tmax >= 1 && p.xa.Tmax <= TMAX_LIMIT;
-    return ok;
-}
-
 template <int NB, int RW, int K, int PRO, int EPI>
 static hipError_t launch_gemv(const GemvP &p, hipStream_t s) {
-    if (!gemv_args_ok<PRO, EPI>(p)) return hipErrorInvalidValue;
+    if (!p.W || p.N <= 0 || !gemv_args_ok<PRO, EPI>(p)) return hipErrorInvalidValue;
     const int rows_per_block = MP_NWAVES * RW;
     GemvP q = p;
     q.nrow_blocks = (p.N + rows_per_block - 1) / rows_per_block;
@@ -392,8 +363,8 @@ static hipError_t launch_gemv(const GemvP &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Named entry points (one per fused op of the decode iteration), instantiated
-// for NB in {1, 2, 4, 8}.
+// The family's op table (mp_ops.hpp): the fused ops of the decode iteration for NB in
+// {1, 2, 4, 8}, and at 16 slots the ops another weight mode's list runs on f32 tensors.
 // rows per wave of the QKV and FFN-up GEMVs (QKV 2: 288 workgroups at 2304 rows; FFN-up 4:
 // 192 workgroups at 3072 rows, at most one per CU: with 2 rows, 384 workgroups, the second
 // workgroup on a CU issued its weights up to 1.7 us late);
@@ -404,51 +375,50 @@ static hipError_t launch_gemv(const GemvP &p, hipStream_t s) {
 #ifndef MP_RW_FF1
 #define MP_RW_FF1 4
 #endif
-constexpr int RW_QKV = MP_RW_QKV, RW_FF1 = MP_RW_FF1;
-#define MP_DECODE_OPS(NB)                                                                                        \
-    hipError_t op_qkv_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, RW_QKV, D, PRO_LN, EPI_QKV>(p, s); }        \
-    hipError_t op_qkv_sa_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, RW_QKV, D, PRO_LN, EPI_QKV_SA>(p, s); }  \
-    hipError_t op_xq_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, D, PRO_LN, EPI_STORE>(p, s); }            \
-    hipError_t op_oproj_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, D, PRO_SA_MERGE, EPI_RESID>(p, s); } \
-    hipError_t op_oproj_xa_##NB(const GemvP &p, hipStream_t s) {                                                   \
-        return launch_gemv<NB, 1, D, PRO_SA_MERGE, EPI_RESID_XA>(p, s);                                            \
-    }                                                                                                              \
-    hipError_t op_ff1_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, RW_FF1, D, PRO_LN, EPI_GELU>(p, s); }       \
-    hipError_t op_ff1x_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, RW_FF1, D, PRO_XA_LN, EPI_GELU>(p, s); }   \
-    hipError_t op_ff2_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, DFF, PRO_PLAIN, EPI_ADD_STORE>(p, s); }  \
-    hipError_t op_lt_in0_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, D, PRO_LN, EPI_BIAS>(p, s); }         \
-    hipError_t op_lt_a_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTD, PRO_LTX_LN, EPI_LTQKV>(p, s); }    \
-    hipError_t op_lt_b_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTD, PRO_LT_ATTN, EPI_ADD_STORE>(p, s); } \
-    hipError_t op_lt_c_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTD, PRO_LN, EPI_GELU>(p, s); }         \
-    hipError_t op_lt_d_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 1, LTF, PRO_PLAIN, EPI_ADD_STORE>(p, s); } \
-    hipError_t op_lt_e_##NB(const GemvP &p, hipStream_t s) { return launch_gemv<NB, 2, LTD, PRO_PLAIN, EPI_BIAS>(p, s); }      \
-
-
-MP_DECODE_OPS(1)
-MP_DECODE_OPS(2)
-MP_DECODE_OPS(4)
-MP_DECODE_OPS(8)
-// the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots the runtime
-// launches lt_pick_kernel + lt_bo instead (the fused prologue would run a wave's slots'
-// picks in sequence), so the op table's entry for 8 is never launched and holds no kernel
-hipError_t op_lt_bg_1(const GemvP &p, hipStream_t s) { return launch_gemv<1, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); }
-hipError_t op_lt_bg_2(const GemvP &p, hipStream_t s) { return launch_gemv<2, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); }
-hipError_t op_lt_bg_4(const GemvP &p, hipStream_t s) { return launch_gemv<4, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s); }
-hipError_t op_lt_bg_8(const GemvP &, hipStream_t) { return hipErrorInvalidValue; }
-// LT in_proj of a caller-supplied (already normalised) hidden vector, batch 1
-// (magpie_local_transformer_sample_all, magpie.cpp:1161-1163)
-hipError_t op_lt_inh_1(const GemvP &p, hipStream_t s) { return launch_gemv<1, 1, D, PRO_PLAIN, EPI_BIAS>(p, s); }
-// bf16 weight mode at 16 slots: only the f32 LT in_proj runs on the GEMV family
-hipError_t op_lt_in0_16(const GemvP &p, hipStream_t s) { return launch_gemv<16, 1, D, PRO_LN, EPI_BIAS>(p, s); }
-// Q8_0 weight mode at 16 slots: the FFN convs (F32 in the reference's Q8 file)
-hipError_t op_ff1_16(const GemvP &p, hipStream_t s) { return launch_gemv<16, 2, D, PRO_LN, EPI_GELU>(p, s); }
 #ifndef MP_RW_FF2_16
 #define MP_RW_FF2_16 1
 #endif
-hipError_t op_ff2_16(const GemvP &p, hipStream_t s) { return launch_gemv<16, MP_RW_FF2_16, DFF, PRO_PLAIN, EPI_ADD_STORE>(p, s); }
-// the direct XA's f32 q_net at 16 slots (bf16 mode)
-hipError_t op_xq_16(const GemvP &p, hipStream_t s) { return launch_gemv<16, 1, D, PRO_LN, EPI_STORE>(p, s); }
-
+constexpr int RW_QKV = MP_RW_QKV, RW_FF1 = MP_RW_FF1;
+template <int NB>
+static OpTable make_f32_ops() {
+    OpTable t{};
+    if constexpr (NB <= 8) {
+        t.qkv = &launch_gemv<NB, RW_QKV, D, PRO_LN, EPI_QKV>;
+        t.qkv_sa = &launch_gemv<NB, RW_QKV, D, PRO_LN, EPI_QKV_SA>;
+        t.oproj = &launch_gemv<NB, 1, D, PRO_SA_MERGE, EPI_RESID>;
+        t.oproj_xa = &launch_gemv<NB, 1, D, PRO_SA_MERGE, EPI_RESID_XA>;
+        t.ff1x = &launch_gemv<NB, RW_FF1, D, PRO_XA_LN, EPI_GELU>;
+        // the generic LT steps: a Q8_0 file's F32 LT projections (build_lt's last branch)
+        t.lt_a = &launch_gemv<NB, 1, LTD, PRO_LTX_LN, EPI_LTQKV>;
+        t.lt_b = &launch_gemv<NB, 1, LTD, PRO_LT_ATTN, EPI_ADD_STORE>;
+        // the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots
+        // lt_pick_kernel + lt_bo (the fused prologue would run a wave's slots' picks in sequence)
+        if constexpr (NB < 8) t.lt_bg = &launch_gemv<NB, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>;
+        else t.lt_bo = &launch_gemv<NB, 1, LTD, PRO_PLAIN, EPI_ADD_STORE>;
+        // (batch 1: every list takes the head with the FFN merge as its prologue)
+        if constexpr (NB > 1) t.lt_e = &launch_gemv<NB, 2, LTD, PRO_PLAIN, EPI_BIAS>;
+    }
+    // also at 16 slots: the FFN convs of a Q8_0 / Q4_0 file (F32 in the reference's Q8 file;
+    // FFN-up 2 rows per wave there), and the bf16 mode's f32 LT in_proj and direct-XA q_net
+    t.ff1 = &launch_gemv<NB, NB == 16 ? 2 : RW_FF1, D, PRO_LN, EPI_GELU>;
+    t.ff2 = &launch_gemv<NB, NB == 16 ? MP_RW_FF2_16 : 1, DFF, PRO_PLAIN, EPI_ADD_STORE>;
+    t.xq = &launch_gemv<NB, 1, D, PRO_LN, EPI_STORE>;
+    t.lt_in0 = &launch_gemv<NB, 1, D, PRO_LN, EPI_BIAS>;
+    if constexpr (NB == 1) {
+        // LT in_proj of a caller-supplied (already normalised) hidden vector
+        // (magpie_local_transformer_sample_all, magpie.cpp:1161-1163)
+        t.lt_inh = &launch_gemv<1, 1, D, PRO_PLAIN, EPI_BIAS>;
+        // the LT head with the FFN merge as its prologue: lt_ffn2_kernel's and
+        // lt_ffn_kernel's partial sums have one layout
+        t.lt_em = t.lt_emf = &launch_gemv<1, MP_RW_LTE, LTD, PRO_LTFFN_MERGE, EPI_BIAS>;
+    }
+    return t;
+}
+const OpTable &f32_ops(int NB) {
+    static const OpTable t[5] = {make_f32_ops<1>(), make_f32_ops<2>(), make_f32_ops<4>(), make_f32_ops<8>(),
+                                 make_f32_ops<16>()};
+    return t[op_nb_index(NB)];
+}
 
 hipError_t op_sa_attn(const AttnP &p, int B, hipStream_t s) {
     if (!p.q || !p.kc || !p.vc || !p.pos || !p.part || p.max_seq < 1 || p.max_seq > NCH_MAX * SA_CHUNK)
@@ -504,8 +474,6 @@ hipError_t op_lt_pick(const GemvP &p, int NB, hipStream_t s) {
     mp::launch(lt_pick_kernel, dim3(NB), dim3(64), 0, s, p);
     return hipGetLastError();
 }
-// o_net + residual after lt_pick_kernel (its attention output in src, residual in addsrc)
-hipError_t op_lt_bo_8(const GemvP &p, hipStream_t s) { return launch_gemv<8, 1, LTD, PRO_PLAIN, EPI_ADD_STORE>(p, s); }
 
 // ---------------------------------------------------------------- frame embedding
 // One workgroup per slot; each element summed over the 8 codebooks in order, /8,
@@ -1229,8 +1197,6 @@ hipError_t op_lt_front(const LtFrontP &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the LT head at batch 1 with the FFN merge as its prologue
-hipError_t op_lt_em_1(const GemvP &p, hipStream_t s) { return launch_gemv<1, MP_RW_LTE, LTD, PRO_LTFFN_MERGE, EPI_BIAS>(p, s); }
 // f32 LT position 0: LN(X_0) -> [k_0 | vo_0] (W = [W_k ; W_o W_v], 512 x 256)
 hipError_t op_lt_kvo(const GemvP &p, int NB, hipStream_t s) {
     switch (NB) {

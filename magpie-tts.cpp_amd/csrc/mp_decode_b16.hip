@@ -20,6 +20,7 @@
 
 #include "mp_device.hpp"
 #include "mp_fused.hpp"
+#include "mp_ops.hpp"
 #include "mp_params.hpp"
 #include "mp_sa.hpp"
 #include "mp_xa.hpp"
@@ -379,38 +380,9 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_b16_kernel(const unsigned short
     ts_end(p.ts, t_start);
 }
 
-template <int PRO, int EPI>
-static bool b16_args_ok(const GemvP &p) {
-    if (!p.Wb || p.N <= 0) return false;
-    bool ok = true;
-    if constexpr (PRO == PRO_PLAIN) ok &= p.src != nullptr;
-    if constexpr (PRO == PRO_PLAIN_B16) ok &= p.src_b16 != nullptr;
-    if constexpr (PRO == PRO_SA_MERGE) ok &= p.part != nullptr;
-    if constexpr (PRO == PRO_LTS_MERGE) ok &= p.part && p.addsrc;
-    if constexpr (PRO == PRO_XA_LN) ok &= p.part && p.src && p.lnw && p.xres;
-    if constexpr (PRO == PRO_LN) ok &= p.src && p.lnw;
-    if constexpr (PRO == PRO_LTX_LN) ok &= p.lt_s && p.lt_pos && p.ltX && p.lnw;
-    if constexpr (PRO == PRO_LT_ATTN) ok &= p.ltq && p.ltk && p.ltv;
-    if constexpr (PRO == PRO_LTARG_ATTN)
-        ok &= p.logits && p.codes_cur && p.qkvtab && p.lk && p.lv && p.ltk && p.ltv && p.step && p.smp.cfg && p.smp.argeos;
-    if constexpr (EPI == EPI_STORE || EPI == EPI_GELU) ok &= p.out != nullptr;
-    if constexpr (EPI == EPI_GELU_B16 || EPI == EPI_GELU_F16) ok &= p.out_b16 != nullptr;
-    if constexpr (EPI == EPI_BIAS) ok &= p.out && p.bias;
-    if constexpr (EPI == EPI_RESID) ok &= p.resid != nullptr;
-    if constexpr (EPI == EPI_ADD_STORE) ok &= p.out && p.addsrc;
-    if constexpr (EPI == EPI_LTX_ADD) ok &= p.out && p.ptab && p.lt_pos && p.cb >= 1;
-    if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_SA) ok &= p.out && p.kc && p.vc && p.pos;
-    if constexpr (EPI == EPI_QKV_SA) ok &= qkv_sa_args_ok(p);
-    if constexpr (EPI == EPI_LTQKV) ok &= p.lq && p.lk && p.lv;
-    if constexpr (EPI == EPI_RESID_XA)
-        ok &= p.resid && p.xh && p.iter && p.hx_err && p.N == D && p.xa.part && p.xa.lnw && p.xa.kp && p.xa.vp &&
-              p.xa.T && p.xa.Tmax >= 1 && p.xa.Tmax <= TMAX_LIMIT;
-    return ok;
-}
-
 template <int NB, int K, int PRO, int EPI, bool F16 = false, int KS = 1>
 static hipError_t launch_b16(const GemvP &p, hipStream_t s) {
-    if (!b16_args_ok<PRO, EPI>(p)) return hipErrorInvalidValue;
+    if (!p.Wb || p.N <= 0 || !gemv_args_ok<PRO, EPI>(p)) return hipErrorInvalidValue;
     if (KS > 1 && (!p.kgh || !p.iter || !p.hx_err)) return hipErrorInvalidValue;
     GemvP q = p;
     q.nrow_blocks = (p.N + 15) / 16 * KS;  // row workgroups (KS per 16-row tile)
@@ -436,79 +408,50 @@ constexpr int FF2_KS = MP_FF2_KS;
 constexpr int OPROJ_KS = MP_OPROJ_KS;
 int b16_oproj_ks() { return OPROJ_KS; }
 
-// the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots the runtime
-// launches lt_pick_kernel + lt_bo instead, so the op tables' entries for 8 and 16 are never
-// launched and hold no kernel
+// The family's op tables (mp_ops.hpp), bf16 and F16 weights. The bf16 mode runs its local
+// transformer on lt_slot_kernel (mp_decode.hip), so its table holds only the heads of it;
+// the F16 mode runs build_lt's generic steps on this family, the LT in_proj included
+// (the bf16 mode keeps that f32). The plain QKV exists at 16 slots only: below, every
+// 16-bit list runs the SA in the QKV launch.
 template <int NB, bool F16>
-static hipError_t launch_lt_bg(const GemvP &p, hipStream_t s) {
-    if constexpr (NB >= 8) return hipErrorInvalidValue;
-    else return launch_b16<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD, F16>(p, s);
+static OpTable make_b16_ops() {
+    OpTable t{};
+    if constexpr (NB == 16) t.qkv = &launch_b16<NB, D, PRO_LN, EPI_QKV, F16>;
+    t.qkv_sa = &launch_b16<NB, D, PRO_LN, EPI_QKV_SA, F16>;
+    t.oproj = &launch_b16<NB, D, PRO_SA_MERGE, EPI_RESID, F16, OPROJ_KS>;
+    t.oproj_xa = &launch_b16<NB, D, PRO_SA_MERGE, EPI_RESID_XA, F16, OPROJ_KS>;
+    t.ff1x = &launch_b16<NB, D, PRO_XA_LN, F16 ? EPI_GELU_F16 : EPI_GELU_B16, F16>;
+    t.ff2 = &launch_b16<NB, DFF, PRO_PLAIN_B16, EPI_ADD_STORE, F16, FF2_KS>;
+    t.lt_e = &launch_b16<NB, LTD, PRO_PLAIN, EPI_BIAS, F16>;
+    if constexpr (!F16) {
+        t.ff1 = &launch_b16<NB, D, PRO_LN, EPI_GELU_B16>;
+        // 8 and 16 slots: the O-projection + XA launch reads the SA output its split
+        // workgroups merged (plain rows), and its XA workgroups merge x2
+        if constexpr (NB >= 8) t.oproj_xa_pm = &launch_b16<NB, D, PRO_PLAIN, EPI_RESID_XA, false, OPROJ_KS>;
+        // batch 1: lt_slot_kernel's partial sums merged by the head's prologue
+        if constexpr (NB == 1) t.lt_em = &launch_b16<1, LTD, PRO_LTS_MERGE, EPI_BIAS>;
+    } else {
+        t.lt_in0 = &launch_b16<NB, D, PRO_LN, EPI_BIAS, true>;
+        if constexpr (NB == 1) t.lt_inh = &launch_b16<1, D, PRO_PLAIN, EPI_BIAS, true>;
+        t.lt_a = &launch_b16<NB, LTD, PRO_LTX_LN, EPI_LTQKV, true>;
+        t.lt_b = &launch_b16<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE, true>;
+        // the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots
+        // lt_pick_kernel, then o_net + residual
+        if constexpr (NB < 8) t.lt_bg = &launch_b16<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD, true>;
+        else t.lt_bo = &launch_b16<NB, LTD, PRO_PLAIN, EPI_ADD_STORE, true>;
+        t.lt_c = &launch_b16<NB, LTD, PRO_LN, EPI_GELU, true>;
+        t.lt_d = &launch_b16<NB, LTF, PRO_PLAIN, EPI_ADD_STORE, true>;
+    }
+    return t;
 }
-#define MP_B16_OPS(NB)                                                                                                  \
-    hipError_t b16_qkv_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_LN, EPI_QKV>(p, s); }             \
-    hipError_t b16_qkv_sa_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_LN, EPI_QKV_SA>(p, s); }       \
-    hipError_t b16_oproj_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_SA_MERGE, EPI_RESID, false, OPROJ_KS>(p, s); }   \
-    hipError_t b16_oproj_xa_##NB(const GemvP &p, hipStream_t s) {                                                      \
-        return launch_b16<NB, D, PRO_SA_MERGE, EPI_RESID_XA, false, OPROJ_KS>(p, s);                                   \
-    }                                                                                                                   \
-    hipError_t b16_ff1_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_XA_LN, EPI_GELU_B16>(p, s); }     \
-    hipError_t b16_ff1p_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_LN, EPI_GELU_B16>(p, s); }       \
-    hipError_t b16_ff2_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, DFF, PRO_PLAIN_B16, EPI_ADD_STORE, false, FF2_KS>(p, s); }  \
-    hipError_t b16_lt_a_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LTX_LN, EPI_LTQKV>(p, s); }    \
-    hipError_t b16_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_lt_bg<NB, false>(p, s); } \
-    hipError_t b16_lt_b_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE>(p, s); } \
-    hipError_t b16_lt_c_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LN, EPI_GELU>(p, s); }         \
-    hipError_t b16_lt_d_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTF, PRO_PLAIN, EPI_ADD_STORE>(p, s); } \
-    hipError_t b16_lt_e_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_PLAIN, EPI_BIAS>(p, s); }      \
-    hipError_t b16_lt_es_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_PLAIN, EPI_BIAS>(p, s); }      \
-    hipError_t b16_lt_em_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LTS_MERGE, EPI_BIAS>(p, s); }
-
-#define MP_F16_OPS(NB)                                                                                                  \
-    hipError_t f16_qkv_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_LN, EPI_QKV, true>(p, s); }             \
-    hipError_t f16_qkv_sa_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_LN, EPI_QKV_SA, true>(p, s); }       \
-    hipError_t f16_oproj_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_SA_MERGE, EPI_RESID, true, OPROJ_KS>(p, s); }   \
-    hipError_t f16_oproj_xa_##NB(const GemvP &p, hipStream_t s) {                                                      \
-        return launch_b16<NB, D, PRO_SA_MERGE, EPI_RESID_XA, true, OPROJ_KS>(p, s);                                   \
-    }                                                                                                                   \
-    hipError_t f16_ff1_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, D, PRO_XA_LN, EPI_GELU_F16, true>(p, s); }     \
-    hipError_t f16_ff2_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, DFF, PRO_PLAIN_B16, EPI_ADD_STORE, true, FF2_KS>(p, s); }  \
-    hipError_t f16_lt_a_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LTX_LN, EPI_LTQKV, true>(p, s); }    \
-    hipError_t f16_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_lt_bg<NB, true>(p, s); } \
-    hipError_t f16_lt_b_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE, true>(p, s); } \
-    hipError_t f16_lt_c_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_LN, EPI_GELU, true>(p, s); }         \
-    hipError_t f16_lt_d_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTF, PRO_PLAIN, EPI_ADD_STORE, true>(p, s); } \
-    hipError_t f16_lt_e_##NB(const GemvP &p, hipStream_t s) { return launch_b16<NB, LTD, PRO_PLAIN, EPI_BIAS, true>(p, s); }
-
-MP_B16_OPS(1)
-MP_B16_OPS(2)
-MP_B16_OPS(4)
-MP_B16_OPS(8)
-MP_B16_OPS(16)
-MP_F16_OPS(1)
-MP_F16_OPS(2)
-MP_F16_OPS(4)
-MP_F16_OPS(8)
-MP_F16_OPS(16)
-// bf16 mode at 8 and 16 slots: the O-projection + XA launch reads the SA output its
-// split workgroups merged (plain rows), and its XA workgroups merge x2
-hipError_t b16_oproj_xa_pm_16(const GemvP &p, hipStream_t s) {
-    return launch_b16<16, D, PRO_PLAIN, EPI_RESID_XA, false, OPROJ_KS>(p, s);
+const OpTable &b16_ops(int NB, bool f16) {
+    static const OpTable t[2][5] = {
+        {make_b16_ops<1, false>(), make_b16_ops<2, false>(), make_b16_ops<4, false>(), make_b16_ops<8, false>(),
+         make_b16_ops<16, false>()},
+        {make_b16_ops<1, true>(), make_b16_ops<2, true>(), make_b16_ops<4, true>(), make_b16_ops<8, true>(),
+         make_b16_ops<16, true>()}};
+    return t[f16][op_nb_index(NB)];
 }
-hipError_t b16_oproj_xa_pm_8(const GemvP &p, hipStream_t s) {
-    return launch_b16<8, D, PRO_PLAIN, EPI_RESID_XA, false, OPROJ_KS>(p, s);
-}
-// the LT in_proj of an F16 file is F16 too (the bf16 mode keeps it f32)
-hipError_t f16_lt_in0_1(const GemvP &p, hipStream_t s) { return launch_b16<1, D, PRO_LN, EPI_BIAS, true>(p, s); }
-hipError_t f16_lt_in0_2(const GemvP &p, hipStream_t s) { return launch_b16<2, D, PRO_LN, EPI_BIAS, true>(p, s); }
-hipError_t f16_lt_in0_4(const GemvP &p, hipStream_t s) { return launch_b16<4, D, PRO_LN, EPI_BIAS, true>(p, s); }
-hipError_t f16_lt_in0_8(const GemvP &p, hipStream_t s) { return launch_b16<8, D, PRO_LN, EPI_BIAS, true>(p, s); }
-hipError_t f16_lt_in0_16(const GemvP &p, hipStream_t s) { return launch_b16<16, D, PRO_LN, EPI_BIAS, true>(p, s); }
-hipError_t f16_lt_inh_1(const GemvP &p, hipStream_t s) { return launch_b16<1, D, PRO_PLAIN, EPI_BIAS, true>(p, s); }
-// o_net + residual after lt_pick_kernel (large batches)
-hipError_t b16_lt_bo_8(const GemvP &p, hipStream_t s) { return launch_b16<8, LTD, PRO_PLAIN, EPI_ADD_STORE>(p, s); }
-hipError_t b16_lt_bo_16(const GemvP &p, hipStream_t s) { return launch_b16<16, LTD, PRO_PLAIN, EPI_ADD_STORE>(p, s); }
-hipError_t f16_lt_bo_8(const GemvP &p, hipStream_t s) { return launch_b16<8, LTD, PRO_PLAIN, EPI_ADD_STORE, true>(p, s); }
-hipError_t f16_lt_bo_16(const GemvP &p, hipStream_t s) { return launch_b16<16, LTD, PRO_PLAIN, EPI_ADD_STORE, true>(p, s); }
 
 // f32 [N][K] -> bf16 (F16: f16) fragment order [ceil(N/16)][K/32][64][8], rows >= N
 // zero. f16: round to nearest even; exact for an F16 file's (widened) values.

@@ -35,6 +35,7 @@
 
 #include "mp_device.hpp"
 #include "mp_fused.hpp"
+#include "mp_ops.hpp"
 #include "mp_params.hpp"
 #include "mp_sa.hpp"
 #include "mp_xa.hpp"
@@ -1027,38 +1028,9 @@ hipError_t op_xa_q8(const XaQ8P &p, int B, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int PRO, int EPI>
-static bool q8_args_ok(const GemvP &p) {
-    if (!p.Wq || !p.Wd || p.N <= 0) return false;
-    bool ok = true;
-    if constexpr (PRO == PRO_PLAIN) ok &= p.src != nullptr;
-    if constexpr (PRO == PRO_SA_MERGE) ok &= p.part != nullptr;
-    if constexpr (PRO == PRO_LTFFN_MERGE || PRO == PRO_LTQ_MERGE) ok &= p.part && p.addsrc;
-    if constexpr (PRO == PRO_XA_LN) ok &= p.part && p.src && p.lnw && p.xres;
-    if constexpr (PRO == PRO_LN) ok &= p.src && p.lnw;
-    if constexpr (PRO == PRO_LTX_LN) ok &= p.lt_s && p.lt_pos && p.ltX && p.lnw;
-    if constexpr (PRO == PRO_LT_ATTN) ok &= p.ltq && p.ltk && p.ltv;
-    if constexpr (PRO == PRO_LTARG_ATTN)
-        ok &= p.logits && p.codes_cur && p.qkvtab && p.lk && p.lv && p.ltk && p.ltv && p.step && p.smp.cfg && p.smp.argeos;
-    if constexpr (EPI == EPI_STORE || EPI == EPI_GELU) ok &= p.out != nullptr;
-    if constexpr (EPI == EPI_BIAS) ok &= p.out && p.bias;
-    if constexpr (EPI == EPI_RESID) ok &= p.resid != nullptr;
-    if constexpr (EPI == EPI_ADD_STORE) ok &= p.out && p.addsrc;
-    if constexpr (EPI == EPI_LTX_ADD) ok &= p.out && p.ptab && p.lt_pos && p.cb >= 1;
-    if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_SA) ok &= p.out && p.kc && p.vc && p.pos;
-    if constexpr (EPI == EPI_QKV_SA) ok &= qkv_sa_args_ok(p);
-    if constexpr (EPI == EPI_LTQKV) ok &= p.lq && p.lk && p.lv;
-    if constexpr (EPI == EPI_RESID_XQ8) {
-        const XaQ8P &x = p.xq8;
-        ok &= p.resid && p.xh && p.iter && p.hx_err && p.N == D && x.qg && x.wq && x.wqd && x.lnw && x.x2 && x.wo &&
-              x.wod && x.xak && x.xav && x.T && x.Tmax >= 1 && x.Tmax <= TMAX_LIMIT && x.layer == p.layer;
-    }
-    return ok;
-}
-
 template <int NB, int K, int PRO, int EPI>
 static hipError_t launch_q8(const GemvP &p, hipStream_t s) {
-    if (!q8_args_ok<PRO, EPI>(p)) return hipErrorInvalidValue;
+    if (!p.Wq || !p.Wd || p.N <= 0 || !gemv_args_ok<PRO, EPI>(p)) return hipErrorInvalidValue;
     GemvP q = p;
     q.nrow_blocks = (p.N + 15) / 16;
     const int grid = q.nrow_blocks + (EPI == EPI_QKV_SA ? NH * SA_SPLITS * NB : EPI == EPI_RESID_XQ8 ? (NB <= XQ8_QIN_NB && p.xq8.qin ? XQ8A : XQG + XQ8A) * NB : 0);
@@ -1072,43 +1044,38 @@ static hipError_t launch_q8(const GemvP &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Named entry points of the Q8_0 projections of one decode iteration (the
-// pos_ff conv weights stay F32 in the reference's Q8 file and run on the f32
-// GEMV family), instantiated for NB in {1, 2, 4, 8, 16}.
-// (never launched from 8 slots, where lt_pick_kernel + lt_bo run instead: no kernel there)
+// The family's op table (mp_ops.hpp): the projections whose tensors are Q8_0 / Q4_0 in the
+// file (the pos_ff conv weights stay F32 in the reference's Q8 file and run on the f32
+// GEMV family), for NB in {1, 2, 4, 8, 16}.
 template <int NB>
-static hipError_t launch_lt_bg_q8(const GemvP &p, hipStream_t s) {
-    if constexpr (NB >= 8) return hipErrorInvalidValue;
-    else return launch_q8<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>(p, s);
-}
-#define MP_Q8_OPS(NB)                                                                                                  \
-    hipError_t q8_qkv_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_LN, EPI_QKV>(p, s); }             \
-    hipError_t q8_oproj_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_SA_MERGE, EPI_RESID>(p, s); }      \
-    hipError_t q8_xq_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_LN, EPI_STORE>(p, s); }            \
-    hipError_t q8_lt_in0_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_LN, EPI_BIAS>(p, s); }         \
-    hipError_t q8_lt_a_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, LTD, PRO_LTX_LN, EPI_LTQKV>(p, s); }    \
-    hipError_t q8_lt_bg_##NB(const GemvP &p, hipStream_t s) { return launch_lt_bg_q8<NB>(p, s); } \
-    hipError_t q8_lt_b_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE>(p, s); } \
-    hipError_t q8_lt_e_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, LTD, PRO_PLAIN, EPI_BIAS>(p, s); } \
-    hipError_t q8_qkv_sa_##NB(const GemvP &p, hipStream_t s) { return launch_q8<NB, D, PRO_LN, EPI_QKV_SA>(p, s); }   \
-    hipError_t q8_oproj_xq_##NB(const GemvP &p, hipStream_t s) {                                                    \
-        return launch_q8<NB, D, PRO_SA_MERGE, EPI_RESID_XQ8>(p, s);                                                  \
+static OpTable make_q8_ops() {
+    OpTable t{};
+    t.qkv = &launch_q8<NB, D, PRO_LN, EPI_QKV>;
+    t.qkv_sa = &launch_q8<NB, D, PRO_LN, EPI_QKV_SA>;
+    t.oproj = &launch_q8<NB, D, PRO_SA_MERGE, EPI_RESID>;
+    t.oproj_xq = &launch_q8<NB, D, PRO_SA_MERGE, EPI_RESID_XQ8>;
+    t.xq = &launch_q8<NB, D, PRO_LN, EPI_STORE>;
+    t.lt_in0 = &launch_q8<NB, D, PRO_LN, EPI_BIAS>;
+    t.lt_a = &launch_q8<NB, LTD, PRO_LTX_LN, EPI_LTQKV>;
+    t.lt_b = &launch_q8<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE>;
+    // the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots
+    // lt_pick_kernel, then o_net + residual
+    if constexpr (NB < 8) t.lt_bg = &launch_q8<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>;
+    else t.lt_bo = &launch_q8<NB, LTD, PRO_PLAIN, EPI_ADD_STORE>;
+    t.lt_e = &launch_q8<NB, LTD, PRO_PLAIN, EPI_BIAS>;
+    if constexpr (NB == 1) {
+        // LT in_proj of a caller-supplied normalised hidden (magpie_local_transformer_sample_all)
+        t.lt_inh = &launch_q8<1, D, PRO_PLAIN, EPI_BIAS>;
+        // the LT head with the LT FFN merge as its prologue: lt_slot_q8_kernel's LTQ_P partials,
+        t.lt_em = &launch_q8<1, LTD, PRO_LTQ_MERGE, EPI_BIAS>;
+        // and lt_ffn_kernel's LT_FFN_P interleaved ones (ltp_idx; the standalone LT sample of a Q8_0 file)
+        t.lt_emf = &launch_q8<1, LTD, PRO_LTFFN_MERGE, EPI_BIAS>;
     }
-
-MP_Q8_OPS(1)
-MP_Q8_OPS(2)
-MP_Q8_OPS(4)
-MP_Q8_OPS(8)
-MP_Q8_OPS(16)
-// LT in_proj of a caller-supplied normalised hidden (magpie_local_transformer_sample_all)
-hipError_t q8_lt_inh_1(const GemvP &p, hipStream_t s) { return launch_q8<1, D, PRO_PLAIN, EPI_BIAS>(p, s); }
-// o_net + residual after lt_pick_kernel (large batches)
-hipError_t q8_lt_bo_8(const GemvP &p, hipStream_t s) { return launch_q8<8, LTD, PRO_PLAIN, EPI_ADD_STORE>(p, s); }
-hipError_t q8_lt_bo_16(const GemvP &p, hipStream_t s) { return launch_q8<16, LTD, PRO_PLAIN, EPI_ADD_STORE>(p, s); }
-// the LT head at batch 1 with the LT FFN merge as its prologue (lt_ffn_kernel)
-hipError_t q8_lt_em_1(const GemvP &p, hipStream_t s) { return launch_q8<1, LTD, PRO_LTQ_MERGE, EPI_BIAS>(p, s); }
-// the same head after lt_ffn_kernel (the standalone LT sample of a Q8_0 file): its LT_FFN_P
-// partials are interleaved (ltp_idx)
-hipError_t q8_lt_emf_1(const GemvP &p, hipStream_t s) { return launch_q8<1, LTD, PRO_LTFFN_MERGE, EPI_BIAS>(p, s); }
+    return t;
+}
+const OpTable &q8_ops(int NB) {
+    static const OpTable t[5] = {make_q8_ops<1>(), make_q8_ops<2>(), make_q8_ops<4>(), make_q8_ops<8>(), make_q8_ops<16>()};
+    return t[op_nb_index(NB)];
+}
 
 }  // namespace mp

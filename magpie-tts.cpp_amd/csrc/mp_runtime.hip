@@ -27,148 +27,26 @@
 #include "mp_gguf.hpp"
 #include "mp_device.hpp"
 #include "mp_params.hpp"
-
-
-namespace mp {
-
-// ---- launchers (mp_decode.hip / mp_prefill.hip)
-using GemvFn = hipError_t (*)(const GemvP &, hipStream_t);
-#define MP_DECL_OPS(NB)                                                                                     \
-    hipError_t op_qkv_##NB(const GemvP &, hipStream_t);        \
-    hipError_t op_oproj_##NB(const GemvP &, hipStream_t); hipError_t op_ff1_##NB(const GemvP &, hipStream_t);            \
-    hipError_t op_ff1x_##NB(const GemvP &, hipStream_t); hipError_t op_oproj_xa_##NB(const GemvP &, hipStream_t);       \
-    hipError_t op_qkv_sa_##NB(const GemvP &, hipStream_t); hipError_t op_xq_##NB(const GemvP &, hipStream_t); \
-    hipError_t op_ff2_##NB(const GemvP &, hipStream_t); hipError_t op_lt_in0_##NB(const GemvP &, hipStream_t);           \
-    hipError_t op_lt_a_##NB(const GemvP &, hipStream_t); hipError_t op_lt_b_##NB(const GemvP &, hipStream_t);            \
-    hipError_t op_lt_bg_##NB(const GemvP &, hipStream_t);                                                              \
-    hipError_t op_lt_c_##NB(const GemvP &, hipStream_t); hipError_t op_lt_d_##NB(const GemvP &, hipStream_t);            \
-    hipError_t op_lt_e_##NB(const GemvP &, hipStream_t);
-MP_DECL_OPS(1)
-MP_DECL_OPS(2)
-MP_DECL_OPS(4)
-MP_DECL_OPS(8)
-hipError_t op_lt_in0_16(const GemvP &, hipStream_t);
-#define MP_DECL_B16(NB)                                                                                      \
-    hipError_t b16_qkv_##NB(const GemvP &, hipStream_t);      \
-    hipError_t b16_oproj_##NB(const GemvP &, hipStream_t); hipError_t b16_ff1_##NB(const GemvP &, hipStream_t);          \
-    hipError_t b16_ff2_##NB(const GemvP &, hipStream_t); hipError_t b16_lt_a_##NB(const GemvP &, hipStream_t);           \
-    hipError_t b16_lt_bg_##NB(const GemvP &, hipStream_t); hipError_t b16_lt_b_##NB(const GemvP &, hipStream_t);         \
-    hipError_t b16_lt_c_##NB(const GemvP &, hipStream_t); hipError_t b16_lt_d_##NB(const GemvP &, hipStream_t);          \
-    hipError_t b16_lt_e_##NB(const GemvP &, hipStream_t); hipError_t b16_oproj_xa_##NB(const GemvP &, hipStream_t); \
-    hipError_t b16_qkv_sa_##NB(const GemvP &, hipStream_t); hipError_t b16_ff1p_##NB(const GemvP &, hipStream_t); \
-    hipError_t b16_lt_es_##NB(const GemvP &, hipStream_t); hipError_t b16_lt_em_##NB(const GemvP &, hipStream_t);
-MP_DECL_B16(1)
-MP_DECL_B16(2)
-MP_DECL_B16(4)
-MP_DECL_B16(8)
-MP_DECL_B16(16)
-#define MP_DECL_F16(NB)                                                                                      \
-    hipError_t f16_qkv_##NB(const GemvP &, hipStream_t);      \
-    hipError_t f16_oproj_##NB(const GemvP &, hipStream_t); hipError_t f16_ff1_##NB(const GemvP &, hipStream_t);          \
-    hipError_t f16_ff2_##NB(const GemvP &, hipStream_t); hipError_t f16_lt_a_##NB(const GemvP &, hipStream_t);           \
-    hipError_t f16_lt_bg_##NB(const GemvP &, hipStream_t); hipError_t f16_lt_b_##NB(const GemvP &, hipStream_t);         \
-    hipError_t f16_lt_c_##NB(const GemvP &, hipStream_t); hipError_t f16_lt_d_##NB(const GemvP &, hipStream_t);          \
-    hipError_t f16_lt_e_##NB(const GemvP &, hipStream_t); hipError_t f16_lt_in0_##NB(const GemvP &, hipStream_t); \
-    hipError_t f16_oproj_xa_##NB(const GemvP &, hipStream_t); hipError_t f16_qkv_sa_##NB(const GemvP &, hipStream_t);
-MP_DECL_F16(1)
-MP_DECL_F16(2)
-MP_DECL_F16(4)
-MP_DECL_F16(8)
-MP_DECL_F16(16)
-hipError_t f16_lt_inh_1(const GemvP &, hipStream_t);
-hipError_t f16_lt_bo_8(const GemvP &, hipStream_t);
-hipError_t f16_lt_bo_16(const GemvP &, hipStream_t);
-hipError_t pack_b16(const float *, int, int, unsigned short *, hipStream_t, bool f16);
-#define MP_DECL_Q8(NB)                                                                                       \
-    hipError_t q8_qkv_##NB(const GemvP &, hipStream_t);        \
-    hipError_t q8_oproj_##NB(const GemvP &, hipStream_t); hipError_t q8_xq_##NB(const GemvP &, hipStream_t);             \
-    hipError_t q8_lt_in0_##NB(const GemvP &, hipStream_t);                                                             \
-    hipError_t q8_lt_a_##NB(const GemvP &, hipStream_t); hipError_t q8_lt_bg_##NB(const GemvP &, hipStream_t);           \
-    hipError_t q8_lt_b_##NB(const GemvP &, hipStream_t); hipError_t q8_lt_e_##NB(const GemvP &, hipStream_t);           \
-    hipError_t q8_qkv_sa_##NB(const GemvP &, hipStream_t); hipError_t q8_oproj_xq_##NB(const GemvP &, hipStream_t);
-MP_DECL_Q8(1)
-MP_DECL_Q8(2)
-MP_DECL_Q8(4)
-MP_DECL_Q8(8)
-MP_DECL_Q8(16)
-hipError_t q8_lt_bo_16(const GemvP &, hipStream_t);
-hipError_t op_ff1_16(const GemvP &, hipStream_t);
-hipError_t op_ff2_16(const GemvP &, hipStream_t);
-hipError_t op_xq_16(const GemvP &, hipStream_t);
-hipError_t op_lt_in0_16(const GemvP &, hipStream_t);
-hipError_t pack_q8(const signed char *, const unsigned short *, int, int, unsigned char *, unsigned short *, hipStream_t);
-hipError_t pack_q4(const signed char *, int, int, unsigned char *, hipStream_t);
-hipError_t q8_lt_inh_1(const GemvP &, hipStream_t);
-hipError_t q8_lt_em_1(const GemvP &, hipStream_t);
-hipError_t q8_lt_emf_1(const GemvP &, hipStream_t);
-hipError_t op_lt_pick(const GemvP &, int, hipStream_t);
-hipError_t op_embed(const EmbP &, int, hipStream_t);
-hipError_t op_lt_bo_8(const GemvP &, hipStream_t);
-hipError_t b16_lt_bo_8(const GemvP &, hipStream_t);
-hipError_t b16_lt_bo_16(const GemvP &, hipStream_t);
-hipError_t q8_lt_bo_8(const GemvP &, hipStream_t);
-hipError_t op_lt_em_1(const GemvP &, hipStream_t);
-int b16_oproj_ks();
-hipError_t op_lt_ffn(const LtFfnP &, int, hipStream_t);
-hipError_t op_lt_merge(const LtFfnP &, int, hipStream_t);
-hipError_t op_lt_ffn2(const LtFfn2P &, int, hipStream_t);
-hipError_t op_lt_slot(const LtFfn2P &, int, hipStream_t);
-hipError_t op_lt_front(const LtFrontP &, hipStream_t);
-hipError_t op_lt_slot_q8(const LtSlotQ8P &, int, hipStream_t);
-hipError_t op_lt_kvo(const GemvP &, int, hipStream_t);
-hipError_t op_sa_attn(const AttnP &, int, hipStream_t);
-hipError_t b16_oproj_xa_pm_16(const GemvP &, hipStream_t);
-hipError_t b16_oproj_xa_pm_8(const GemvP &, hipStream_t);
-hipError_t op_xa(const XaP &, int, hipStream_t);
-hipError_t op_xa_q8(const XaQ8P &, int, hipStream_t);
-hipError_t op_finalize(const FinP &, int, hipStream_t);
-
-}  // namespace mp
-
+#include "mp_ops.hpp"
 #include "mp_prefill_api.hpp"
 
 namespace mp {
 
-// ff1: LN(x2) prologue (x2 materialised: Q8 unfused XA); ff1x: the fused XA's split states merged into x2 first
-// oproj_xa: O-projection + the fused XA in one launch (EPI_RESID_XA)
-// qkv_sa: the QKV projection + the SA in one launch (EPI_QKV_SA)
-// xq: the direct XA's f32 q_net GEMV (f32 and bf16 modes); ff1: FFN up from a materialised x2
-struct OpTable { GemvFn qkv, oproj, ff1, ff1x, ff2, lt_in0, lt_a, lt_bg, lt_b, lt_c, lt_d, lt_e, oproj_xa,
-                 qkv_sa, xq, lt_es, lt_em; };
-#define MP_TABLE(NB) { op_qkv_##NB, op_oproj_##NB, op_ff1_##NB, op_ff1x_##NB, op_ff2_##NB, \
-                       op_lt_in0_##NB, op_lt_a_##NB, op_lt_bg_##NB, op_lt_b_##NB, op_lt_c_##NB, op_lt_d_##NB, op_lt_e_##NB, \
-                       op_oproj_xa_##NB, op_qkv_sa_##NB, op_xq_##NB }
-// 16 slots in the f32 family only for a Q8_0 file's F32 tensors: its FFN convs and LT in_proj
-static const OpTable kTables[5] = {MP_TABLE(1), MP_TABLE(2), MP_TABLE(4), MP_TABLE(8),
-                                   {nullptr, nullptr, op_ff1_16, nullptr, op_ff2_16, op_lt_in0_16, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, op_xq_16}};
-// bf16 weight mode: every projection on MFMA except the f32 LT in_proj
-#define MP_TABLE_B16(NB) { b16_qkv_##NB, b16_oproj_##NB, b16_ff1p_##NB, b16_ff1_##NB, b16_ff2_##NB, \
-                           op_lt_in0_##NB, b16_lt_a_##NB, b16_lt_bg_##NB, b16_lt_b_##NB, b16_lt_c_##NB,  \
-                           b16_lt_d_##NB, b16_lt_e_##NB, b16_oproj_xa_##NB, b16_qkv_sa_##NB, op_xq_##NB, b16_lt_es_##NB, b16_lt_em_##NB }
-static const OpTable kTablesB16[5] = {MP_TABLE_B16(1), MP_TABLE_B16(2), MP_TABLE_B16(4), MP_TABLE_B16(8),
-                                      MP_TABLE_B16(16)};
-// F16 weight mode (an F16 GGUF): the same MFMA family on f16, the LT in_proj included
-#define MP_TABLE_F16(NB) { f16_qkv_##NB, f16_oproj_##NB, nullptr, f16_ff1_##NB, f16_ff2_##NB, \
-                           f16_lt_in0_##NB, f16_lt_a_##NB, f16_lt_bg_##NB, f16_lt_b_##NB, f16_lt_c_##NB,  \
-                           f16_lt_d_##NB, f16_lt_e_##NB, f16_oproj_xa_##NB, f16_qkv_sa_##NB }
-static const OpTable kTablesF16[5] = {MP_TABLE_F16(1), MP_TABLE_F16(2), MP_TABLE_F16(4), MP_TABLE_F16(8),
-                                      MP_TABLE_F16(16)};
-// Q8_0 weight mode: the projections whose tensors are Q8_0 in the file (mp_decode_q8.hip)
-struct OpTableQ8 { GemvFn qkv, oproj, xq, lt_in0, lt_a, lt_bg, lt_b, lt_e, qkv_sa, oproj_xq; };
-#define MP_TABLE_Q8(NB) { q8_qkv_##NB, q8_oproj_##NB, q8_xq_##NB, q8_lt_in0_##NB, \
-                          q8_lt_a_##NB, q8_lt_bg_##NB, q8_lt_b_##NB, q8_lt_e_##NB, q8_qkv_sa_##NB, q8_oproj_xq_##NB }
-static const OpTableQ8 kTablesQ8[5] = {MP_TABLE_Q8(1), MP_TABLE_Q8(2), MP_TABLE_Q8(4), MP_TABLE_Q8(8),
-                                        MP_TABLE_Q8(16)};
-static int nb_index(int NB) { return NB == 1 ? 0 : NB == 2 ? 1 : NB == 4 ? 2 : NB == 8 ? 3 : 4; }
 // the 16-bit MFMA family serves the bf16 and F16 weight modes
 static bool h16_mode(int weight_mode) { return weight_mode == MP_WEIGHTS_BF16 || weight_mode == MP_WEIGHTS_F16; }
-static const OpTable &table_for(int NB, int weight_mode) {
-    return weight_mode == MP_WEIGHTS_F16 ? kTablesF16[nb_index(NB)]
-           : weight_mode == MP_WEIGHTS_BF16 ? kTablesB16[nb_index(NB)]
-                                            : kTables[nb_index(NB)];
+// The weight mode's op table at NB slots (mp_ops.hpp). f32 and Q8_0 modes: the f32 family
+// (a Q8_0 file's quantised tensors take q8_ops(NB) instead, tensor by tensor). bf16 mode:
+// every projection on MFMA except the f32 LT in_proj and the direct XA's f32 q_net. F16
+// mode (an F16 GGUF): the same MFMA family on f16, the LT in_proj included.
+static OpTable table_for(int NB, int weight_mode) {
+    if (!h16_mode(weight_mode)) return f32_ops(NB);
+    OpTable t = b16_ops(NB, weight_mode == MP_WEIGHTS_F16);
+    if (weight_mode == MP_WEIGHTS_BF16) {
+        const OpTable &f = f32_ops(NB);
+        t.lt_in0 = f.lt_in0; t.lt_inh = f.lt_inh; t.xq = f.xq;
+    }
+    return t;
 }
-static const OpTableQ8 &table_q8(int NB) { return kTablesQ8[nb_index(NB)]; }
 
 // A Q8_0 tensor (weight mode MP_WEIGHTS_Q8): as stored, int8 [N][K] + fp16 scales
 // [N][K/32] (the preamble GEMMs), and for the decode projections also in int8 MFMA
@@ -236,7 +114,7 @@ struct Model {
     size_t arena_bytes = 0;
 };
 
-enum OpKind { K_GEMV = 0, K_ATTN = 1, K_FIN = 2, K_XA = 3, K_XAQ8 = 5, K_LTFFN = 6, K_LTMERGE = 7, K_LTPICK = 8, K_EMBED = 9,
+enum OpKind { K_GEMV = 0, K_ATTN = 1, K_FIN = 2, K_XA = 3, K_XAQ8 = 5, K_LTFFN = 6, K_LTMERGE = 7, K_LTPICK = 8,
               K_LTFFN2 = 10, K_LTKVO = 11, K_LTSLOT = 12, K_LTFRONT = 13, K_LTSLOTQ8 = 14 };
 // the f32 batch-1 LT front's granules (one zeroed buffer, LtFrontP::gh): in_proj output, vo_0
 constexpr size_t LTFG_TOTAL = 2 * 256;
@@ -259,7 +137,6 @@ struct OpRec {
     LtFfn2P l2;
     LtFrontP lf3;
     LtSlotQ8P lq8;
-    EmbP e;
     int B;
     double bytes;
     bool add_sa = false;  // the launch also runs the SA (EPI_QKV_SA): its live-cache bytes are added
@@ -280,7 +157,6 @@ struct LtIo {
     SmpCfg *cfg;
     int sampling, ignore_eos, emit_eos, max_steps, lt_only;
 };
-hipError_t op_lt_inh_1(const GemvP &, hipStream_t);
 
 }  // namespace mp
 
@@ -1004,8 +880,17 @@ int split_merge8() { return mp::env_int("MAGPIE_MERGE8", 3); }
 // the head's prologue. Every setting computes the same bits (tests/test_q8_fused_gpu.py).
 int ltq8_mode() { return mp::env_int("MAGPIE_LTQ8", 2); }
 
-// a quantised tensor's decode bytes per weight: Q8_0 34/32, Q4_0 nibble fragments 18/32
-double Fq(const mp::QW &w) { return w.nib ? 18.0 / 32.0 : 34.0 / 32.0; }
+// a tensor's decode bytes per weight: quantised in the file Q8_0 34/32, Q4_0 nibble
+// fragments 18/32; else F, its width in the weight mode
+double weight_bytes(const mp::QW &q, double F) { return !q ? F : q.nib ? 18.0 / 32.0 : 34.0 / 32.0; }
+// a GEMV's weight operands: f32 rows, 16-bit fragments (bf16 / F16 modes), and the Q8_0 /
+// Q4_0 fragments of a tensor quantised in the file (the kernel family reads its own)
+void set_weights(mp::GemvP &g, const float *W, const unsigned short *Wb, const mp::QW &q) {
+    g.W = W; g.Wb = Wb; g.Wq = q.pq; g.Wd = q.pd; g.q4 = q.nib;
+}
+// the hand-off state of a launch whose workgroups wait on one another: the decode
+// iteration counter (the granules' tags) and the error bits, both behind ndone
+template <class P> void set_handoff(P &p, int *ndone) { p.iter = ndone + 1; p.hx_err = ndone + 2; }
 
 // a zeroed GemvP with the model's constants and its slots' step and sampling state
 mp::GemvP gemv_base(const mp::Model &m, int NB, int *step, const mp::Sampling &smp, bool ignore_eos) {
@@ -1053,8 +938,10 @@ struct Emit {
 int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &out, bool q8dump = false) {
     const mp::Model &m = dev->m;
     const bool b16 = mp::h16_mode(m.weight_mode);
-    const mp::OpTable &tb = mp::table_for(NB, m.weight_mode);
-    const mp::OpTableQ8 &tq = mp::table_q8(NB);
+    const mp::OpTable tb = mp::table_for(NB, m.weight_mode);
+    const mp::OpTable &tq = mp::q8_ops(NB);
+    // the family of a tensor: the Q8_0 one where the file holds it quantised
+    auto fam = [&](const mp::QW &q) -> const mp::OpTable & { return q ? tq : tb; };
     const double F = b16 ? 2.0 : 4.0, A = 4.0, act = (double)NB;
     const mp::Sampling smp{io.sampling, io.cfg, io.argeos, io.amax};
     const Emit e{dev, out, NB, q8dump, mp::LtDumpP{io.logits, io.ltX, io.ltY, io.lty2, io.ltq, io.codes_cur}};
@@ -1099,27 +986,27 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
         }
         if (merged) { g.part = io.ltp; g.addsrc = io.ltY; }
         return e.gemv("lt_e", fn, g,
-                      (m.lt_out8 ? Fq(m.lt_out8) : F) * (2024.0 * 256) + A * 2024 + A * act * (src_elems + 2024));
+                      weight_bytes(m.lt_out8, F) * (2024.0 * 256) + A * 2024 + A * act * (src_elems + 2024));
     };
     // f32 mode at batch 1: final LN + in_proj + position 0 + codebook 0's FFN step in one
     // launch (lt_front_kernel: the same rows, the same arithmetic; 2 in-launch granule edges)
     const bool front = f32_lt_mode(m) && NB == 1 && !io.lt_only && io.ltfg && io.iter;
     if (!front) {
         mp::GemvP g = base(0);
-        g.W = m.lt_in_w; g.N = 256; g.bias = m.lt_in_b; g.out = io.lt_s; g.out_ld = 9 * 256;
-        g.Wq = m.lt_in8.pq; g.Wd = m.lt_in8.pd; g.q4 = m.lt_in8.nib; g.Wb = m.pk_lt_in;  // pk_lt_in: F16 mode only
-        const double Fi = m.lt_in8 ? Fq(m.lt_in8) : m.pk_lt_in ? 2.0 : A;
+        set_weights(g, m.lt_in_w, m.pk_lt_in, m.lt_in8);  // pk_lt_in: F16 mode only
+        g.N = 256; g.bias = m.lt_in_b; g.out = io.lt_s; g.out_ld = 9 * 256;
+        const double Fi = weight_bytes(m.lt_in8, m.pk_lt_in ? 2.0 : A);
         if (io.lt_only) {
             // in_proj of the caller's (already normalised) hidden (1161-1163)
             g.src = io.hidden; g.src_ld = 768;
-            if (int rc = e.gemv("lt_inh", m.lt_in8 ? mp::q8_lt_inh_1 : m.pk_lt_in ? mp::f16_lt_inh_1 : mp::op_lt_inh_1, g,
+            if (int rc = e.gemv("lt_inh", fam(m.lt_in8).lt_inh, g,
                                 Fi * 256.0 * 768 + A * 256 + A * (768 + 256)))
                 return rc;
         } else {
             // final LN -> hidden (4394) fused into LT in_proj (1162-1163)
             g.lnw = m.dec_norm_out; g.src = io.x; g.src_ld = 768; g.hidden_out = io.hidden;
             if (io.trace) { g.trace = io.trace; g.trace_steps = io.trace_steps; g.step = io.step; }
-            if (int rc = e.gemv("lt_in0", m.lt_in8 ? tq.lt_in0 : tb.lt_in0, g,
+            if (int rc = e.gemv("lt_in0", fam(m.lt_in8).lt_in0, g,
                                 Fi * 256.0 * 768 + A * 256 + A * act * ((768 + 768 + 256))))
                 return rc;
         }
@@ -1141,7 +1028,7 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
             e.add("lt_slot", mp::K_LTSLOT, &mp::OpRec::l2, l2,
                   F * (1024.0 * 256 * 2) + A * act * (cb ? 2024 + 4 * 256 + 2 * 256 * cb : 512) +
                       A * act * (mp::LTS_P * 256 + 256));
-            if (int rc = head(cb, head_merge ? tb.lt_em : tb.lt_es, head_merge, head_merge ? mp::LTS_P * 256 : 256))
+            if (int rc = head(cb, head_merge ? tb.lt_em : tb.lt_e, head_merge, head_merge ? mp::LTS_P * 256 : 256))
                 return rc;
         }
     } else if (f32_lt_mode(m)) {
@@ -1166,17 +1053,17 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
                           A * act * (mp::LT_FFN_P * 256 + 256));
             }
             merge(l2.f);
-            if (int rc = head(cb, NB == 1 ? mp::op_lt_em_1 : tb.lt_e, NB == 1, 256)) return rc;
+            if (int rc = head(cb, NB == 1 ? tb.lt_em : tb.lt_e, NB == 1, 256)) return rc;
         }
     } else if (m.weight_mode == MP_WEIGHTS_Q8 && m.lt_o8 && m.lt_out8 && m.lt_ff2q && !io.lt_only && io.ltyg) {
         // Q8_0 mode: position 0's q|k|v (the Q8_0 GEMV), then per codebook the LT step as
         // LTQ_P workgroups per slot (lt_slot_q8_kernel: pick, attention, Q8_0 o_net, F32
         // FFN, partial sums merged through granules) and the Q8_0 head on its output
         mp::GemvP g = base(0);
-        g.W = m.lt_qkv; g.N = 768; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX;
-        g.Wq = m.lt_qkv8.pq; g.Wd = m.lt_qkv8.pd; g.q4 = m.lt_qkv8.nib;
+        set_weights(g, m.lt_qkv, nullptr, m.lt_qkv8);
+        g.N = 768; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX;
         g.lnw = m.lt_norm_self; g.lq = io.ltq; g.lk = io.ltk; g.lv = io.ltv;
-        if (int rc = e.gemv("lt_a", tq.lt_a, g, Fq(m.lt_qkv8) * (768.0 * 256) + A * act * (256 * 3 + 768 + 256)))
+        if (int rc = e.gemv("lt_a", tq.lt_a, g, weight_bytes(m.lt_qkv8, F) * (768.0 * 256) + A * act * (256 * 3 + 768 + 256)))
             return rc;
         const int lm = ltq8_mode();
         for (int cb = 0; cb < 8; ++cb) {
@@ -1194,7 +1081,7 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
                   (34.0 / 32.0) * (256.0 * 256) + A * (1024.0 * 256 * 2) +
                       A * act * (cb ? 2024 + 4 * 256 + 2 * 256 * cb : 512) + A * act * (mp::LTQ_P * 256 + 512));
             // (sp.part: the FFN merge is the head's prologue)
-            if (int rc = head(cb, sp.part ? mp::q8_lt_em_1 : tq.lt_e, sp.part != nullptr, 256)) return rc;
+            if (int rc = head(cb, sp.part ? tq.lt_em : tq.lt_e, sp.part != nullptr, 256)) return rc;
         }
     } else
     for (int cb = 0; cb < 8; ++cb) {
@@ -1202,18 +1089,17 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
         if (cb == 0) {
             // position 0 (the hidden's in_proj): LN + q|k|v GEMV, then attention + o_net
             g = base(0);
-            g.W = m.lt_qkv; g.Wb = m.pk_lt_qkv; g.N = 768; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX;
-            g.Wq = m.lt_qkv8.pq; g.Wd = m.lt_qkv8.pd; g.q4 = m.lt_qkv8.nib;
+            set_weights(g, m.lt_qkv, m.pk_lt_qkv, m.lt_qkv8);
+            g.N = 768; g.lt_s = io.lt_s; g.lt_pos = m.lt_pos; g.ltX = io.ltX;
             g.lnw = m.lt_norm_self; g.lq = io.ltq; g.lk = io.ltk; g.lv = io.ltv;
-            if (int rc = e.gemv("lt_a", m.lt_qkv8 ? tq.lt_a : tb.lt_a, g,
-                                (m.lt_qkv8 ? Fq(m.lt_qkv8) : F) * (768.0 * 256) + A * act * (256 * 3 + 768 + 256)))
+            if (int rc = e.gemv("lt_a", fam(m.lt_qkv8).lt_a, g,
+                                weight_bytes(m.lt_qkv8, F) * (768.0 * 256) + A * act * (256 * 3 + 768 + 256)))
                 return rc;
             g = base(0);
-            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.ltq = io.ltq; g.ltk = io.ltk; g.ltv = io.ltv; g.out = io.ltY;
-            g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
+            set_weights(g, m.lt_o, m.pk_lt_o, m.lt_o8);
+            g.N = 256; g.ltq = io.ltq; g.ltk = io.ltk; g.ltv = io.ltv; g.out = io.ltY;
             g.out_ld = 256; g.addsrc = io.ltX;
-            if (int rc = e.gemv("lt_b", m.lt_o8 ? tq.lt_b : tb.lt_b, g,
-                                (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) + A * act * (256 * 5)))
+            if (int rc = e.gemv("lt_b", fam(m.lt_o8).lt_b, g, weight_bytes(m.lt_o8, F) * (256.0 * 256) + A * act * (256 * 5)))
                 return rc;
         } else if (NB >= 8) {
             // large batches: the per-slot pick + gathers + attention as one wave per slot
@@ -1224,29 +1110,25 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
             g.out = io.ltq;
             e.add("lt_pick", mp::K_LTPICK, &mp::OpRec::g, g, A * act * (2024 + 4 * 256 + 2 * 256 * cb + 4 * 256));
             g = base(cb);
-            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.src = io.ltq; g.src_ld = 256; g.out = io.ltY; g.out_ld = 256;
-            g.addsrc = io.ltX; g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
-            const bool f16 = m.weight_mode == MP_WEIGHTS_F16;
-            const mp::GemvFn bo = m.lt_o8 ? (NB == 16 ? mp::q8_lt_bo_16 : mp::q8_lt_bo_8)
-                                  : f16   ? (NB == 16 ? mp::f16_lt_bo_16 : mp::f16_lt_bo_8)
-                                  : b16   ? (NB == 16 ? mp::b16_lt_bo_16 : mp::b16_lt_bo_8)
-                                          : mp::op_lt_bo_8;
-            if (int rc = e.gemv("lt_bo", bo, g, (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) + A * act * (256 * 3))) return rc;
+            set_weights(g, m.lt_o, m.pk_lt_o, m.lt_o8);
+            g.N = 256; g.src = io.ltq; g.src_ld = 256; g.out = io.ltY; g.out_ld = 256; g.addsrc = io.ltX;
+            if (int rc = e.gemv("lt_bo", fam(m.lt_o8).lt_bo, g, weight_bytes(m.lt_o8, F) * (256.0 * 256) + A * act * (256 * 3)))
+                return rc;
         } else {
             // position cb: codebook cb-1's pick, its q|k|v row gathered from the load-time
             // table (no q|k|v GEMV), attention + o_net + residual, one launch
             g = base(cb);
-            g.W = m.lt_o; g.Wb = m.pk_lt_o; g.N = 256; g.out = io.ltY; g.out_ld = 256;
-            g.Wq = m.lt_o8.pq; g.Wd = m.lt_o8.pd; g.q4 = m.lt_o8.nib;
+            set_weights(g, m.lt_o, m.pk_lt_o, m.lt_o8);
+            g.N = 256; g.out = io.ltY; g.out_ld = 256;
             g.logits = io.logits; g.codes_cur = io.codes_cur; g.qkvtab = m.lt_qkvtab; g.ptab = m.lt_ptab;
             g.lt_pos = m.lt_pos; g.ltk = io.ltk; g.ltv = io.ltv; g.lk = io.ltk; g.lv = io.ltv;
-            if (int rc = e.gemv("lt_bg", m.lt_o8 ? tq.lt_bg : tb.lt_bg, g,
-                                (m.lt_o8 ? Fq(m.lt_o8) : F) * (256.0 * 256) +
+            if (int rc = e.gemv("lt_bg", fam(m.lt_o8).lt_bg, g,
+                                weight_bytes(m.lt_o8, F) * (256.0 * 256) +
                                     A * act * (2024 + 3 * 256 + 2 * 256 * cb + 2 * 256 + 256)))
                 return rc;
         }
         // FFN up + GELU + FFN down: one launch of partial sums (f32 FFN weights), merged by
-        // the head's prologue at batch 1 or by a one-workgroup merge; bf16 mode: two GEMVs
+        // the head's prologue at batch 1 or by a one-workgroup merge; F16 mode: two GEMVs
         const bool ffn1 = !b16;
         if (ffn1) {
             const mp::LtFfnP lf{io.ltY, m.lt_norm_ff, m.lt_ff1, m.lt_ff2s, m.eps, io.ltp, io.lty2};
@@ -1264,7 +1146,7 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
         }
         // (batch 1: the FFN merge, lt_ffn_kernel's interleaved partials, is the head's prologue)
         const bool em = ffn1 && NB == 1;
-        if (int rc = head(cb, em ? (m.lt_out8 ? mp::q8_lt_emf_1 : mp::op_lt_em_1) : (m.lt_out8 ? tq.lt_e : tb.lt_e), em, 256))
+        if (int rc = head(cb, em ? fam(m.lt_out8).lt_emf : fam(m.lt_out8).lt_e, em, 256))
             return rc;
     }
     mp::FinP f{io.logits, io.codes_cur, io.codes_prev, io.codes_out, io.step, io.pos, io.done, io.nframes, io.ndone,
@@ -1281,8 +1163,10 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     const mp::Model &m = dev->m;
     const int NB = dev->NB, L = m.dec_layers;
     const bool b16 = mp::h16_mode(m.weight_mode);  // 16-bit MFMA family (bf16 or F16 weights)
-    const mp::OpTable &tb = mp::table_for(NB, m.weight_mode);
-    const mp::OpTableQ8 &tq = mp::table_q8(NB);
+    const mp::OpTable tb = mp::table_for(NB, m.weight_mode);
+    const mp::OpTable &tq = mp::q8_ops(NB);
+    // the family of a tensor: the Q8_0 one where the file holds it quantised
+    auto fam = [&](const mp::QW &q) -> const mp::OpTable & { return q ? tq : tb; };
     // algorithmic bytes: weights at their stored width (Q8_0: 34 B per 32), activations f32
     const double F = b16 ? 2.0 : 4.0, A = 4.0, act = (double)NB;
     const bool sampling = dev->params.temperature >= 0.01f;
@@ -1312,32 +1196,32 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
         const mp::DecLayerW &W = m.dec[l];
         mp::GemvP g = base(l);
         // LN + QKV (+ frame embedding on layer 0) + KV append   (3415-3442)
-        g.W = W.qkv; g.Wb = b16 ? m.pk_qkv[l] : nullptr; g.N = 2304; g.lnw = W.norm_self; g.src = dev->x; g.src_ld = 768; g.out = dev->q;
-        g.Wq = W.qkv8.pq; g.Wd = W.qkv8.pd; g.q4 = W.qkv8.nib;
+        set_weights(g, W.qkv, b16 ? m.pk_qkv[l] : nullptr, W.qkv8);
+        g.N = 2304; g.lnw = W.norm_self; g.src = dev->x; g.src_ld = 768; g.out = dev->q;
         g.kc = dev->kc; g.vc = dev->vc; g.kv16 = dev->kv16;
         // the frame embedding (2746-2787) is in x already: written by the previous
         // iteration's finalize (lt_finalize_kernel), for the first frame by reset_decode_state
         // self-attention over the cache, split over keys (3457-3476); the f32 family runs
         // it in the QKV launch on a hand-off of q|k|v (EPI_QKV_SA), the others separately
         mp::AttnP a{dev->q, dev->kc, dev->vc, l, L, dev->max_seq, dev->pos, dev->kv16, dev->sa_part};
-        if (merge_sa) { a.merged = dev->sa_out; a.gh = dev->sagh; a.iter = dev->ndone + 1; a.hx_err = dev->ndone + 2; }
-        const bool sa_in_qkv = (W.qkv8 ? q8_fuse && tq.qkv_sa : tb.qkv_sa != nullptr) && sa16;
-        const double qkv_bytes = (W.qkv8 ? Fq(W.qkv8) : F) * (2304.0 * 768) + A * act * ((768 + 2304));
+        if (merge_sa) { a.merged = dev->sa_out; a.gh = dev->sagh; set_handoff(a, dev->ndone); }
+        const bool sa_in_qkv = fam(W.qkv8).qkv_sa && (!W.qkv8 || q8_fuse) && sa16;
+        const double qkv_bytes = weight_bytes(W.qkv8, F) * (2304.0 * 768) + A * act * ((768 + 2304));
         if (sa_in_qkv) {
-            g.sa = a; g.qh = dev->qh; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
-            if (int rc = e.gemv("qkv_sa", W.qkv8 ? tq.qkv_sa : tb.qkv_sa, g, qkv_bytes)) return rc;
+            g.sa = a; g.qh = dev->qh; set_handoff(g, dev->ndone);
+            if (int rc = e.gemv("qkv_sa", fam(W.qkv8).qkv_sa, g, qkv_bytes)) return rc;
             out.back().add_sa = true;
         } else {
-            if (int rc = e.gemv("qkv", W.qkv8 ? tq.qkv : tb.qkv, g, qkv_bytes)) return rc;
+            if (int rc = e.gemv("qkv", fam(W.qkv8).qkv, g, qkv_bytes)) return rc;
             e.add("sa_attn", mp::K_ATTN, &mp::OpRec::a, a, -1);  // bytes: the live cache length's, computed at timing time
         }
         // O-proj + residual (3479, 3509)
         g = base(l);
-        g.W = W.o; g.Wb = b16 ? m.pk_o[l] : nullptr; g.N = 768; g.resid = dev->x; g.part = dev->sa_part;
-        g.Wq = W.o8.pq; g.Wd = W.o8.pd; g.q4 = W.o8.nib;
+        set_weights(g, W.o, b16 ? m.pk_o[l] : nullptr, W.o8);
+        g.N = 768; g.resid = dev->x; g.part = dev->sa_part;
         // split-K partial tiles (MP_OPROJ_KS > 1 builds only): the plain O-projection then
         // carries a hand-off; with one slice it has none and stays timeable standalone
-        if (b16 && mp::b16_oproj_ks() > 1) { g.kgh = dev->kgh; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2; }
+        if (b16 && mp::b16_oproj_ks() > 1) { g.kgh = dev->kgh; set_handoff(g, dev->ndone); }
         mp::XaP xp{dev->x, dev->xa_part, W.norm_xq, m.eps, dev->kp, dev->vp, dev->T, dev->Tmax, l, L};
         xp.q_f16 = m.weight_mode == MP_WEIGHTS_F16;
         const double xa_bytes = A * act * (768.0 + 2.0 * 768 * dev->Tmax + mp::XA_SPLITS * mp::XA_PART);
@@ -1357,9 +1241,9 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
             xq.layer = l; xq.nlayers = L; xq.wo = W.xo8.q; xq.wod = W.xo8.d;
             xq.wq = W.xq8.q; xq.wqd = W.xq8.d; xq.lnw = W.norm_xq; xq.eps = m.eps; xq.qg = dev->xqh;
             xq.qin = NB <= mp::XQ8_QIN_NB;  // small batches: q in the attention workgroups (one hand-off)
-            g.xq8 = xq; g.xh = dev->xh; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
+            g.xq8 = xq; g.xh = dev->xh; set_handoff(g, dev->ndone);
             if (int rc = e.gemv("oproj_xa_q8", tq.oproj_xq, g,
-                                Fq(W.o8) * (768.0 * 768) + A * act * (768 * 3) + (34.0 / 32.0) * (2.0 * 128 * 768) +
+                                weight_bytes(W.o8, F) * (768.0 * 768) + A * act * (768 * 3) + (34.0 / 32.0) * (2.0 * 128 * 768) +
                                     A * act * (768 + 2.0 * 128 * dev->Tmax)))
                 return rc;
         } else if (xa_in_oproj) {
@@ -1367,13 +1251,13 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
             mp::GemvFn fn = tb.oproj_xa;
             if (merge_sa) {  // the SA output merged by its split workgroups: plain rows
                 g.part = nullptr; g.src = dev->sa_out; g.src_ld = 768;
-                fn = NB == 16 ? mp::b16_oproj_xa_pm_16 : mp::b16_oproj_xa_pm_8;
+                fn = tb.oproj_xa_pm;
             }
             if (merge_xa) { xp.x2 = dev->x2; xp.gh = dev->xagh; }  // x2 merged by the XA workgroups
-            g.xa = xp; g.xh = dev->xh; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
+            g.xa = xp; g.xh = dev->xh; set_handoff(g, dev->ndone);
             if (int rc = e.gemv("oproj_xa", fn, g, F * (768.0 * 768) + A * act * (768 * 3) + xa_bytes)) return rc;
-        } else if (int rc = e.gemv("oproj", W.o8 ? tq.oproj : tb.oproj, g,
-                                   (W.o8 ? Fq(W.o8) : F) * (768.0 * 768) + A * act * (768 * 3))) {
+        } else if (int rc = e.gemv("oproj", fam(W.o8).oproj, g,
+                                   weight_bytes(W.o8, F) * (768.0 * 768) + A * act * (768 * 3))) {
             return rc;
         }
         if (xa_dir && !xq8_in_oproj) {
@@ -1381,10 +1265,10 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
             // x2 = x + o_net attn(q, K, V) (xa_q8_kernel / xa_f32_kernel); Q8_0 q_net / o_net
             // quantise their activations, else f32 (the bf16 mode keeps XA f32)
             g = base(l);
-            g.W = W.xq; g.Wq = W.xq8.pq; g.Wd = W.xq8.pd; g.q4 = W.xq8.nib; g.N = 128; g.lnw = W.norm_xq; g.src = dev->x; g.src_ld = 768;
-            g.out = dev->xqb; g.out_ld = 128;
-            const double Fx = W.xq8 ? Fq(W.xq8) : A;
-            if (int rc = e.gemv("xq", W.xq8 ? tq.xq : tb.xq, g, Fx * (128.0 * 768) + A * act * (768 + 128))) return rc;
+            set_weights(g, W.xq, nullptr, W.xq8);  // (f32 in the 16-bit modes)
+            g.N = 128; g.lnw = W.norm_xq; g.src = dev->x; g.src_ld = 768; g.out = dev->xqb; g.out_ld = 128;
+            const double Fx = weight_bytes(W.xq8, A);
+            if (int rc = e.gemv("xq", fam(W.xq8).xq, g, Fx * (128.0 * 768) + A * act * (768 + 128))) return rc;
             mp::XaQ8P xq{};
             xq.x = dev->x; xq.x2 = dev->x2; xq.q = dev->xqb; xq.xak = dev->xak; xq.xav = dev->xav; xq.T = dev->T;
             xq.Tmax = dev->Tmax; xq.layer = l; xq.nlayers = L;
@@ -1415,7 +1299,7 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
         if (b16) {
             g.src = nullptr; g.src_b16 = dev->h_b16;
             // split-K partial tiles (the FFN-down half of kgh: each op its own granules)
-            g.kgh = dev->kgh + (size_t)(768 / 16) * mp::KGH_MAX_KS * 256; g.iter = dev->ndone + 1; g.hx_err = dev->ndone + 2;
+            g.kgh = dev->kgh + (size_t)(768 / 16) * mp::KGH_MAX_KS * 256; set_handoff(g, dev->ndone);
         }
         if (int rc = e.gemv("ff2", tb.ff2, g, F * (768.0 * 3072) + A * act * ((3072 + 2 * 768)))) return rc;
     }
@@ -1423,7 +1307,7 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     io.x = dev->x; io.hidden = dev->hidden; io.trace = dev->trace; io.trace_steps = dev->max_steps + 1;
     io.lt_s = dev->lt_s; io.ltX = dev->ltX; io.ltY = dev->ltY; io.lty2 = dev->lty2; io.ltq = dev->ltq;
     io.ltk = dev->ltk; io.ltv = dev->ltv; io.ltf = dev->ltf; io.logits = dev->logits; io.ltp = dev->ltp;
-    io.ltgh = dev->ltgh; io.ltfg = dev->ltfg; io.ltyg = dev->ltyg; io.iter = dev->ndone + 1; io.hx_err = dev->ndone + 2;
+    io.ltgh = dev->ltgh; io.ltfg = dev->ltfg; io.ltyg = dev->ltyg; set_handoff(io, dev->ndone);
     io.codes_cur = dev->codes_cur; io.codes_prev = dev->codes_prev; io.codes_out = dev->codes_out; io.step = dev->step;
     io.pos = dev->pos; io.done = dev->done; io.nframes = dev->nframes; io.ndone = dev->ndone; io.argeos = dev->argeos;
     io.amax = dev->amax; io.cfg = dev->smpcfg;
@@ -1447,7 +1331,6 @@ hipError_t launch_rec(const mp::OpRec &r, hipStream_t s) {
     case mp::K_LTFRONT: return mp::op_lt_front(r.lf3, s);
     case mp::K_LTSLOTQ8: return mp::op_lt_slot_q8(r.lq8, r.B, s);
     case mp::K_LTKVO: return mp::op_lt_kvo(r.g, r.B, s);
-    case mp::K_EMBED: return mp::op_embed(r.e, r.B, s);
     case mp::K_FIN: return mp::op_finalize(r.f, r.B, s);
     }
     return hipErrorInvalidValue;

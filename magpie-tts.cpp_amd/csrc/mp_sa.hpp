@@ -238,6 +238,45 @@ inline bool qkv_sa_args_ok(const GemvP &p) {
            p.sa.max_seq == p.max_seq && p.sa.max_seq >= 1 && p.sa.max_seq <= NCH_MAX * SA_CHUNK;
 }
 
+// Host-side check that every pointer the (PRO, EPI) pair dereferences is set:
+// a mismatch between an op's compile-time epilogue and its arguments must fail
+// at launch, not fault on the device. One check for the three GEMV families (a branch for a
+// PRO / EPI a family never instantiates costs nothing); each launch_*<> adds its own
+// weight pointer, N > 0 and split-K tests.
+template <int PRO, int EPI>
+inline bool gemv_args_ok(const GemvP &p) {
+    bool ok = true;
+    if constexpr (PRO == PRO_PLAIN) ok &= p.src != nullptr;
+    if constexpr (PRO == PRO_PLAIN_B16) ok &= p.src_b16 != nullptr;
+    if constexpr (PRO == PRO_SA_MERGE) ok &= p.part != nullptr;
+    if constexpr (PRO == PRO_LTFFN_MERGE || PRO == PRO_LTS_MERGE || PRO == PRO_LTQ_MERGE) ok &= p.part && p.addsrc;
+    if constexpr (PRO == PRO_XA_LN) ok &= p.part && p.src && p.lnw && p.xres;
+    if constexpr (PRO == PRO_LN) ok &= p.src && p.lnw;
+    if constexpr (PRO == PRO_LTX_LN) ok &= p.lt_s && p.lt_pos && p.ltX && p.lnw;
+    if constexpr (PRO == PRO_LT_ATTN) ok &= p.ltq && p.ltk && p.ltv;
+    if constexpr (PRO == PRO_LTARG_ATTN)
+        ok &= p.logits && p.codes_cur && p.qkvtab && p.lk && p.lv && p.ltk && p.ltv && p.step && p.smp.cfg && p.smp.argeos;
+    if constexpr (EPI == EPI_STORE || EPI == EPI_GELU) ok &= p.out != nullptr;
+    if constexpr (EPI == EPI_GELU_B16 || EPI == EPI_GELU_F16) ok &= p.out_b16 != nullptr;
+    if constexpr (EPI == EPI_BIAS) ok &= p.out && p.bias;
+    if constexpr (EPI == EPI_RESID) ok &= p.resid != nullptr;
+    if constexpr (EPI == EPI_ADD_STORE) ok &= p.out && p.addsrc;
+    if constexpr (EPI == EPI_LTX_ADD) ok &= p.out && p.ptab && p.lt_pos && p.cb >= 1;
+    if constexpr (EPI == EPI_QKV || EPI == EPI_QKV_SA) ok &= p.out && p.kc && p.vc && p.pos;
+    if constexpr (EPI == EPI_QKV_SA) ok &= qkv_sa_args_ok(p);
+    if constexpr (EPI == EPI_LTQKV) ok &= p.lq && p.lk && p.lv;
+    if constexpr (EPI == EPI_LTKVO) ok &= p.lk && p.lv && p.N == 2 * LTD;
+    if constexpr (EPI == EPI_RESID_XA)
+        ok &= p.resid && p.xh && p.iter && p.hx_err && p.N == D && p.xa.part && p.xa.lnw && p.xa.kp && p.xa.vp &&
+              p.xa.T && p.xa.Tmax >= 1 && p.xa.Tmax <= TMAX_LIMIT;
+    if constexpr (EPI == EPI_RESID_XQ8) {
+        const XaQ8P &x = p.xq8;
+        ok &= p.resid && p.xh && p.iter && p.hx_err && p.N == D && x.qg && x.wq && x.wqd && x.lnw && x.x2 && x.wo &&
+              x.wod && x.xak && x.xav && x.T && x.Tmax >= 1 && x.Tmax <= TMAX_LIMIT && x.layer == p.layer;
+    }
+    return ok;
+}
+
 // the launch's SA workgroups (blockIdx.x >= nrow_blocks): (head, split, slot) of
 // k = blockIdx.x - nrow_blocks, head fastest
 __device__ __forceinline__ void sa_tail(const GemvP &p, unsigned long long t_start) {

@@ -35,6 +35,8 @@ cache = os.environ.get("MAGPIE_CACHE", "/tmp/magpie_amd_cache")
 os.makedirs(cache, exist_ok=True)
 if weights == "q8":  # the Q8 mode needs a file with Q8_0 tensors
     path = ma.synth_gguf(os.path.join(cache, "magpie_357m_q8_k32.gguf"), dtype="q8_0", lt_head_scale=ma.DECISIVE)
+elif weights == "f16":  # and the F16 mode one with F16 projections
+    path = ma.synth_gguf(os.path.join(cache, "magpie_357m_f16_k32.gguf"), dtype="f16", lt_head_scale=ma.DECISIVE)
 else:
     path = ma.synth_gguf(os.path.join(cache, "magpie_357m_f32_k32.gguf"), lt_head_scale=ma.DECISIVE)
 dev = ma.Device(path, weights=weights)

@@ -87,28 +87,28 @@ int main(int argc, char **argv) {
         GemvP p = g;
         if (op == "ff1") {
             p.W = W1; p.N = 3072; p.src = x; p.src_ld = 768; p.out = out; p.out_ld = 3072;
-            if (op_ff1_1(p, st) != hipSuccess) exit(2);
+            if (f32_ops(1).ff1(p, st) != hipSuccess) exit(2);
             return {"ff1 (PRO_LN, GELU)", 3072, out};
         }
         if (op == "ff1x") {
             p.W = W1; p.N = 3072; p.src = x; p.src_ld = 768; p.part = xa_part; p.xres = xres; p.out = out; p.out_ld = 3072;
-            if (op_ff1x_1(p, st) != hipSuccess) exit(2);
+            if (f32_ops(1).ff1x(p, st) != hipSuccess) exit(2);
             return {"ff1x (PRO_XA_LN, GELU)", 3072, out};
         }
         if (op == "ff2") {
             p.W = W2; p.N = 768; p.src = h; p.src_ld = 3072; p.out = out; p.out_ld = 768; p.addsrc = x;
-            if (op_ff2_1(p, st) != hipSuccess) exit(2);
+            if (f32_ops(1).ff2(p, st) != hipSuccess) exit(2);
             return {"ff2 (PLAIN, ADD_STORE)", 768, out};
         }
         if (op == "qkv") {
             p.W = Wqkv; p.N = 2304; p.src = x; p.src_ld = 768; p.out = out; p.kc = kc; p.vc = vc; p.layer = 0;
-            if (op_qkv_1(p, st) != hipSuccess) exit(2);
+            if (f32_ops(1).qkv(p, st) != hipSuccess) exit(2);
             return {"qkv (PRO_LN, QKV)", 768, out};
         }
         if (op == "oproj") {
             if (hipMemcpyAsync(out, x, 768 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) exit(2);
             p.W = Wo; p.N = 768; p.part = sa_part; p.resid = out;
-            if (op_oproj_1(p, st) != hipSuccess) exit(2);
+            if (f32_ops(1).oproj(p, st) != hipSuccess) exit(2);
             return {"oproj (PRO_SA_MERGE, RESID)", 768, out};
         }
         if (op == "sa") {
