@@ -57,34 +57,18 @@ constexpr int KS[3] = {3, 7, 11};
 constexpr int DIL[3] = {1, 3, 5};
 constexpr int HOP = 1024;
 // LDS bytes per time row of a 32-channel f16 operand block: 64 B of data + 16 B of pad.
-// Measured and kept (round 5): a B fragment is one ds_read_b128 per lane at row base + l16,
-// byte 16 kg; by the 16-lane groups gfx950 serves a ds_read_b128 in (MI355X_MICROARCH.md
-// §LDS) an 80-byte row stride puts 3 lanes of each group on a taken bank quad and 96 bytes
-// none, yet 96 made the codec slower (8 x 32 frames 1.620 -> 1.637 / 1.654 ms, rb_kernel at
-// 64 channels 322 -> 345 us; gpurun_out/r05h_codec*.txt): the A-fragment stream and the
-// workgroups per CU, not LDS reads, bound these kernels.
-#ifndef MP_CODEC_ROWB
-#define MP_CODEC_ROWB 80
-#endif
-constexpr int LDS_ROWB = MP_CODEC_ROWB;
-// conv2_kernel pins each A-fragment ring load at its place in the tap loop (a scheduling
-// barrier after it): left free, the scheduler sank the loads to just before their MFMAs
-// (issue, then s_waitcnt vmcnt(1) four instructions later), exposing the L2 latency at
-// every step. Measured (gpurun_out/r05q_*): the 448-channel stage's conv2_kernel 241 ->
-// 180 us per decode. rb_kernel: its steps run as one flat (channel block, tap) sequence,
-// each step's B fragments read one step ahead (across channel blocks too) and pinned
-// before the step's MFMAs, the ring loads pinned after them (MP_RB_PIN 2): 8 x 32 frames
-// 1.58 -> 1.48 ms (gpurun_out/r05ze_*; the ring loads alone, 1: 1.49; a 2-slot ring 1.53;
-// a 4-slot one takes more than 128 VGPRs). Pinned per tap loop with the B reads fenced at
-// every channel block's start, it had cost 5-7 %.
-#ifndef MP_CONV2_PIN
-#define MP_CONV2_PIN 1
-#endif
-#ifndef MP_RB_PIN
-#define MP_RB_PIN 2
-#endif
-constexpr bool CONV2_PIN = MP_CONV2_PIN != 0;
-constexpr int RB_PIN = MP_RB_PIN;  // 1: sched barrier after the ring loads, 2: and after the B loads
+// A B fragment is one ds_read_b128 per lane at row base + l16, byte 16 kg. An 80-byte row
+// stride leaves 3 lanes of each 16-lane group on a taken bank quad and 96 bytes none, yet
+// 96 measured slower (codec): the A-fragment stream and the workgroups per CU,
+// not LDS reads, bound these kernels.
+constexpr int LDS_ROWB = 80;
+// The scheduling barriers in the conv loops (conv2_body, rb_body, rl_body) pin loads where
+// they are written. Left free, the scheduler sank every A-fragment ring load to just before
+// its MFMAs (issue, then s_waitcnt vmcnt(1) four instructions later) and exposed the L2
+// latency at every step. conv2_body pins the ring loads after each tap's MFMAs. rb_body and
+// rl_body run their steps as one flat (channel block, tap) sequence: each step's B fragments
+// are read one step ahead (across channel blocks too) and pinned before the step's MFMAs,
+// the ring loads after them.
 
 enum InMode { IN_F16 = 0, IN_FSQ = 1 };
 
@@ -143,25 +127,16 @@ __device__ __forceinline__ float hs_snake(float v, float a) {
 }
 __device__ __forceinline__ float hs_leaky(float v) { return fmaxf(v, 0.01f * v); }
 // 0: every lane's channels [c0, c1] snake, 1: every lane's leaky, 2: otherwise
-#ifndef MP_HS_SPLIT
-#define MP_HS_SPLIT 1
-#endif
 __device__ __forceinline__ int hs_wave_kind(int c0, int c1, int n_snake, int cin_real) {
-    if (!MP_HS_SPLIT) return 2;
     if (__all(c1 < n_snake)) return 0;
     if (__all(c0 >= n_snake && c1 < cin_real)) return 1;
     return 2;
 }
 
-// Residual convs (x' = x + conv(h) + b): the accumulators start at the residual x, the
+// Residual convs (x' = x + conv(h) + b): the accumulators start at the residual x and the
 // bias is added after the MFMAs -- (x + sum) + b in every kernel (conv_mfma_kernel,
-// conv2_kernel, rb_kernel, which loads x as phase C frees the registers, under conv_1's
-// MFMAs), the same bits across them; 0: (sum + b) + x, x loaded in the epilogue.
-// Measured (gpurun_out/r05zs_*): 1.49-1.51 -> 1.42-1.43 ms per 8 x 32-frame decode.
-#ifndef MP_RESINIT
-#define MP_RESINIT 1
-#endif
-constexpr bool RESINIT = MP_RESINIT != 0;
+// conv2_kernel, rl_kernel, and rb_kernel, which loads x as phase C frees the registers,
+// under conv_1's MFMAs), the same bits across them. The reference's order is (sum + b) + x.
 
 // fsq_dequantize_cpu (nano-codec.cpp:721-752): channel c = 4*cb + d
 __device__ __forceinline__ float fsq(int code, int d) {
@@ -203,7 +178,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
     floatx4 acc[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
-    if (RESINIT && p.resid[br]) {  // the accumulators start at the residual (MP_RESINIT)
+    if (p.resid[br]) {  // the accumulators start at the residual
         const int o = m0 + rw * 16 + 4 * kg;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -319,10 +294,6 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
         if (t >= p.T) continue;
         float4 v = make_float4(acc[j][0] + bb.x, acc[j][1] + bb.y, acc[j][2] + bb.z, acc[j][3] + bb.w);
         const size_t off = chunk_out + (size_t)t * p.Coutp + o;
-        if (!RESINIT && p.resid[br]) {
-            const float4 r = *(const float4 *)(p.resid[br] + off);
-            v.x = r.x + v.x; v.y = r.y + v.y; v.z = r.z + v.z; v.w = r.w + v.w;  // input + h (568-599)
-        }
         if (p.out[br]) *(float4 *)(p.out[br] + off) = v;
         if (p.act[br]) {  // the next conv's operand: f16(HalfSnake(v)) (ggml F16 im2col)
             typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -376,7 +347,7 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
     for (int a = 0; a < C2_WR; ++a)
 #pragma unroll
         for (int j = 0; j < C2_NT; ++j) acc[a][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-    if (RESINIT && p.resid[br]) {  // the accumulators start at the residual (MP_RESINIT)
+    if (p.resid[br]) {  // the accumulators start at the residual
 #pragma unroll
         for (int a = 0; a < C2_WR; ++a)
 #pragma unroll
@@ -446,7 +417,7 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
                 ring[st % R][0] = *(const half8 *)(wrow0 + (size_t)(st + R) * 512);
                 ring[st % R][1] = *(const half8 *)(wrow1 + (size_t)(st + R) * 512);
             }
-            if constexpr (CONV2_PIN) __builtin_amdgcn_sched_barrier(0);  // the ring loads stay R steps ahead
+            __builtin_amdgcn_sched_barrier(0);  // the ring loads stay R steps ahead
             if (k + 1 < KS) {
 #pragma unroll
                 for (int j = 0; j < C2_NT; ++j) bc[j] = bn[j];
@@ -455,9 +426,9 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
     }
     // ---- epilogue through LDS: the accumulator tile (C[row = 4*kg + r][col = l16] per
     // fragment) is written as [time][channel] f32, then every thread handles 4
-    // consecutive channels of one time step in linear order, so bias / residual /
-    // output / f16 operand accesses are contiguous rows (the whole [t0, t0 + BN) x
-    // Coutp range when the tile spans every channel)
+    // consecutive channels of one time step in linear order, so bias / output / f16
+    // operand accesses are contiguous rows (the whole [t0, t0 + BN) x Coutp range when
+    // the tile spans every channel)
     constexpr int BM = RWV * 32, CST = BM + 4;  // +4 floats: row stride off the bank period
     float *ct = (float *)xs;
     __syncthreads();  // every wave is done with the input buffers
@@ -479,20 +450,9 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
         const float4 a4 = *(const float4 *)(p.act_alpha[br] + o);
         al[0] = a4.x; al[1] = a4.y; al[2] = a4.z; al[3] = a4.w;
     }
-    // the residual rows of every step this thread stores, loaded before the first store
-    // (a load behind a store to another buffer waited one round trip per step)
     constexpr int RSTEP = NTH / (BM / 4), IT = BN / RSTEP;
     static_assert(BN % RSTEP == 0, "whole steps per thread");
     const int tl0 = tid / (BM / 4);
-    float4 rres[IT];
-    if (!RESINIT && p.resid[br]) {
-#pragma unroll
-        for (int i = 0; i < IT; ++i) {
-            const int t = t0 + tl0 + i * RSTEP;
-            rres[i] = t < p.T ? *(const float4 *)(p.resid[br] + chunk_out + (size_t)t * p.Coutp + o)
-                              : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
         const int tl = tl0 + i * RSTEP;
@@ -501,10 +461,6 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
         const float4 a4 = *(const float4 *)(ct + tl * CST + cl);
         float4 v = make_float4(a4.x + bb.x, a4.y + bb.y, a4.z + bb.z, a4.w + bb.w);
         const size_t off = chunk_out + (size_t)t * p.Coutp + o;
-        if (!RESINIT && p.resid[br]) {
-            const float4 r = rres[i];
-            v.x = r.x + v.x; v.y = r.y + v.y; v.z = r.z + v.z; v.w = r.w + v.w;  // input + h (568-599)
-        }
         if (p.out[br]) *(float4 *)(p.out[br] + off) = v;
         if (p.act[br]) {  // the next conv's operand: f16(HalfSnake(v)) (ggml F16 im2col), block-major
             typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -560,54 +516,24 @@ struct RbP {
     int nsnake, creal, T, dil, tiles_per_chunk, nchunk;
     int ntiles;     // tiles per branch (nchunk x tiles_per_chunk)
     int order[3];   // item order: branch of items [k ntiles, (k + 1) ntiles), most taps first
-    int *ctr;       // this launch's item counter (zeroed once per decode)
     unsigned long long *ts;  // diagnostics (MAGPIE_CODEC_TS): per workgroup RB_TS_N phase stamps, else null
 };
 constexpr int RB_ROWB = LDS_ROWB;  // LDS bytes per time row of a 32-channel block
 constexpr int RB_TS_GX = 16384;    // diagnostics: stamp rows per branch (workgroups beyond: none)
 constexpr int RB_TS_N = 48;        // diagnostics: stamps per workgroup (16 + 2 per wave)
-// A-fragment ring slots of the residual-block convs (steps of lead for the weight loads)
-#ifndef MP_RB_RING
-#define MP_RB_RING 3
-#endif
-constexpr int RB_RING = MP_RB_RING;
-// rb_kernel's work items: (branch, tile), heaviest branch (most taps) first, one workgroup
-// per item in a 1-D grid. MP_RB_PERSIST=1: persistent workgroups taking items from a
-// counter, the next item's x rows prefetched into registers during the current item's
-// convolutions. Measured (gpurun_out/r05z_*, 8 x 32 frames): per-item with heaviest-first
-// order 1.584-1.599 ms against 1.647-1.649 for the earlier branch-major 2-D grid
-// (the 11-tap branch's workgroups no longer start last); persistent 1.91-1.92 ms -- the
-// prefetched rows (48 VGPRs at 128 channels) halve the workgroups per CU. Off.
-#ifndef MP_RB_PERSIST
-#define MP_RB_PERSIST 0
-#endif
-constexpr bool RB_PERSIST = MP_RB_PERSIST != 0;
-// rb_kernel's conv_d bias, HS_sk alpha and conv_1 bias staged in LDS with the x rows (1), or
-// loaded from global memory where phases C / E use them (0)
-#ifndef MP_RB_PRM
-#define MP_RB_PRM 1
-#endif
-constexpr bool RB_PRM = MP_RB_PRM != 0;
-// rb_kernel's residual rows (phase E) loaded before conv_1 (1) or after it (0)
-#ifndef MP_RB_RXPRE
-#define MP_RB_RXPRE 0
-#endif
-constexpr bool RB_RXPRE = MP_RB_RXPRE != 0;
-constexpr bool RB_RESINIT = RESINIT;
+// A-fragment ring slots of the residual-block convs (steps of lead for the weight loads);
+// 2 measured slower, 4 take more than 128 VGPRs
+constexpr int RB_RING = 3;
 constexpr int RB_MAXHALO = 50;  // (11 - 1) * 5
 
 template <int RWV, int CWV, int NT>
 constexpr int rb_lds_bytes() { return RWV * (16 * NT * CWV + RB_MAXHALO) * RB_ROWB; }
-// + the staged parameters (RB_PRM): bd, al_sk, b1, CP floats each
+// + the staged parameters: bd, al_sk, b1, CP floats each
 template <int RWV, int CWV, int NT>
-constexpr int rb_lds_total() { return rb_lds_bytes<RWV, CWV, NT>() + (RB_PRM ? 3 * RWV * 32 * 4 : 0); }
+constexpr int rb_lds_total() { return rb_lds_bytes<RWV, CWV, NT>() + 3 * RWV * 32 * 4; }
 
-// Work items (branch, tile), heaviest branch first (RB_PERSIST above). With PERSIST the
-// grid holds as many workgroups as the chip runs at once; workgroup g starts with item g,
-// takes the next from a per-launch counter and loads its x rows into registers right after
-// the current item's rows are staged (their HBM latency under the current item's convs:
-// tools_dev/codec_rb_timeline.py shows ~6 us of rows per workgroup on every stage). Tiles
-// and their arithmetic are the same in every form: the same bits.
+// rb_kernel's work items are (branch, tile), heaviest branch (most taps) first, one workgroup
+// per item in a 1-D grid: the 11-tap branch's workgroups do not start last.
 template <int RWV, int CWV, int NT>
 struct RbGeo {
     static constexpr int NCB = RWV, CPD = NCB * 32, NTH = 64 * RWV * CWV;
@@ -624,12 +550,15 @@ struct RbGeo {
     __device__ static int piece(int tid) { return HALF ? ((tid >> 6) & 1) * PH + (tid & 63) % PH : tid % PPR; }
     __device__ static int row0(int tid) { return HALF ? (tid >> 7) * (64 / PH) + (tid & 63) / PH : tid / PPR; }
 };
-// the x rows item `it` stages (thread: piece pc of rows r0 + u RSTEP), zero outside the chunk
+// the x rows an item stages (thread: piece pc of rows r0 + u RSTEP), zero outside the chunk.
+// Called from rb_body, inside rb_kernel's switch over the tap count: issued once ahead of
+// the switch, the rows cost 26-52 more VGPRs (200 bytes of scratch per lane at 224
+// channels). The halo takes the tap count from p.ks, not rb_body's KS: the same value, but
+// with the constant the 224-channel kernel spills two registers.
 template <int RWV, int CWV, int NT>
-__device__ __forceinline__ void rb_load_rows(const RbP &p, int it, float4 (&v)[RbGeo<RWV, CWV, NT>::NU][2]) {
+__device__ __forceinline__ void rb_load_rows(const RbP &p, int br, int tile, float4 (&v)[RbGeo<RWV, CWV, NT>::NU][2]) {
     using G = RbGeo<RWV, CWV, NT>;
     const int tid = threadIdx.x, pc = G::piece(tid), r0 = G::row0(tid);
-    const int br = p.order[it / p.ntiles], tile = it % p.ntiles;
     const int halo = (p.ks[br] - 1) * p.dil, rows = G::NCD + halo;
     const int chunk = tile / p.tiles_per_chunk, t0 = (tile % p.tiles_per_chunk) * G::BN, tx0 = t0 - 16 - halo;
     const float *src = p.x[br] + (size_t)chunk * p.T * G::CPD + pc * 8;
@@ -643,18 +572,18 @@ __device__ __forceinline__ void rb_load_rows(const RbP &p, int it, float4 (&v)[R
         }
     }
 }
-// One item: branch br's tile `tile`, its rows in v. `next`: the item whose rows are loaded
-// into v once this item's rows are staged (none if >= 3 ntiles).
-template <int KS, int RWV, int CWV, int NT, int R, bool PERSIST>
-__device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile, int next,
-                                        float4 (&v)[RbGeo<RWV, CWV, NT>::NU][2], bool first) {
+// One item: branch br's tile `tile`.
+template <int KS, int RWV, int CWV, int NT, int R>
+__device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile) {
     using G = RbGeo<RWV, CWV, NT>;
     constexpr int NCB = G::NCB, CPD = G::CPD, NCD = G::NCD, BN = G::BN, XR = G::XR, RSTEP = G::RSTEP, NU = G::NU;
     constexpr int NS = NCB * KS;  // A-stream steps (channel block, tap)
-    // diagnostics: thread 0 stamps the phases of its first item (A x rows staged, B conv_d,
-    // C the intermediate staged, D conv_1, E stored; wave 0's own: 9 conv_d done, 6 its part
-    // of C computed, 7 its residual rows landed, 8 its stores done)
-    unsigned long long *tsw = p.ts && first && blockIdx.x < RB_TS_GX ? p.ts + RB_TS_N * ((size_t)br * RB_TS_GX + blockIdx.x) : nullptr;
+    float4 v[NU][2];
+    rb_load_rows<RWV, CWV, NT>(p, br, tile, v);
+    // diagnostics: thread 0 stamps the phases (A x rows staged, B conv_d, C the intermediate
+    // staged, D conv_1, E stored; wave 0's own: 9 conv_d done, 6 its part of C computed, 7 its
+    // epilogue operands landed, 8 its stores done)
+    unsigned long long *tsw = p.ts && blockIdx.x < RB_TS_GX ? p.ts + RB_TS_N * ((size_t)br * RB_TS_GX + blockIdx.x) : nullptr;
     auto stamp = [&](int k) {
         if (tsw && threadIdx.x == 0) tsw[k] = __builtin_amdgcn_s_memrealtime();
     };
@@ -673,12 +602,10 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
     constexpr int NPRM = 3 * CPD / 4;  // float4 pieces
     static_assert(NPRM <= G::NTH, "one piece per thread");
     float4 pv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (RB_PRM) {
-        if (tid < NPRM) {
-            const int which = tid / (CPD / 4), o = (tid % (CPD / 4)) * 4;
-            const float *src = which == 0 ? p.bd[br] : which == 1 ? p.al_sk[br] : p.b1[br];
-            pv = *(const float4 *)(src + o);
-        }
+    if (tid < NPRM) {
+        const int which = tid / (CPD / 4), o = (tid % (CPD / 4)) * 4;
+        const float *src = which == 0 ? p.bd[br] : which == 1 ? p.al_sk[br] : p.b1[br];
+        pv = *(const float4 *)(src + o);
     }
     // ---- A: x rows -> HS_in -> f16 -> LDS (each thread keeps one 8-channel piece)
     {
@@ -709,11 +636,7 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
         else if (kind == 1) stage_rows([&](float x, int) { return hs_leaky(x); });
         else stage_rows([&](float x, int i) { return half_snake_sel(x, c0 + i, p.nsnake, p.creal, al[i]); });
     }
-    if constexpr (RB_PRM)
-        if (tid < NPRM) *(float4 *)(prm + 4 * tid) = pv;
-    // the next item's rows, in flight during this item's convolutions
-    if constexpr (PERSIST)
-        if (next < 3 * p.ntiles) rb_load_rows<RWV, CWV, NT>(p, next, v);
+    if (tid < NPRM) *(float4 *)(prm + 4 * tid) = pv;
     __syncthreads();
     stamp(1);
 
@@ -722,13 +645,7 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
     floatx4 acc[C2_WR][NT];
     half8 ring[R][C2_WR];
     const int colb = cw * 16 * NT + l16;
-    auto conv = [&](const _Float16 *wf, int rowoff, int dk, int nt, bool init) {
-        if (init) {
-#pragma unroll
-            for (int a = 0; a < C2_WR; ++a)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[a][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-        }
+    auto conv = [&](const _Float16 *wf, int rowoff, int dk, int nt) {
         const _Float16 *wrow0 = wf + (size_t)(rw * 2) * NS * 512 + lane * 8, *wrow1 = wrow0 + (size_t)NS * 512;
 #pragma unroll
         for (int q = 0; q < R; ++q)
@@ -750,7 +667,7 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
 #pragma unroll
                 for (int j = 0; j < NT; ++j) bn[j] = bfrag(st + 1, j);
             }
-            if constexpr (RB_PIN >= 2) __builtin_amdgcn_sched_barrier(0);  // ... issued before this step's MFMAs
+            __builtin_amdgcn_sched_barrier(0);  // ... issued before this step's MFMAs
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 if (j < nt) {
@@ -762,7 +679,7 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
                 ring[st % R][0] = *(const half8 *)(wrow0 + (size_t)(st + R) * 512);
                 ring[st % R][1] = *(const half8 *)(wrow1 + (size_t)(st + R) * 512);
             }
-            if constexpr (RB_PIN >= 1) __builtin_amdgcn_sched_barrier(0);  // the ring loads stay R steps ahead
+            __builtin_amdgcn_sched_barrier(0);  // the ring loads stay R steps ahead
             if (st + 1 < NS) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) bc[j] = bn[j];
@@ -770,7 +687,11 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
         }
     };
     // B: conv_d, column c = time t0 - 16 + c, x row c + k d
-    conv(p.Wd[br], 0, d, NT, true);
+#pragma unroll
+    for (int a = 0; a < C2_WR; ++a)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[a][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+    conv(p.Wd[br], 0, d, NT);
     // each lane's 8 channels: rw * 32 + a * 16 + 4 kg + r
     const int chl = rw * 32 + 4 * kg;
     stamp(9);
@@ -785,13 +706,8 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
         float4 bbs[C2_WR], als[C2_WR];
 #pragma unroll
         for (int a = 0; a < C2_WR; ++a) {
-            if constexpr (RB_PRM) {
-                bbs[a] = *(const float4 *)(prm + chl + a * 16);
-                als[a] = *(const float4 *)(prm + CPD + chl + a * 16);
-            } else {
-                bbs[a] = *(const float4 *)(p.bd[br] + chl + a * 16);
-                als[a] = *(const float4 *)(p.al_sk[br] + chl + a * 16);
-            }
+            bbs[a] = *(const float4 *)(prm + chl + a * 16);
+            als[a] = *(const float4 *)(prm + CPD + chl + a * 16);
         }
 #pragma unroll
         for (int a = 0; a < C2_WR; ++a) {
@@ -807,12 +723,11 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
                     for (int r = 0; r < 4; ++r) h[r] = (_Float16)hs(acc[a][j][r] + bv[r], r);
                     if (t < 0) h = half4{0, 0, 0, 0};
                     *(half4 *)(xs + rw * XR * RB_ROWB + c * RB_ROWB + (a * 16 + 4 * kg) * 2) = h;
-                    if constexpr (RB_RESINIT) {  // conv_1's accumulator starts at its residual rows
-                        const int to = t0 + cw * 16 * NT + j * 16 + l16;
-                        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-                        if (j < nt && to < p.T) r = *(const float4 *)(p.x[br] + cbase + (size_t)to * CPD + chl + a * 16);
-                        acc[a][j] = floatx4{r.x, r.y, r.z, r.w};
-                    }
+                    // conv_1's accumulator starts at its residual rows
+                    const int to = t0 + cw * 16 * NT + j * 16 + l16;
+                    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (j < nt && to < p.T) r = *(const float4 *)(p.x[br] + cbase + (size_t)to * CPD + chl + a * 16);
+                    acc[a][j] = floatx4{r.x, r.y, r.z, r.w};
                 }
             };
             const int kind = hs_wave_kind(ch, ch + 3, p.nsnake, p.creal);
@@ -825,33 +740,14 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
     __syncthreads();
     stamp(3);
     // ---- D: conv_1, output column o = time t0 + o, h row o + 16 - (KS - 1) + k
-    // ---- E's operands: every residual element and bias before the stores (a load after a
-    // store to the other buffer may alias it, so per fragment the loop had waited one L2
-    // round trip each); with RB_RXPRE before conv_1, their latency under its MFMAs
-    float4 bb1[C2_WR], rx[C2_WR][NT];
-    auto load_e = [&]() {
-#pragma unroll
-        for (int a = 0; a < C2_WR; ++a) {
-            const int ch = chl + a * 16;
-            bb1[a] = RB_PRM ? *(const float4 *)(prm + 2 * CPD + ch) : *(const float4 *)(p.b1[br] + ch);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int t = t0 + cw * 16 * NT + j * 16 + l16;
-                rx[a][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!RB_RESINIT && j < nt && t < p.T) rx[a][j] = *(const float4 *)(p.x[br] + cbase + (size_t)t * CPD + ch);
-            }
-        }
-    };
-    if constexpr (RB_RXPRE) {
-        load_e();
-        __builtin_amdgcn_sched_barrier(0);  // issued here, not sunk to their use
-    }
-    conv(p.W1[br], 16 - (KS - 1), 1, nt, !RB_RESINIT);
+    conv(p.W1[br], 16 - (KS - 1), 1, nt);
     stamp(4);
     if (tsw && lane == 0) tsw[17 + 2 * w] = __builtin_amdgcn_s_memrealtime();  // every wave's conv_1 end
-    // ---- E: + bias + x -> x'
-    if constexpr (!RB_RXPRE) load_e();
-    if (tsw) {  // diagnostics: wave 0's residual rows landed
+    // ---- E: (x + conv_1) + bias -> x', both fragments' bias rows before the stores
+    float4 bb1[C2_WR];
+#pragma unroll
+    for (int a = 0; a < C2_WR; ++a) bb1[a] = *(const float4 *)(prm + 2 * CPD + chl + a * 16);
+    if (tsw) {  // diagnostics: wave 0's epilogue operands landed
         __builtin_amdgcn_s_waitcnt(0);
         stamp(7);
     }
@@ -865,13 +761,7 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
             if (j >= nt || t >= p.T) continue;
             const size_t off = cbase + (size_t)t * CPD + ch;
             const floatx4 y = acc[a][j];
-            const float4 vo = make_float4(y[0] + bb.x, y[1] + bb.y, y[2] + bb.z, y[3] + bb.w);
-            if constexpr (RB_RESINIT) {
-                *(float4 *)(p.out[br] + off) = vo;  // (input + conv_1) + bias
-                continue;
-            }
-            const float4 r = rx[a][j];
-            *(float4 *)(p.out[br] + off) = make_float4(r.x + vo.x, r.y + vo.y, r.z + vo.z, r.w + vo.w);  // input + h
+            *(float4 *)(p.out[br] + off) = make_float4(y[0] + bb.x, y[1] + bb.y, y[2] + bb.z, y[3] + bb.w);
         }
     }
     if (tsw) {
@@ -882,85 +772,22 @@ __device__ __forceinline__ void rb_body(const RbP &p, char *xs, int br, int tile
     }
 }
 
-// PERSIST false: one item per workgroup (the grid covers every item), no prefetch -- for
-// the 224-channel stage, whose 14-wave workgroups cannot hold a second tile's rows
-// minimum waves per SIMD the register allocation must allow (launch bounds): MP_RB3_W /
-// MP_RB4_W for the 64- / 32-channel stages' kernels (<2,4,4> / <1,8,2>), 0: the default
-#ifndef MP_RB3_W
-#define MP_RB3_W 0
-#endif
-#ifndef MP_RB4_W
-#define MP_RB4_W 0
-#endif
-// per stage (224 / 128 / 64 / 32 channels): column waves (CWV) and 16-column fragments
-// per wave (NT); a tile is 16 NT CWV - 16 outputs
-#ifndef MP_RB1_CWV
-#define MP_RB1_CWV 2
-#endif
-#ifndef MP_RB1_NT
-#define MP_RB1_NT 4
-#endif
-#ifndef MP_RB2_CWV
-#define MP_RB2_CWV 2
-#endif
-#ifndef MP_RB2_NT
-#define MP_RB2_NT 4
-#endif
-#ifndef MP_RB3_CWV
-#define MP_RB3_CWV 4
-#endif
-#ifndef MP_RB3_NT
-#define MP_RB3_NT 4
-#endif
-#ifndef MP_RB4_CWV
-#define MP_RB4_CWV 8
-#endif
-#ifndef MP_RB4_NT
-#define MP_RB4_NT 2
-#endif
-#ifndef MP_RB1_W
-#define MP_RB1_W 0
-#endif
+// minimum waves per SIMD the register allocation must allow (launch bounds)
 template <int RWV, int CWV, int NT>
 constexpr int rb_minw() {
-    if (RWV == 2 && CWV == 4 && NT == 4 && MP_RB3_W) return MP_RB3_W;
-    if (RWV == 1 && CWV == 8 && NT == 2 && MP_RB4_W) return MP_RB4_W;
-    if (RWV == 7 && MP_RB1_W) return MP_RB1_W;
     if (NT >= 8) return 2;  // <= 256 registers
     return RWV * CWV > 8 || NT > 4 ? 1 : 2;
 }
-template <int RWV, int CWV, int NT, bool PERSIST>
+template <int RWV, int CWV, int NT>
 __global__ __launch_bounds__(64 * RWV * CWV, (rb_minw<RWV, CWV, NT>())) void rb_kernel(RbP p) {
     __shared__ __attribute__((aligned(16))) char xs[rb_lds_total<RWV, CWV, NT>()];
-    __shared__ int sh_next;
-    using G = RbGeo<RWV, CWV, NT>;
-    const int total = 3 * p.ntiles;
-    int it = blockIdx.x;
-    if (it >= total) return;
-    float4 v[G::NU][2];
-    if constexpr (!PERSIST) {  // one item: its rows loaded and staged in one place
-        const int br = p.order[it / p.ntiles], tile = it % p.ntiles;
-        switch (p.ks[br]) {
-            case 3: rb_load_rows<RWV, CWV, NT>(p, it, v); rb_body<3, RWV, CWV, NT, RB_RING, false>(p, xs, br, tile, total, v, true); break;
-            case 7: rb_load_rows<RWV, CWV, NT>(p, it, v); rb_body<7, RWV, CWV, NT, RB_RING, false>(p, xs, br, tile, total, v, true); break;
-            default: rb_load_rows<RWV, CWV, NT>(p, it, v); rb_body<11, RWV, CWV, NT, RB_RING, false>(p, xs, br, tile, total, v, true); break;
-        }
-        return;
-    }
-    rb_load_rows<RWV, CWV, NT>(p, it, v);
-    for (bool first = true; it < total; first = false) {
-        // the next item: from the per-launch counter (items below gridDim.x are the static
-        // first ones); the previous item's barriers have retired every read of sh_next
-        if (threadIdx.x == 0) sh_next = PERSIST ? (int)gridDim.x + atomicAdd(p.ctr, 1) : total;
-        __syncthreads();  // sh_next published; the previous item's conv_1 is done with the LDS rows
-        const int next = sh_next;
-        const int br = p.order[it / p.ntiles], tile = it % p.ntiles;
-        switch (p.ks[br]) {
-            case 3: rb_body<3, RWV, CWV, NT, RB_RING, PERSIST>(p, xs, br, tile, next, v, first); break;
-            case 7: rb_body<7, RWV, CWV, NT, RB_RING, PERSIST>(p, xs, br, tile, next, v, first); break;
-            default: rb_body<11, RWV, CWV, NT, RB_RING, PERSIST>(p, xs, br, tile, next, v, first); break;
-        }
-        it = next;
+    const int it = blockIdx.x;
+    if (it >= 3 * p.ntiles) return;
+    const int br = p.order[it / p.ntiles], tile = it % p.ntiles;
+    switch (p.ks[br]) {
+        case 3: rb_body<3, RWV, CWV, NT, RB_RING>(p, xs, br, tile); break;
+        case 7: rb_body<7, RWV, CWV, NT, RB_RING>(p, xs, br, tile); break;
+        default: rb_body<11, RWV, CWV, NT, RB_RING>(p, xs, br, tile); break;
     }
 }
 
@@ -988,12 +815,6 @@ struct RlP {
     int first[4];
 };
 constexpr int RL_HALO = RB_MAXHALO;  // zero rows left of column 0: conv_d's (ks - 1) d at most
-#ifndef MP_RL_NT32
-#define MP_RL_NT32 4  // 16-column fragments per wave, 32-channel stage
-#endif
-#ifndef MP_RL_NT64
-#define MP_RL_NT64 4  // 64-channel stage (4 column waves)
-#endif
 
 template <int KS, int RWV, int CWV, int NT, int R>
 __device__ __forceinline__ void rl_body(const RlP &p, char *xs, int br, int tile) {
@@ -1083,7 +904,7 @@ __device__ __forceinline__ void rl_body(const RlP &p, char *xs, int br, int tile
 #pragma unroll
                 for (int j = 0; j < NT; ++j) bn[j] = bfrag(st + 1, j);
             }
-            if constexpr (RB_PIN >= 2) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 if (j >= jlo) {
@@ -1095,7 +916,7 @@ __device__ __forceinline__ void rl_body(const RlP &p, char *xs, int br, int tile
                 ring[st % R][0] = *(const half8 *)(wrow0 + (size_t)(st + R) * 512);
                 ring[st % R][1] = *(const half8 *)(wrow1 + (size_t)(st + R) * 512);
             }
-            if constexpr (RB_PIN >= 1) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             if (st + 1 < NS) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) bc[j] = bn[j];
@@ -1151,20 +972,9 @@ __device__ __forceinline__ void rl_body(const RlP &p, char *xs, int br, int tile
         }
 }
 
-#ifndef MP_RL_W32
-#define MP_RL_W32 2  // minimum waves per SIMD the register allocation must allow, 32-channel stage
-#endif
-#ifndef MP_RL_W64
-#define MP_RL_W64 2
-#endif
-#ifndef MP_RL_CWV32
-#define MP_RL_CWV32 4  // column waves, 32-channel stage
-#endif
-#ifndef MP_RL_CWV64
-#define MP_RL_CWV64 4  // column waves, 64-channel stage
-#endif
+// launch bounds: the register allocation must allow 2 waves per SIMD
 template <int RWV, int CWV, int NT>
-__global__ __launch_bounds__(64 * RWV * CWV, RWV == 1 ? MP_RL_W32 : MP_RL_W64) void rl_kernel(RlP p) {
+__global__ __launch_bounds__(64 * RWV * CWV, 2) void rl_kernel(RlP p) {
     __shared__ __attribute__((aligned(16))) char xs[RWV * (16 * NT * CWV + RL_HALO) * RB_ROWB];
     const int it = blockIdx.x;
     if (it >= p.first[3]) return;
@@ -1180,11 +990,6 @@ __global__ __launch_bounds__(64 * RWV * CWV, RWV == 1 ? MP_RL_W32 : MP_RL_W64) v
 // Grouped ConvTranspose1d (nano-codec.cpp:481-565), HalfSnake on its input,
 // optional 3-branch mean before it: out[t][g] = b[g] + sum_{c in {2g,2g+1}}
 // sum_{tau: 0 <= t - tau*s < 2s} x[tau][c] * w[c][t - tau*s]; kept length T*s.
-// input steps per thread of the later stages' ConvTranspose (each thread re-reads one step
-// of halo: R = 8 reads 1.125x the input; 4: 1.25x, 1.45-1.47 vs 1.44-1.45 ms per decode)
-#ifndef MP_CT_R
-#define MP_CT_R 8
-#endif
 struct ConvTP {
     const float *x, *xa, *xb;  // input [chunk][Tin][Cinp] (xa/xb: AVG3)
     const float *alpha;
@@ -1196,66 +1001,19 @@ struct ConvTP {
     const float *act_alpha[3];
     int cout_real, Coutp, Tin, s, nchunk;
 };
-// One thread per (chunk, input step tau, output group g): its outputs are
-// t in [tau*s, tau*s + s), fed by inputs tau-1 and tau of channels 2g, 2g+1
-// (the 3-branch mean and HalfSnake of those 4 values computed once).
-template <bool AVG>
-__global__ __launch_bounds__(256) void conv_transpose_kernel(ConvTP p) {
-    const size_t total = (size_t)p.nchunk * p.Tin * p.Coutp;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int g = (int)(e % p.Coutp);
-        const size_t tt = e / p.Coutp;
-        const int tau = (int)(tt % p.Tin), chunk = (int)(tt / p.Tin);
-        const int K = 2 * p.s;
-        float in[2][2] = {{0.f, 0.f}, {0.f, 0.f}};  // [tau-1, tau][channel 2g, 2g+1]
-        if (g < p.cout_real) {
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const int ta = tau - 1 + dt;
-                if (ta < 0) continue;
-#pragma unroll
-                for (int ci = 0; ci < 2; ++ci) {
-                    const int c = 2 * g + ci;
-                    const size_t xo = ((size_t)chunk * p.Tin + ta) * p.Cinp + c;
-                    float v = p.x[xo];
-                    if constexpr (AVG) v = ((v + p.xa[xo]) + p.xb[xo]) * (1.0f / 3.0f);
-                    in[dt][ci] = half_snake(v, c, p.n_snake, p.cin_real, p.alpha);
-                }
-            }
-        }
-        for (int u = 0; u < p.s; ++u) {
-            const int t = tau * p.s + u;
-            float acc = 0.f;
-            if (g < p.cout_real) {
-                // ggml order: channel c outer, tau = t/s - 1 then t/s inner
-#pragma unroll
-                for (int ci = 0; ci < 2; ++ci) {
-                    const int c = 2 * g + ci;
-                    if (tau >= 1) acc += in[0][ci] * p.w[(size_t)c * K + (t - (tau - 1) * p.s)];
-                    acc += in[1][ci] * p.w[(size_t)c * K + (t - tau * p.s)];
-                }
-                acc += p.bias[g];
-            }
-            const size_t oo = ((size_t)chunk * p.Tin * p.s + t) * p.Coutp + g;
-            p.out[oo] = acc;
-            // the f16 operands block-major [chunk][Coutp/32][T][32]
-            const size_t ob = (size_t)chunk * p.Tin * p.s * p.Coutp + ((size_t)(g >> 5) * p.Tin * p.s + t) * 32 + (g & 31);
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-                p.act[j][ob] = (_Float16)half_snake(acc, g, p.cout_real / 2, p.cout_real, p.act_alpha[j]);
-        }
-    }
-}
-
-// The same grouped ConvTranspose1d with the shape compile-time per stage: one thread
-// per (chunk, run of R input steps, output channel pair). The channel pair's 4
-// input channels arrive as one float4 per branch and step (the previous step kept in
-// registers), its 4 x 2s weights and all alphas stay in registers, outputs go out as
-// float2 (f32) and half2 (block-major f16 operands). Same arithmetic and summation
-// order as conv_transpose_kernel.
+// input steps per thread on the long later stages: a thread re-reads one step of halo,
+// 1.125x the input at 8 (4: 1.25x, measured slower)
+constexpr int CT_R = 8;
+// The shape is compile-time per stage: one thread per (chunk, run of R input steps, output
+// channel pair). Its outputs are t in [tau*s, tau*s + s) for each of its steps tau, fed by
+// inputs tau-1 and tau (the previous step kept in registers; each thread re-reads one step
+// of halo). The channel pair's 4 input channels arrive as one float4 per branch and step,
+// their 3-branch mean (AVG) and HalfSnake computed once; its 4 x 2s weights and all alphas
+// stay in registers, outputs go out as float2 (f32) and half2 (block-major f16 operands).
+// ggml's summation order: channel c outer, tau = t/s - 1 then t/s inner.
 // ACT: also emit the 3 branches' k=0 in_conv operands (the stages whose residual
 // blocks are fused compute them from the f32 output instead).
-template <int CINP, int COUTP, int S, bool AVG, int R, bool ACT = true>
+template <int CINP, int COUTP, int S, bool AVG, int R, bool ACT>
 __global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p) {
     constexpr int NG = COUTP / 2, K = 2 * S;
     const int e = blockIdx.x * 256 + threadIdx.x;
@@ -1424,7 +1182,6 @@ struct mp_codec {
     float *h_audio_pin = nullptr;
     size_t h_codes_cap = 0, h_audio_cap = 0;
     float last_ms = 0.f;  // device time of the last decode (launch sequence only)
-    int *rb_ctr = nullptr;  // rb_kernel's item counters, one per launch of a decode (zeroed per decode)
     // diagnostics (MAGPIE_CODEC_TS=stage,block,file): the phase stamps of one rb_kernel launch
     unsigned long long *ts_dev = nullptr;
     int ts_stage = -1, ts_block = -1;
@@ -1585,55 +1342,34 @@ hipError_t launch_conv2(mpc::ConvP p, int nchunk, int nbranch, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int RWV, int CWV, int NT = 4, bool PERSIST = mpc::RB_PERSIST>
+template <int RWV, int CWV, int NT>
 hipError_t launch_rb(mpc::RbP p, int nchunk, hipStream_t s) {
     constexpr int BN = 16 * NT * CWV - 16;
     p.tiles_per_chunk = (p.T + BN - 1) / BN;
     p.nchunk = nchunk;
     p.ntiles = nchunk * p.tiles_per_chunk;
-    // items heaviest first: the branches by tap count, descending
+    // one workgroup per item, heaviest first: the branches by tap count, descending
     for (int j = 0; j < 3; ++j) p.order[j] = j;
     std::sort(p.order, p.order + 3, [&](int a, int b) { return p.ks[a] > p.ks[b]; });
-    const int total = 3 * p.ntiles;
-    // persistent: as many workgroups as the chip runs at once (the kernel's occupancy
-    // times the CU count), each taking items from the counter; else one per item
-    int gx = total;
-    if (PERSIST) {
-        // cached per device (a process may drive devices of different CU counts)
-        constexpr int MAXDEV = 64;
-        static int per_cu_d[MAXDEV], ncu_d[MAXDEV];
-        int dev = 0;
-        hipGetDevice(&dev);
-        int per_cu = 1, ncu = 1;
-        if (dev >= 0 && dev < MAXDEV && per_cu_d[dev] > 0) {
-            per_cu = per_cu_d[dev];
-            ncu = ncu_d[dev];
-        } else {
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mpc::rb_kernel<RWV, CWV, NT, PERSIST>, 64 * RWV * CWV, 0) !=
-                    hipSuccess || per_cu < 1)
-                per_cu = 1;
-            if (dev >= 0 && dev < MAXDEV) { ncu_d[dev] = ncu; per_cu_d[dev] = per_cu; }
-        }
-        gx = std::min(total, std::max(1, per_cu * ncu));
-    }
-    hipLaunchKernelGGL((mpc::rb_kernel<RWV, CWV, NT, PERSIST>), dim3(gx), dim3(64 * RWV * CWV), 0, s, p);
+    hipLaunchKernelGGL((mpc::rb_kernel<RWV, CWV, NT>), dim3(3 * p.ntiles), dim3(64 * RWV * CWV), 0, s, p);
     return hipGetLastError();
 }
-// the fused residual block for a stage's padded channel count (0: not fused)
+// the stages (by padded channel count) that have a fused residual block
+constexpr bool rb_fusable(int Cp) { return Cp == 224 || Cp == 128 || Cp == 64 || Cp == 32; }
 bool rb_fused(int Cp) {
     const bool off = mp::env_int("MAGPIE_CODEC_UNFUSED", 0) != 0;  // A/B switch (read per decode): the two-launch blocks
-    return !off && (Cp == 224 || Cp == 128 || Cp == 64 || Cp == 32);
+    return !off && rb_fusable(Cp);
 }
 hipError_t run_rb(const mpc::RbP &p, int Cp, int nchunk, hipStream_t s) {
-    // waves x steps per wave, measured per stage (8 x 32-frame chunks, same box): 64 steps
-    // per wave everywhere but the 32-channel stage (32: 240 vs 273 us); 128 per wave took
-    // 1.2-1.5x longer (one workgroup per CU), 32 per wave 1.3x on 128 / 64 channels
+    // <channel blocks, column waves (CWV), 16-column fragments per wave (NT)>; a tile is
+    // 16 NT CWV - 16 outputs. Measured per stage (codec): 64 steps per wave
+    // everywhere but the 32-channel stage, which is faster at 32; 128 per wave leave one
+    // workgroup per CU and were slower on every stage, 32 slower at 128 / 64 channels
     switch (Cp) {
-        case 224: return launch_rb<7, MP_RB1_CWV, MP_RB1_NT, false>(p, nchunk, s);
-        case 128: return launch_rb<4, MP_RB2_CWV, MP_RB2_NT>(p, nchunk, s);
-        case 64: return launch_rb<2, MP_RB3_CWV, MP_RB3_NT>(p, nchunk, s);
-        case 32: return launch_rb<1, MP_RB4_CWV, MP_RB4_NT>(p, nchunk, s);
+        case 224: return launch_rb<7, 2, 4>(p, nchunk, s);
+        case 128: return launch_rb<4, 2, 4>(p, nchunk, s);
+        case 64: return launch_rb<2, 4, 4>(p, nchunk, s);
+        case 32: return launch_rb<1, 8, 2>(p, nchunk, s);
     }
     return hipErrorInvalidValue;
 }
@@ -1664,8 +1400,8 @@ hipError_t launch_rl(mpc::RlP p, int nchunk, hipStream_t s) {
 }
 hipError_t run_rl(const mpc::RlP &p, int Cp, int nchunk, hipStream_t s) {
     switch (Cp) {
-        case 64: return launch_rl<2, MP_RL_CWV64, MP_RL_NT64>(p, nchunk, s);
-        case 32: return launch_rl<1, MP_RL_CWV32, MP_RL_NT32>(p, nchunk, s);
+        case 64: return launch_rl<2, 4, 4>(p, nchunk, s);  // <channel blocks, column waves, fragments per wave>
+        case 32: return launch_rl<1, 4, 4>(p, nchunk, s);
     }
     return hipErrorInvalidValue;
 }
@@ -1690,13 +1426,21 @@ hipError_t run_conv(const mpc::ConvP &p, int BM, int mode, int nchunk, int nbran
     return launch_conv<32, 128, IN_F16>(p, nchunk, nbranch, s);
 }
 
+// One stage's ConvTranspose; a stage whose residual blocks run fused takes no f16 operands
+template <int CINP, int COUTP, int S, bool AVG, int R>
+hipError_t launch_convt(const mpc::ConvTP &p, bool fused, hipStream_t s) {
+    const dim3 grid((p.nchunk * ((p.Tin + R - 1) / R) * (COUTP / 2) + 255) / 256);
+    auto kernel = mpc::conv_transpose2_kernel<CINP, COUTP, S, AVG, R, true>;
+    if constexpr (rb_fusable(COUTP))  // the 448-channel stage has no fused form: no second instantiation
+        if (fused) kernel = mpc::conv_transpose2_kernel<CINP, COUTP, S, AVG, R, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 // Decode nchunk independent chunks of F frames each (codes [chunk][8][F]).
 int codec_run(mp_codec *c, int nchunk, int F) {
     using namespace mpc;
     hipStream_t s = c->stream;
-    constexpr size_t NCTR = (size_t)NSTAGE * 3 * 16;
-    if (!c->rb_ctr) CHK(hipMalloc((void **)&c->rb_ctr, NCTR * sizeof(int)));
-    CHK(hipMemsetAsync(c->rb_ctr, 0, NCTR * sizeof(int), s));
     // pre-conv with the FSQ dequant in its loader
     {
         ConvP p{};
@@ -1717,30 +1461,15 @@ int codec_run(mp_codec *c, int nchunk, int F) {
         tp.w = c->up_w[i]; tp.bias = c->up_b[i]; tp.out = c->x0; tp.cout_real = C; tp.Coutp = Cp;
         for (int j = 0; j < 3; ++j) { tp.act[j] = c->a16[j]; tp.act_alpha[j] = c->rb_alpha[i][j][0][0]; }
         tp.Tin = T; tp.s = RATE[i]; tp.nchunk = nchunk;
-        // R input steps per thread: 1 on the short early stages (threads), 4 later (re-reads)
-        const int R = i == 0 ? 1 : i == 1 ? 2 : MP_CT_R;
-        const dim3 g2((nchunk * ((T + R - 1) / R) * (Cp / 2) + 255) / 256);
+        // input steps per thread: 1 and 2 on the short early stages (threads), CT_R later
         const bool fused = rb_fused(Cp);
         switch (i) {
-            case 0: hipLaunchKernelGGL((conv_transpose2_kernel<896, 448, 8, false, 1>), g2, dim3(256), 0, s, tp); break;
-            case 1:
-                if (fused) hipLaunchKernelGGL((conv_transpose2_kernel<448, 224, 8, true, 2, false>), g2, dim3(256), 0, s, tp);
-                else hipLaunchKernelGGL((conv_transpose2_kernel<448, 224, 8, true, 2>), g2, dim3(256), 0, s, tp);
-                break;
-            case 2:
-                if (fused) hipLaunchKernelGGL((conv_transpose2_kernel<224, 128, 4, true, MP_CT_R, false>), g2, dim3(256), 0, s, tp);
-                else hipLaunchKernelGGL((conv_transpose2_kernel<224, 128, 4, true, MP_CT_R>), g2, dim3(256), 0, s, tp);
-                break;
-            case 3:
-                if (fused) hipLaunchKernelGGL((conv_transpose2_kernel<128, 64, 2, true, MP_CT_R, false>), g2, dim3(256), 0, s, tp);
-                else hipLaunchKernelGGL((conv_transpose2_kernel<128, 64, 2, true, MP_CT_R>), g2, dim3(256), 0, s, tp);
-                break;
-            default:
-                if (fused) hipLaunchKernelGGL((conv_transpose2_kernel<64, 32, 2, true, MP_CT_R, false>), g2, dim3(256), 0, s, tp);
-                else hipLaunchKernelGGL((conv_transpose2_kernel<64, 32, 2, true, MP_CT_R>), g2, dim3(256), 0, s, tp);
-                break;
+            case 0: CHK((launch_convt<896, 448, 8, false, 1>(tp, fused, s))); break;
+            case 1: CHK((launch_convt<448, 224, 8, true, 2>(tp, fused, s))); break;
+            case 2: CHK((launch_convt<224, 128, 4, true, CT_R>(tp, fused, s))); break;
+            case 3: CHK((launch_convt<128, 64, 2, true, CT_R>(tp, fused, s))); break;
+            default: CHK((launch_convt<64, 32, 2, true, CT_R>(tp, fused, s))); break;
         }
-        CHK(hipGetLastError());
         T *= RATE[i];
         if (fused && rl_fused(Cp)) {
             RlP lp{};
@@ -1773,7 +1502,6 @@ int codec_run(mp_codec *c, int nchunk, int F) {
                 }
                 rp.nsnake = C / 2; rp.creal = C; rp.T = T; rp.dil = DIL[k];
                 rp.ts = (c->ts_dev && i == c->ts_stage && k == c->ts_block) ? c->ts_dev : nullptr;
-                rp.ctr = c->rb_ctr + (i * 3 + k) * 16;  // 64 B apart
                 CHK(run_rb(rp, Cp, nchunk, s));
             }
             continue;
@@ -1913,7 +1641,6 @@ void mp_hip_codec_free(mp_codec *c) {
     if (c->h_audio_pin) hipHostFree(c->h_audio_pin);
     for (void *p : c->weight_allocs) hipFree(p);
     if (c->ts_dev) hipFree(c->ts_dev);
-    if (c->rb_ctr) hipFree(c->rb_ctr);
     float *bufs[5] = {c->x_pre, c->x0, c->brb[0], c->brb[1], c->brb[2]};
     for (float *b : bufs) if (b) hipFree(b);
     for (int j = 0; j < 3; ++j) {

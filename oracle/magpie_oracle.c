@@ -1013,7 +1013,7 @@ static void half_snake(const snake_t *s, const float *x, float *y, int C, int T)
 // magpie_codec_build_causal_conv1d (nano-codec.cpp:429-466): left pad (k-1)*dil.
 // f16=1: operands rounded to fp16 as ggml_conv_1d's F16 im2col does (A.7).
 // resid (nullable): the accumulators start at resid[o][t] instead of 0, so y = (resid + sum)
-// + b: the rounding order of this build's residual convs (MP_RESINIT, mp_codec.hip), the
+// + b: the rounding order of this build's residual convs (mp_codec.hip), the
 // oracle's codec "resinit" mode; the reference's is (sum + b) + resid (nano-codec.cpp:454-462,
 // 568-599), the default.
 static void causal_conv_r(const conv_t *cv, const float *x, float *y, int T, int dil, int f16, const float *resid);

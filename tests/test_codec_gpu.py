@@ -103,7 +103,7 @@ def test_reslayer_launch_equals_block_launches(gpu_codec, monkeypatch, F, mode):
 
 def test_codec_matches_oracle_resinit_order(gpu_codec, cpu_codec):
     """This build's residual convs round as (x + sum) + b (accumulators initialised with the
-    residual, MP_RESINIT); the reference's order is (sum + b) + x (nano-codec.cpp:454-462,
+    residual, bias after); the reference's order is (sum + b) + x (nano-codec.cpp:454-462,
     568-599). The oracle's resinit mode restates the build's order. With plain f32 operands the
     two orders differ at f32 rounding (3e-7, tests/test_oracle_cpu.py); with ggml's f16 im2col
     operands every ulp moved in a residual can move the next conv's f16 operand, and the two
