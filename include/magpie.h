@@ -201,6 +201,13 @@ std::vector<int32_t> magpie_synthesize_codes_graph_reuse(magpie_context *ctx, co
 bool magpie_synthesize_codes_batch(magpie_context *ctx, const int32_t *const *tokens, const int *n_tokens, int B,
                                    std::vector<int32_t> *out);
 
+// Added: any number N of independent utterances through `slots` decode slots
+// (1..mp_hip_max_batch), a finished slot refilled with the next utterance between two
+// frames (mp_hip_decode_queue); out[i] receives utterance i's codes. Temperature, top_k,
+// seed and speaker come from the context, as for the batch call. Returns false on failure.
+bool magpie_synthesize_codes_queue(magpie_context *ctx, const int32_t *const *tokens, const int *n_tokens, int N,
+                                   int slots, std::vector<int32_t> *out);
+
 // ---- nano-codec (magpie.h:746-759)
 magpie_codec *magpie_codec_init(const char *codec_path);
 magpie_codec *magpie_codec_init_with_backend(const char *codec_path, magpie_backend_type backend);

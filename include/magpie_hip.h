@@ -155,6 +155,35 @@ int mp_hip_begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
  * [B][max_dec_steps][8] frame-major (BOS excluded, as magpie.cpp:4416-4420);
  * n_frames: [B]. */
 int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames);
+/* Continuous batching: N utterances through `slots` decode slots (1..mp_hip_max_batch), a
+ * finished slot refilled from the queue between two graph replays instead of recomputing
+ * its last frame until the batch's longest utterance stops. No reference counterpart (the
+ * reference decodes one utterance at a time).
+ * tokens [N][tmax] / n_tokens [N] / speaker [N] as for mp_hip_begin_batch, checked for every
+ * utterance before anything runs. `next` returns the index of the next utterance to run,
+ * or -1 once the queue is drained (NULL: 0, 1, ..., N-1 in order); an index is run once.
+ * The first `slots` claimed utterances start as an ordinary batch whose text stride is
+ * tmax; at every poll-th iteration (poll <= 0: 8, mp_hip_decode's) the host reads the
+ * slots' done flags and, for each finished slot in slot order, hands its codes to `done`,
+ * then installs the next claimed utterance, whose preamble ran on a side stream (one
+ * utterance is always staged ahead; the decode stream waits for it in-stream). The
+ * iteration count is therefore a function of the frame counts, slots, poll and the claim
+ * order only. Utterance i draws from stream params->stream_base + i and, with the device's
+ * SA cache type and XA form, produces the codes of a single run (the XA form is chosen
+ * once from tmax). params->trace_hidden is refused (MP_ERR_ARG). `done` receives each
+ * utterance once; codes is valid during the call. stats may be NULL. */
+typedef int (*mp_next_cb)(void *user);
+typedef void (*mp_done_cb)(int utt, const int32_t *codes /*[n_frames][8]*/, int n_frames, void *user);
+typedef struct mp_queue_stats {
+    int iterations;              /* decode iterations (graph replays) executed */
+    int slots;                   /* slots in use: min(slots, utterances claimed at the start) */
+    int refills;                 /* slot installs after the start */
+    long long useful_slot_iters; /* frames produced over all utterances */
+    double decode_ms;            /* device time of the whole loop (hipEvents) */
+} mp_queue_stats;
+int mp_hip_decode_queue(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int N,
+                        int tmax, int slots, int poll, const mp_params *params, mp_next_cb next, mp_done_cb done,
+                        void *user, mp_queue_stats *stats);
 /* decoder hidden state after every step (BOS first): [B][max_dec_steps+1][768];
  * requires params.trace_hidden. */
 int mp_hip_get_trace(mp_dev *dev, float *hidden);

@@ -131,6 +131,32 @@ bool magpie_synthesize_codes_batch(magpie_context *ctx, const int32_t *const *to
     return true;
 }
 
+bool magpie_synthesize_codes_queue(magpie_context *ctx, const int32_t *const *tokens, const int *n_tokens, int N,
+                                   int slots, std::vector<int32_t> *out) {
+    if (!ctx || !ctx->model.dev || !tokens || !n_tokens || N < 1 || !out) return false;
+    int tmax = 0;
+    for (int i = 0; i < N; ++i) {
+        if (!tokens[i] || n_tokens[i] <= 0) return false;
+        tmax = std::max(tmax, n_tokens[i]);
+    }
+    std::vector<int32_t> tok((size_t)N * tmax, 0), nt(N), spk(N, ctx->speaker_id);
+    for (int i = 0; i < N; ++i) {
+        nt[i] = n_tokens[i];
+        std::copy(tokens[i], tokens[i] + n_tokens[i], tok.begin() + (size_t)i * tmax);
+    }
+    const mp_params p = params_of(ctx);
+    for (int i = 0; i < N; ++i) out[i].clear();
+    auto on_done = [](int utt, const int32_t *codes, int n_frames, void *user) {
+        ((std::vector<int32_t> *)user)[utt].assign(codes, codes + (size_t)n_frames * 8);
+    };
+    if (mp_hip_decode_queue(ctx->model.dev, tok.data(), nt.data(), spk.data(), N, tmax, slots, 0, &p, nullptr, on_done,
+                            out, nullptr) != MP_OK) {
+        fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));
+        return false;
+    }
+    return true;
+}
+
 // magpie_synthesize_codes_graph_reuse (magpie.cpp:4063-4432): empty on failure.
 std::vector<int32_t> magpie_synthesize_codes_graph_reuse(magpie_context *ctx, const int32_t *tokens, int n_tokens) {
     if (!ctx || !tokens || n_tokens <= 0) {

@@ -498,6 +498,112 @@ hipError_t op_embed(const EmbP &p, int NB, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- slot refill
+// Makes slot b a fresh utterance from a staged single-utterance preamble (InstallP), in one
+// launch on the decode stream between two graph replays. A memory-bound copy: the work is
+// cut into 16-byte units, per layer [kc rows | vc rows | xak | xav | kp | vp] and behind the
+// layers the slot's codes_out rows (zeroed); every thread moves INSTALL_ILP units per round,
+// loads first, then stores, the grid striding over the rest. Workgroup 0 also writes the
+// slot's scalars and x[b], the BOS frame's embedding at position CTX, element by element in
+// embed_kernel's order (codebooks 0..7 in sequence, / 8, + position): the same bits.
+// Rows past the copied ones keep the previous tenant's bytes: attention stops at pos,
+// cross-attention at T[b].
+constexpr int INSTALL_ILP = 4;
+struct InstallShape {
+    unsigned cu, xu, pu, per, copy_total, total;  // units: cache, xak, kp per layer; a layer; all layers; + zeroed
+};
+__host__ __device__ inline InstallShape install_shape(const InstallP &p) {
+    InstallShape s;
+    s.cu = (unsigned)CTX * p.cache_row16;
+    s.xu = (unsigned)p.T * (DXA * 4 / 16);
+    s.pu = p.kp ? (unsigned)p.T * (D * 4 / 16) : 0u;
+    s.per = 2 * (s.cu + s.xu + s.pu);
+    s.copy_total = s.per * (unsigned)p.nlayers;
+    s.total = s.copy_total + (unsigned)p.max_steps * (NCB * 4 / 16);
+    return s;
+}
+__global__ __launch_bounds__(MP_BLOCK) void slot_install_kernel(InstallP p) {
+    const InstallShape sh = install_shape(p);
+    const unsigned stride = gridDim.x * MP_BLOCK;
+    const size_t slot_l = (size_t)p.b * p.nlayers;
+    for (unsigned u0 = blockIdx.x * MP_BLOCK + threadIdx.x; u0 < sh.total; u0 += stride * INSTALL_ILP) {
+        uint4 v[INSTALL_ILP];
+        uint4 *dst[INSTALL_ILP];
+#pragma unroll
+        for (int i = 0; i < INSTALL_ILP; ++i) {
+            const unsigned u = u0 + i * stride;
+            dst[i] = nullptr;
+            v[i] = make_uint4(0u, 0u, 0u, 0u);
+            if (u >= sh.total) continue;
+            if (u >= sh.copy_total) {  // the slot's output rows: zeroed
+                dst[i] = (uint4 *)(p.codes_out + (size_t)p.b * p.max_steps * NCB) + (u - sh.copy_total);
+                continue;
+            }
+            const unsigned l = u / sh.per;
+            unsigned r = u % sh.per;
+            const uint4 *src;
+            if (r < 2 * sh.cu) {
+                const bool second = r >= sh.cu;
+                r -= second ? sh.cu : 0u;
+                src = (second ? p.svc : p.skc) + (size_t)l * p.smax_seq * p.cache_row16 + r;
+                dst[i] = (second ? p.vc : p.kc) + (slot_l + l) * p.max_seq * p.cache_row16 + r;
+            } else if ((r -= 2 * sh.cu) < 2 * sh.xu) {
+                const bool second = r >= sh.xu;
+                r -= second ? sh.xu : 0u;
+                src = (second ? p.sxav : p.sxak) + (size_t)l * sh.xu + r;
+                dst[i] = (second ? p.xav : p.xak) + (slot_l + l) * p.Tmax * (DXA * 4 / 16) + r;
+            } else {
+                r -= 2 * sh.xu;
+                const bool second = r >= sh.pu;
+                r -= second ? sh.pu : 0u;
+                src = (second ? p.svp : p.skp) + (size_t)l * sh.pu + r;
+                dst[i] = (second ? p.vp : p.kp) + (slot_l + l) * p.Tmax * (D * 4 / 16) + r;
+            }
+            v[i] = *src;
+        }
+#pragma unroll
+        for (int i = 0; i < INSTALL_ILP; ++i)
+            if (dst[i]) *dst[i] = v[i];
+    }
+    if (blockIdx.x != 0) return;
+    const int b = p.b, tid = threadIdx.x;
+    if (tid < NCB) p.codes_prev[b * NCB + tid] = p.audio_bos;
+    if (tid == 0) {
+        p.Tn[b] = p.T;
+        p.spkn[b] = p.spk;
+        p.pos[b] = CTX;
+        p.step[b] = 0;
+        p.done[b] = 0;
+        p.nframes[b] = 0;
+        p.argeos[b] = 0;
+        p.cfg->stream[b] = p.stream;
+        atomicSub(p.ndone, 1);  // the slot counted as done (lt_finalize_kernel's atomicAdd)
+    }
+    for (int k = tid; k < D; k += MP_BLOCK) {
+        float s = p.emb[((size_t)0 * VCB + p.audio_bos) * D + k];
+#pragma unroll
+        for (int cb = 1; cb < NCB; ++cb) s = s + p.emb[((size_t)cb * VCB + p.audio_bos) * D + k];
+        p.x[(size_t)b * D + k] = s * 0.125f + p.pos_emb[(size_t)CTX * D + k];
+    }
+}
+hipError_t op_slot_install(const InstallP &p, hipStream_t s) {
+    if (!p.skc || !p.svc || !p.kc || !p.vc || !p.sxak || !p.sxav || !p.xak || !p.xav || (p.kp && (!p.vp || !p.skp || !p.svp)) ||
+        !p.Tn || !p.spkn || !p.pos || !p.step || !p.done || !p.nframes || !p.argeos || !p.codes_prev || !p.codes_out ||
+        !p.ndone || !p.cfg || !p.emb || !p.pos_emb || !p.x)
+        return hipErrorInvalidValue;
+    if (p.b < 0 || p.b >= 16 || p.nlayers < 1 || p.T < 1 || p.T > p.Tmax || p.Tmax > TMAX_LIMIT || p.smax_seq < CTX ||
+        p.max_seq < CTX || (p.cache_row16 != D * 4 / 16 && p.cache_row16 != D * 2 / 16) || p.max_steps < 1 ||
+        p.audio_bos < 0 || p.audio_bos >= VCB)
+        return hipErrorInvalidValue;
+    const InstallShape sh = install_shape(p);
+    // a grid sized to the bytes: one round of INSTALL_ILP units per thread, at most 2048
+    // workgroups (256 CUs x 8), the rest grid-strided
+    const unsigned per_block = MP_BLOCK * INSTALL_ILP;
+    const unsigned grid = std::min(2048u, (sh.total + per_block - 1) / per_block);
+    mp::launch(slot_install_kernel, dim3(grid), dim3(MP_BLOCK), 0, s, p);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- LT FFN
 // FFN up + GELU + FFN down of the local transformer in one launch
 // (magpie.cpp:983-992): workgroup p owns hidden units j in [16p, 16p+16). Its

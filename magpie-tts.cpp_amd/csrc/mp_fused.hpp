@@ -25,7 +25,7 @@ namespace mp {
 // and the first i with u < cumsum_i (fallback: the k-th). Radix-select finds the
 // k-th key, a ballot compaction gathers the k candidates into LDS, a counting rank
 // orders them, lane 0 runs the two sequential float loops. scratch: 2*VCB floats.
-// `stream` is the batch slot; the draw stream is cfg->stream_base + slot.
+// `stream` is the batch slot; the draw stream is the slot's entry of cfg->stream.
 constexpr int PICK_R = (VCB + 63) / 64;  // logits per lane
 __device__ __forceinline__ void load_logits(const float *lg, float (&lv)[PICK_R]) {
     const int lane = threadIdx.x & 63;
@@ -145,7 +145,7 @@ __device__ inline int wave_pick_v(float (&lv)[PICK_R], bool forbid_eos, int audi
     if (lane == 0) {
         float sum = 0.f;
         for (int i = 0; i < k; ++i) sum += sv[i];
-        const float u = mp_uniform(smp.cfg->seed, smp.cfg->stream_base + stream, step, cb);
+        const float u = mp_uniform(smp.cfg->seed, smp.cfg->stream[stream], step, cb);
         float cum = 0.f;
         code = si[k - 1];
         for (int i = 0; i < k; ++i) {

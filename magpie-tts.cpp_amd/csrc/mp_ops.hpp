@@ -52,6 +52,7 @@ hipError_t op_xa(const XaP &, int, hipStream_t);
 hipError_t op_xa_q8(const XaQ8P &, int, hipStream_t);
 hipError_t op_finalize(const FinP &, int, hipStream_t);
 hipError_t op_embed(const EmbP &, int, hipStream_t);
+hipError_t op_slot_install(const InstallP &, hipStream_t);  // between two replays, never in the iteration's list
 hipError_t op_lt_kvo(const GemvP &, int, hipStream_t);
 hipError_t op_lt_pick(const GemvP &, int, hipStream_t);
 hipError_t op_lt_ffn(const LtFfnP &, int, hipStream_t);

@@ -95,7 +95,10 @@ struct SmpCfg {                // device-resident, so a captured graph serves an
     float temperature;
     int top_k;                 // 1..VCB
     unsigned long long seed;
-    int stream_base;           // draw stream of slot b = stream_base + b
+    int stream_base;           // the batch's first draw stream (mp_params::stream_base)
+    int stream[16];            // draw stream of slot b: stream_base + b from mp_hip_begin_batch; a slot
+                               // refilled by mp_hip_decode_queue carries its utterance's
+                               // (slot_install_kernel), so a draw follows the utterance, not the slot
 };
 struct Sampling {
     int on;                    // temperature >= 0.01 (baked into the captured graph)
@@ -178,6 +181,29 @@ struct EmbP {
     const float *pos_emb;
     const int *pos;        // [B]
     float *x;              // [B][768]
+};
+
+// Slot refill (slot_install_kernel, mp_hip_decode_queue): one launch between two graph
+// replays makes slot b a fresh utterance from a staged single-utterance preamble. Every
+// copy moves 16-byte units (all offsets and row sizes are multiples of 16 bytes).
+struct InstallP {
+    // SA cache: staged [L][smax_seq][768] -> pool [NB][L][max_seq][768], rows 0..CTX-1 of
+    // every layer; cache_row16 = 16-byte units per row (768 elements: 192 f32, 96 bf16)
+    const uint4 *skc, *svc;
+    uint4 *kc, *vc;
+    int nlayers, smax_seq, max_seq, cache_row16;
+    // cross-attention: staged stride T rows per layer -> pool stride Tmax; T rows of 128 f32
+    // (xak, xav) and, in the reassociated form, of 768 f32 (kp, vp; null otherwise)
+    const uint4 *sxak, *sxav, *skp, *svp;
+    uint4 *xak, *xav, *kp, *vp;
+    int T, Tmax;
+    // slot state
+    int b, spk, stream, audio_bos, max_steps;
+    int *Tn, *spkn, *pos, *step, *done, *nframes, *argeos, *codes_prev, *codes_out, *ndone;
+    SmpCfg *cfg;
+    // x[b] = the BOS frame's embedding at position CTX (embed_kernel's arithmetic)
+    const float *emb, *pos_emb;
+    float *x;
 };
 
 // splitmix64 finaliser

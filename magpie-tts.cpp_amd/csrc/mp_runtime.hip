@@ -160,6 +160,32 @@ struct LtIo {
 
 }  // namespace mp
 
+// The preamble's buffers and stream: the batch's own (mp_hip_begin_batch: batch_ws) or a
+// staging workspace of the slot pool (mp_hip_decode_queue), which runs one utterance's
+// preamble on a side stream while the batch keeps decoding. The outputs' strides follow
+// from Tmax (xak / xav / kp / vp rows per layer) and max_seq (kc / vc rows per layer).
+struct PreWs {
+    const int32_t *tok, *T, *spk;  // device [NB][Tmax] token ids, [NB] lengths, [NB] speakers
+    int NB, Tmax, max_seq, kv16;
+    bool xa_direct;                // no K' / V' (kp, vp unused)
+    float *pX, *pH, *pQKV, *pATT, *pF, *pXQ, *pXAO, *gpart, *enc_out;  // scratch
+    float *xak, *xav, *kp, *vp, *kc, *vc;                              // outputs
+    hipStream_t stream;
+};
+// A staging workspace of the slot pool: one utterance's preamble (NB = 1) of up to tmax
+// tokens, run on the pool's side stream; `ready` is recorded behind the preamble,
+// `installed` behind the slot_install_kernel launch that read it (the workspace is reused
+// only after that event has completed).
+struct StageWs {
+    PreWs w{};
+    std::vector<void *> allocs;
+    int32_t *tok = nullptr, *T = nullptr, *spk = nullptr;  // device
+    int32_t *h = nullptr;                                  // pinned [tmax + 2]: tokens, length, speaker
+    hipEvent_t ready = nullptr, installed = nullptr;
+    bool install_pending = false;
+    int utt = -1, n = 0;
+};
+
 struct mp_dev {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -221,6 +247,12 @@ struct mp_dev {
     size_t q8dump_slot = 0;
     int q8dump_cap = 0, q8dump_n = 0;
     std::vector<int> q8dump_index;
+    // slot pool (mp_hip_decode_queue): two staging workspaces and the side stream their
+    // preambles run on, kept between calls while their shape (tmax, cache type, XA form) holds
+    StageWs stage[2];
+    hipStream_t side = nullptr;
+    int stage_tmax = 0, stage_kv16 = 0;
+    bool stage_direct = false;
 };
 
 namespace {
@@ -263,6 +295,19 @@ void free_batch(mp_dev *dev) {
     dev->q8dump = nullptr;  // (one of allocs)
     dev->q8dump_cap = dev->q8dump_n = 0;
     dev->q8dump_index.clear();
+}
+
+// the slot pool's staging workspaces (the side stream stays until mp_hip_free)
+void free_stage(mp_dev *dev) {
+    if (dev->side) hipStreamSynchronize(dev->side);
+    for (StageWs &s : dev->stage) {
+        for (void *p : s.allocs) hipFree(p);
+        if (s.h) hipHostFree(s.h);
+        if (s.ready) hipEventDestroy(s.ready);
+        if (s.installed) hipEventDestroy(s.installed);
+        s = StageWs{};
+    }
+    dev->stage_tmax = 0;
 }
 
 // MAGPIE_Q8DUMP: give a Q8_0 decode GEMM launch its dump slot and index record
@@ -1427,16 +1472,22 @@ static int run_encoder(mp_dev *dev, const EncWs &w, hipStream_t s) {
     return MP_OK;
 }
 
-int run_preamble(mp_dev *dev) {
+static PreWs batch_ws(const mp_dev *dev) {
+    return PreWs{dev->tok, dev->T, dev->spk, dev->NB, dev->Tmax, dev->max_seq, dev->kv16, dev->xa_direct,
+                 dev->pX, dev->pH, dev->pQKV, dev->pATT, dev->pF, dev->pXQ, dev->pXAO, dev->gpart, dev->enc_out,
+                 dev->xak, dev->xav, dev->kp, dev->vp, dev->kc, dev->vc, dev->stream};
+}
+
+int run_preamble(mp_dev *dev, const PreWs &w) {
     using namespace mp;
     const Model &m = dev->m;
-    const int NB = dev->NB, Tmax = dev->Tmax, L = m.dec_layers;
-    hipStream_t s = dev->stream;
+    const int NB = w.NB, Tmax = w.Tmax, L = m.dec_layers;
+    hipStream_t s = w.stream;
     const int Me = NB * Tmax;
-    auto pre_gemm = [&](GemmP gp, int epi, hipStream_t st) { return preamble_gemm(m, dev->gpart, gp, epi, st); };
+    auto pre_gemm = [&](GemmP gp, int epi, hipStream_t st) { return preamble_gemm(m, w.gpart, gp, epi, st); };
     {
-        const EncWs w{dev->tok, dev->T, NB, Tmax, dev->pX, dev->pH, dev->pQKV, dev->pATT, dev->pF, dev->gpart, dev->enc_out};
-        if (int rc = run_encoder(dev, w, s)) return rc;
+        const EncWs e{w.tok, w.T, NB, Tmax, w.pX, w.pH, w.pQKV, w.pATT, w.pF, w.gpart, w.enc_out};
+        if (int rc = run_encoder(dev, e, s)) return rc;
     }
     // --- cross-attention K/V per layer (1663-1711): LN(encoder output) with each layer's
     //     norm_xmem, then kv_net. Layers whose tensors sit at one stride in the arena (the
@@ -1461,11 +1512,11 @@ int run_preamble(mp_dev *dev) {
                       : 1;
     for (int l0 = 0; l0 < L; l0 += G) {
         const int g = std::min(G, L - l0);
-        HIPCHK(pre_ln_rows_multi(dev->enc_out, 768, m.dec[l0].norm_xmem, s_norm, dev->pF, 768, (long long)Me * 768, Me, g,
+        HIPCHK(pre_ln_rows_multi(w.enc_out, 768, m.dec[l0].norm_xmem, s_norm, w.pF, 768, (long long)Me * 768, Me, g,
                                  m.eps, s));
         GemmP gp{};
-        gp.A = dev->pF; gp.lda = 768; gp.W = m.dec[l0].xkv; gp.Wq = m.dec[l0].xkv8.q; gp.Wd = m.dec[l0].xkv8.d; gp.M = Me; gp.N = 256; gp.K = 768; gp.rows_per_utt = Tmax;
-        gp.T = dev->T; gp.xak = dev->xak; gp.xav = dev->xav; gp.layer = l0; gp.nlayers = L; gp.Tmax = Tmax;
+        gp.A = w.pF; gp.lda = 768; gp.W = m.dec[l0].xkv; gp.Wq = m.dec[l0].xkv8.q; gp.Wd = m.dec[l0].xkv8.d; gp.M = Me; gp.N = 256; gp.K = 768; gp.rows_per_utt = Tmax;
+        gp.T = w.T; gp.xak = w.xak; gp.xav = w.xav; gp.layer = l0; gp.nlayers = L; gp.Tmax = Tmax;
         gp.nbatch = g; gp.wmod = g; gp.sA = (long long)Me * 768; gp.sW = s_xkv; gp.sWq = s_xkvq; gp.sWd = s_xkvd;
         HIPCHK(pre_gemm(gp, GE_XAKV, s));
     }
@@ -1476,74 +1527,74 @@ int run_preamble(mp_dev *dev) {
     bool any_xq8 = false;
     for (int l = 0; l < L; ++l) any_xq8 |= (bool)m.dec[l].xq8;
     const long long s_xo = stride_of([&](int l) { return m.dec[l].xo; });
-    if (!dev->xa_direct && !any_xq8 && s_xo >= 0) {
+    if (!w.xa_direct && !any_xq8 && s_xo >= 0) {
         GemmP gp{};
-        gp.A = dev->xak; gp.lda = 128; gp.W = m.xq_t[0]; gp.C = dev->kp; gp.ldc = 768;
+        gp.A = w.xak; gp.lda = 128; gp.W = m.xq_t[0]; gp.C = w.kp; gp.ldc = 768;
         gp.M = Tmax; gp.N = 768; gp.K = 128; gp.rows_per_utt = Tmax;
         gp.xround = -1;
         gp.nbatch = NB * L; gp.wmod = L; gp.sA = (long long)Tmax * 128; gp.sW = 768 * 128; gp.sC = (long long)Tmax * 768;
         HIPCHK(pre_gemm(gp, GE_STORE, s));
-        gp.A = dev->xav; gp.W = m.dec[0].xo; gp.C = dev->vp; gp.sW = s_xo;
+        gp.A = w.xav; gp.W = m.dec[0].xo; gp.C = w.vp; gp.sW = s_xo;
         HIPCHK(pre_gemm(gp, GE_STORE, s));
     } else {
         for (int b = 0; b < NB; ++b)
             for (int l = 0; l < L; ++l) {
-                if (m.dec[l].xq8 || dev->xa_direct) continue;
+                if (m.dec[l].xq8 || w.xa_direct) continue;
                 const size_t xo = ((size_t)(b * L + l) * Tmax) * 128, po = ((size_t)(b * L + l) * Tmax) * 768;
                 GemmP gp{};
-                gp.A = dev->xak + xo; gp.lda = 128; gp.W = m.xq_t[l]; gp.C = dev->kp + po; gp.ldc = 768;
+                gp.A = w.xak + xo; gp.lda = 128; gp.W = m.xq_t[l]; gp.C = w.kp + po; gp.ldc = 768;
                 gp.M = Tmax; gp.N = 768; gp.K = 128; gp.rows_per_utt = Tmax;
                 gp.xround = -1;
                 HIPCHK(pre_gemm(gp, GE_STORE, s));
-                gp.A = dev->xav + xo; gp.W = m.dec[l].xo; gp.C = dev->vp + po;
+                gp.A = w.xav + xo; gp.W = m.dec[l].xo; gp.C = w.vp + po;
                 HIPCHK(pre_gemm(gp, GE_STORE, s));
             }
     }
     // --- baked context + 110-frame causal prefill (3991-4060, 4167-4238)
     const int Mc = NB * CTX;
-    HIPCHK(pre_embed_context(dev->spk, NB, m.baked, m.dec_pos, dev->pX, s));
-    HIPCHK(pre_ln_rows(dev->pX, 768, m.dec[0].norm_self, dev->pH, 768, Mc, m.eps, s));
+    HIPCHK(pre_embed_context(w.spk, NB, m.baked, m.dec_pos, w.pX, s));
+    HIPCHK(pre_ln_rows(w.pX, 768, m.dec[0].norm_self, w.pH, 768, Mc, m.eps, s));
     for (int l = 0; l < L; ++l) {
         const DecLayerW &W = m.dec[l];
         GemmP gp{};
-        gp.A = dev->pH; gp.lda = 768; gp.W = W.qkv; gp.Wq = W.qkv8.q; gp.Wd = W.qkv8.d; gp.C = dev->pQKV; gp.ldc = 2304; gp.M = Mc; gp.N = 2304; gp.K = 768;
-        gp.rows_per_utt = CTX; gp.kc = dev->kc; gp.vc = dev->vc; gp.kv16 = dev->kv16; gp.layer = l; gp.nlayers = L;
-        gp.max_seq = dev->max_seq;
+        gp.A = w.pH; gp.lda = 768; gp.W = W.qkv; gp.Wq = W.qkv8.q; gp.Wd = W.qkv8.d; gp.C = w.pQKV; gp.ldc = 2304; gp.M = Mc; gp.N = 2304; gp.K = 768;
+        gp.rows_per_utt = CTX; gp.kc = w.kc; gp.vc = w.vc; gp.kv16 = w.kv16; gp.layer = l; gp.nlayers = L;
+        gp.max_seq = w.max_seq;
         HIPCHK(pre_gemm(gp, GE_QKV_CACHE, s));
         RowAttnP ra{};
-        ra.Q = dev->pQKV; ra.ldq = 2304;
+        ra.Q = w.pQKV; ra.ldq = 2304;
         {   // layer l's rows, offset in cache elements (bf16 elements in MP_KV_BF16 mode)
-            const size_t off = (size_t)l * dev->max_seq * 768;
-            ra.Kb = dev->kv16 ? (const float *)((const unsigned short *)dev->kc + off) : dev->kc + off;
-            ra.Vb = dev->kv16 ? (const float *)((const unsigned short *)dev->vc + off) : dev->vc + off;
+            const size_t off = (size_t)l * w.max_seq * 768;
+            ra.Kb = w.kv16 ? (const float *)((const unsigned short *)w.kc + off) : w.kc + off;
+            ra.Vb = w.kv16 ? (const float *)((const unsigned short *)w.vc + off) : w.vc + off;
         }
-        ra.utt_stride = (size_t)L * dev->max_seq * 768; ra.row_stride = 768; ra.O = dev->pATT; ra.M = Mc;
-        ra.rows_per_utt = CTX; ra.heads = 12; ra.T = dev->T; ra.kv16 = dev->kv16;
+        ra.utt_stride = (size_t)L * w.max_seq * 768; ra.row_stride = 768; ra.O = w.pATT; ra.M = Mc;
+        ra.rows_per_utt = CTX; ra.heads = 12; ra.T = w.T; ra.kv16 = w.kv16;
         HIPCHK(pre_row_attn(ra, s));
         gp = GemmP{};
-        gp.A = dev->pATT; gp.lda = 768; gp.W = W.o; gp.Wq = W.o8.q; gp.Wd = W.o8.d; gp.C = dev->pX; gp.ldc = 768; gp.M = Mc; gp.N = 768; gp.K = 768;
+        gp.A = w.pATT; gp.lda = 768; gp.W = W.o; gp.Wq = W.o8.q; gp.Wd = W.o8.d; gp.C = w.pX; gp.ldc = 768; gp.M = Mc; gp.N = 768; gp.K = 768;
         gp.rows_per_utt = CTX;
-        gp.ln_w = W.norm_xq; gp.ln_out = dev->pH; gp.ln_ld = 768;
+        gp.ln_w = W.norm_xq; gp.ln_out = w.pH; gp.ln_ld = 768;
         HIPCHK(pre_gemm(gp, GE_RESID, s));
         gp = GemmP{};
-        gp.A = dev->pH; gp.lda = 768; gp.W = W.xq; gp.Wq = W.xq8.q; gp.Wd = W.xq8.d; gp.C = dev->pXQ; gp.ldc = 128; gp.M = Mc; gp.N = 128; gp.K = 768;
+        gp.A = w.pH; gp.lda = 768; gp.W = W.xq; gp.Wq = W.xq8.q; gp.Wd = W.xq8.d; gp.C = w.pXQ; gp.ldc = 128; gp.M = Mc; gp.N = 128; gp.K = 768;
         gp.rows_per_utt = CTX;
         HIPCHK(pre_gemm(gp, GE_STORE, s));
-        RowXaP rx{dev->pXQ, dev->xak, dev->xav, l, L, Tmax, CTX, Mc, dev->T, dev->pXAO};
+        RowXaP rx{w.pXQ, w.xak, w.xav, l, L, Tmax, CTX, Mc, w.T, w.pXAO};
         HIPCHK(pre_row_xa(rx, s));
         gp = GemmP{};
-        gp.A = dev->pXAO; gp.lda = 128; gp.W = W.xo; gp.Wq = W.xo8.q; gp.Wd = W.xo8.d; gp.C = dev->pX; gp.ldc = 768; gp.M = Mc; gp.N = 768; gp.K = 128;
+        gp.A = w.pXAO; gp.lda = 128; gp.W = W.xo; gp.Wq = W.xo8.q; gp.Wd = W.xo8.d; gp.C = w.pX; gp.ldc = 768; gp.M = Mc; gp.N = 768; gp.K = 128;
         gp.rows_per_utt = CTX;
-        gp.ln_w = W.norm_ff; gp.ln_out = dev->pH; gp.ln_ld = 768;
+        gp.ln_w = W.norm_ff; gp.ln_out = w.pH; gp.ln_ld = 768;
         HIPCHK(pre_gemm(gp, GE_RESID, s));
         gp = GemmP{};
-        gp.A = dev->pH; gp.lda = 768; gp.W = W.ff1; gp.C = dev->pF; gp.ldc = 3072; gp.M = Mc; gp.N = 3072; gp.K = 768;
+        gp.A = w.pH; gp.lda = 768; gp.W = W.ff1; gp.C = w.pF; gp.ldc = 3072; gp.M = Mc; gp.N = 3072; gp.K = 768;
         gp.rows_per_utt = CTX;
         HIPCHK(pre_gemm(gp, GE_GELU, s));
         gp = GemmP{};
-        gp.A = dev->pF; gp.lda = 3072; gp.W = W.ff2; gp.C = dev->pX; gp.ldc = 768; gp.M = Mc; gp.N = 768; gp.K = 3072;
+        gp.A = w.pF; gp.lda = 3072; gp.W = W.ff2; gp.C = w.pX; gp.ldc = 768; gp.M = Mc; gp.N = 768; gp.K = 3072;
         gp.rows_per_utt = CTX;
-        if (l + 1 < L) { gp.ln_w = m.dec[l + 1].norm_self; gp.ln_out = dev->pH; gp.ln_ld = 768; }
+        if (l + 1 < L) { gp.ln_w = m.dec[l + 1].norm_self; gp.ln_out = w.pH; gp.ln_ld = 768; }
         HIPCHK(pre_gemm(gp, GE_RESID, s));
     }
     return MP_OK;
@@ -1596,6 +1647,7 @@ int mp_hip_load_model_ex(mp_dev *dev, const char *path, int weight_mode) {
         return fail(dev, MP_ERR_ARG, "unknown weight mode");
     HIPCHK(hipSetDevice(dev->device));
     free_batch(dev);
+    free_stage(dev);  // sized for the previous model's layers
     dev->loaded = false;
     dev->m.weight_mode = MP_WEIGHTS_AS_STORED;
     // drop the Q8_0 views of a previous model
@@ -1674,6 +1726,8 @@ void mp_hip_free(mp_dev *dev) {
     hipSetDevice(dev->device);
     if (dev->stream) hipStreamSynchronize(dev->stream);
     free_batch(dev);
+    free_stage(dev);
+    if (dev->side) hipStreamDestroy(dev->side);
     if (dev->m.arena) hipFree(dev->m.arena);
     if (dev->m.lt_ptab) hipFree(dev->m.lt_ptab);
     if (dev->m.lt_qkvtab) hipFree(dev->m.lt_qkvtab);
@@ -1699,17 +1753,24 @@ void mp_hip_free(mp_dev *dev) {
 
 const char *mp_hip_error(mp_dev *dev) { return dev ? dev->err.c_str() : "null mp_dev"; }
 
-int mp_hip_begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int B,
-                       int tmax, const mp_params *params) {
-    if (!dev) return MP_ERR_ARG;
-    if (!dev->loaded) return fail(dev, MP_ERR_STATE, "no model loaded");
-    const int bmax = mp_hip_max_batch(dev);
-    if (!tokens || !n_tokens || !speaker || B < 1 || B > bmax || tmax < 1 || !params)
-        return fail(dev, MP_ERR_ARG, "invalid arguments (B must be 1..mp_hip_max_batch: 8 with f32 weights, 16 in the bf16 / F16 / Q8_0 / Q4_0 modes)");
+// mp_hip_begin_batch's argument checks, shared with mp_hip_decode_queue (which applies them
+// to every utterance of its queue before anything runs): the sampling settings and the
+// frame budget (max_steps receives it) ...
+static int check_params(mp_dev *dev, const mp_params *params, int *max_steps) {
     if (params->temperature >= 0.01f && (params->top_k < 1 || params->top_k > mp::VCB))
         return fail(dev, MP_ERR_ARG, "top_k must be in 1..2024 when sampling");
+    *max_steps = params->max_dec_steps > 0 ? params->max_dec_steps : dev->m.max_dec_steps;
+    if (mp::CTX + *max_steps + 16 > mp::NCH_MAX * mp::SA_CHUNK)
+        return fail(dev, MP_ERR_ARG, "max_dec_steps too large (cache limited to 1024 positions)");
+    if (mp::CTX + *max_steps > dev->m.dec_pos_rows)
+        return fail(dev, MP_ERR_ARG, "max_dec_steps exceeds the decoder position table");
+    return MP_OK;
+}
+// ... and n utterances' lengths, speakers and token ids (Tmax receives the longest text)
+static int check_utterances(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int n,
+                            int tmax, int *Tmax_out) {
     int Tmax = 0;
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < n; ++b) {
         if (n_tokens[b] < 1 || n_tokens[b] > tmax) return fail(dev, MP_ERR_ARG, "n_tokens out of range");
         if (speaker[b] < 0 || speaker[b] >= dev->m.n_spk) return fail(dev, MP_ERR_ARG, "speaker id out of range");
         for (int t = 0; t < n_tokens[b]; ++t)
@@ -1718,11 +1779,23 @@ int mp_hip_begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
         Tmax = std::max(Tmax, (int)n_tokens[b]);
     }
     if (Tmax > mp::TMAX_LIMIT || Tmax > 4096) return fail(dev, MP_ERR_ARG, "too many text tokens");
-    const int max_steps = params->max_dec_steps > 0 ? params->max_dec_steps : dev->m.max_dec_steps;
-    if (mp::CTX + max_steps + 16 > mp::NCH_MAX * mp::SA_CHUNK)
-        return fail(dev, MP_ERR_ARG, "max_dec_steps too large (cache limited to 1024 positions)");
-    if (mp::CTX + max_steps > dev->m.dec_pos_rows)
-        return fail(dev, MP_ERR_ARG, "max_dec_steps exceeds the decoder position table");
+    *Tmax_out = Tmax;
+    return MP_OK;
+}
+
+// mp_hip_begin_batch. pin_tmax > 0 (the slot pool): the batch's text stride is pin_tmax,
+// not its own longest text, so a later utterance of up to pin_tmax tokens fits any slot.
+static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int B,
+                       int tmax, const mp_params *params, int pin_tmax) {
+    if (!dev) return MP_ERR_ARG;
+    if (!dev->loaded) return fail(dev, MP_ERR_STATE, "no model loaded");
+    const int bmax = mp_hip_max_batch(dev);
+    if (!tokens || !n_tokens || !speaker || B < 1 || B > bmax || tmax < 1 || !params)
+        return fail(dev, MP_ERR_ARG, "invalid arguments (B must be 1..mp_hip_max_batch: 8 with f32 weights, 16 in the bf16 / F16 / Q8_0 / Q4_0 modes)");
+    int Tmax = 0, max_steps = 0;
+    if (int rc = check_params(dev, params, &max_steps)) return rc;
+    if (int rc = check_utterances(dev, tokens, n_tokens, speaker, B, tmax, &Tmax)) return rc;
+    if (pin_tmax > 0) Tmax = std::max(Tmax, pin_tmax);
     HIPCHK(hipSetDevice(dev->device));
     const bool trace = params->trace_hidden != 0;
     const bool same = dev->NB > 0 && dev->B == B && dev->Tmax == Tmax && dev->max_steps == max_steps &&
@@ -1747,16 +1820,22 @@ int mp_hip_begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
     HIPCHK(hipMemcpyAsync(dev->T, h_T.data(), NB * 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(dev->spk, h_spk.data(), NB * 4, hipMemcpyHostToDevice, dev->stream));
     {   // sampling settings live on the device: the captured graph serves any of them
-        mp::SmpCfg cfg{params->temperature, params->top_k, (unsigned long long)params->seed, params->stream_base};
+        mp::SmpCfg cfg{params->temperature, params->top_k, (unsigned long long)params->seed, params->stream_base, {}};
+        for (int b = 0; b < 16; ++b) cfg.stream[b] = params->stream_base + b;
         HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
         HIPCHK(hipMemsetAsync(dev->argeos, 0, NB * 4, dev->stream));
     }
-    if (int rc = run_preamble(dev)) return rc;
+    if (int rc = run_preamble(dev, batch_ws(dev))) return rc;
     HIPCHK(hipStreamSynchronize(dev->stream));
     dev->timing = mp_timing{};
     dev->timing.preamble_ms = ms_since(t0);
     dev->batch_ready = true;
     return MP_OK;
+}
+
+int mp_hip_begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int B,
+                       int tmax, const mp_params *params) {
+    return begin_batch(dev, tokens, n_tokens, speaker, B, tmax, params, 0);
 }
 
 // magpie_encode_text (magpie.cpp:2284-2374) on its own: the text encoder of one
@@ -1872,18 +1951,21 @@ int launch_iteration(mp_dev *dev, hipStream_t s = nullptr) {
 
 // An in-launch hand-off that gave up (EPI_RESID_XA's bounded sweep) poisons its
 // output and raises ndone[2]: report it instead of returning those codes.
-static int check_handoff(mp_dev *dev) {
-    int nd[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpy(nd, dev->ndone, sizeof nd, hipMemcpyDeviceToHost));
-    if (nd[2]) {
+static int handoff_bits(mp_dev *dev, int bits) {  // ndone[2] as read by the caller
+    if (bits) {
         std::string what;
-        if (nd[2] & mp::HX_ERR_XA) what += " O-projection -> cross-attention";
-        if (nd[2] & mp::HX_ERR_SA) what += std::string(what.empty() ? "" : ",") + " QKV -> self-attention";
-        if (nd[2] & mp::HX_ERR_LT) what += std::string(what.empty() ? "" : ",") + " LT FFN partial sums";
-        if (nd[2] & mp::HX_ERR_KS) what += std::string(what.empty() ? "" : ",") + " split-K partial tiles";
+        if (bits & mp::HX_ERR_XA) what += " O-projection -> cross-attention";
+        if (bits & mp::HX_ERR_SA) what += std::string(what.empty() ? "" : ",") + " QKV -> self-attention";
+        if (bits & mp::HX_ERR_LT) what += std::string(what.empty() ? "" : ",") + " LT FFN partial sums";
+        if (bits & mp::HX_ERR_KS) what += std::string(what.empty() ? "" : ",") + " split-K partial tiles";
         return fail(dev, MP_ERR_HIP, "in-launch hand-off timed out:" + what);
     }
     return MP_OK;
+}
+static int check_handoff(mp_dev *dev) {
+    int nd[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(nd, dev->ndone, sizeof nd, hipMemcpyDeviceToHost));
+    return handoff_bits(dev, nd[2]);
 }
 
 int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames) {
@@ -1930,6 +2012,262 @@ int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames) {
     dev->timing.frames_total = total;
     dev->timing.iterations = it;
     return MP_OK;
+}
+
+// ---------------------------------------------------------------- slot pool
+// the decode reads K' / V' (reassociated XA): not in the direct form, nor in a layer whose
+// q_net / o_net are Q8_0 (every layer of the converter's Q8_0 files)
+static bool batch_reads_kp(const mp_dev *dev) {
+    if (!dev->kp) return false;
+    for (const mp::DecLayerW &W : dev->m.dec)
+        if (!W.xq8) return true;
+    return false;
+}
+// The pool's two staging workspaces: one utterance (NB = 1) of up to tmax tokens each, in
+// the current batch's SA cache type and XA form; the cache holds the CTX prefill rows in
+// whole SA chunks. Kept on the mp_dev while that shape holds.
+static int ensure_stage(mp_dev *dev, int tmax) {
+    if (dev->stage_tmax == tmax && dev->stage_kv16 == dev->kv16 && dev->stage_direct == dev->xa_direct) return MP_OK;
+    free_stage(dev);
+    if (!dev->side) HIPCHK(hipStreamCreateWithFlags(&dev->side, hipStreamNonBlocking));
+    const size_t L = dev->m.dec_layers, D = 768, T = tmax, rows = std::max(tmax, (int)mp::CTX);
+    const int smax_seq = (mp::CTX + mp::SA_CHUNK - 1) / mp::SA_CHUNK * mp::SA_CHUNK;
+    size_t gcap = enc_gpart_elems(T);
+    auto need = [&](size_t M, int N, int K) { gcap = std::max(gcap, (size_t)mp::gemm_splits_max(K) * M * N); };
+    need(mp::CTX, 2304, 768); need(mp::CTX, 3072, 768); need(mp::CTX, 768, 3072); need(mp::CTX, 768, 768);
+    need(T, 256 * (int)L, 768);
+    for (StageWs &s : dev->stage) {
+        auto al = [&](auto **p, size_t n) -> int {  // n 4-byte elements
+            void *v = nullptr;
+            HIPCHK(hipMalloc(&v, n * 4 + 256));
+            s.allocs.push_back(v);
+            *p = (std::remove_reference_t<decltype(**p)> *)v;
+            return MP_OK;
+        };
+        PreWs &w = s.w;
+        int rc = MP_OK;
+        const size_t kvn = L * smax_seq * D / (dev->kv16 ? 2 : 1);
+        if ((rc = al(&s.tok, T)) || (rc = al(&s.T, 1)) || (rc = al(&s.spk, 1)) || (rc = al(&w.pX, rows * D)) ||
+            (rc = al(&w.pH, rows * D)) || (rc = al(&w.pQKV, rows * 3 * D)) || (rc = al(&w.pATT, rows * D)) ||
+            (rc = al(&w.pF, rows * 3072)) || (rc = al(&w.pXQ, rows * 128)) || (rc = al(&w.pXAO, rows * 128)) ||
+            (rc = al(&w.gpart, gcap)) || (rc = al(&w.enc_out, T * D)) || (rc = al(&w.xak, L * T * 128)) ||
+            (rc = al(&w.xav, L * T * 128)) || (rc = al(&w.kc, kvn)) || (rc = al(&w.vc, kvn)) ||
+            (batch_reads_kp(dev) && ((rc = al(&w.kp, L * T * D)) || (rc = al(&w.vp, L * T * D))))) {
+            free_stage(dev);
+            return rc;
+        }
+        w.tok = s.tok; w.T = s.T; w.spk = s.spk;
+        w.NB = 1; w.Tmax = tmax; w.max_seq = smax_seq; w.kv16 = dev->kv16; w.xa_direct = dev->xa_direct;
+        w.stream = dev->side;
+        if (hipHostMalloc((void **)&s.h, (T + 2) * 4, 0) != hipSuccess ||
+            hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&s.installed, hipEventDisableTiming) != hipSuccess) {
+            free_stage(dev);
+            return fail(dev, MP_ERR_HIP, "slot pool: staging workspace allocation failed");
+        }
+    }
+    dev->stage_tmax = tmax;
+    dev->stage_kv16 = dev->kv16;
+    dev->stage_direct = dev->xa_direct;
+    return MP_OK;
+}
+
+// One run of the pool (mp_hip_decode_queue, which checks the arguments and cleans up)
+struct PoolRun {
+    const int32_t *tokens, *n_tokens, *speaker;
+    int N, tmax, slots, poll;
+    mp_params params;
+    mp_next_cb next;
+    mp_done_cb done;
+    void *user;
+    int seq = 0;
+    bool drained = false;
+    std::vector<char> claimed;
+    int32_t *h = nullptr;  // pinned: [ndone 4 | done 16 | nframes 16 | codes max_steps x 8]
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    mp_queue_stats st{};
+};
+// the next utterance to run (-1: drained; out: MP_OK or an error)
+static int pool_claim(mp_dev *dev, PoolRun &r, int *utt) {
+    *utt = -1;
+    if (r.drained) return MP_OK;
+    const int u = r.next ? r.next(r.user) : (r.seq < r.N ? r.seq++ : -1);
+    if (u < 0) { r.drained = true; return MP_OK; }
+    if (u >= r.N) return fail(dev, MP_ERR_ARG, "next: utterance index out of range");
+    if (r.claimed[u]) return fail(dev, MP_ERR_ARG, "next: utterance claimed twice");
+    r.claimed[u] = 1;
+    *utt = u;
+    return MP_OK;
+}
+// utterance utt's preamble into s on the side stream, as a single run computes it
+// (NB = 1, Tmax = its own length)
+static int pool_stage(mp_dev *dev, PoolRun &r, StageWs &s, int utt) {
+    if (s.install_pending) {  // the install that read this workspace must have completed
+        HIPCHK(hipEventSynchronize(s.installed));
+        s.install_pending = false;
+    }
+    const int n = r.n_tokens[utt];
+    memcpy(s.h, r.tokens + (size_t)utt * r.tmax, (size_t)n * 4);
+    s.h[r.tmax] = n;
+    s.h[r.tmax + 1] = r.speaker[utt];
+    HIPCHK(hipMemcpyAsync(s.tok, s.h, (size_t)n * 4, hipMemcpyHostToDevice, dev->side));
+    HIPCHK(hipMemcpyAsync(s.T, s.h + r.tmax, 4, hipMemcpyHostToDevice, dev->side));
+    HIPCHK(hipMemcpyAsync(s.spk, s.h + r.tmax + 1, 4, hipMemcpyHostToDevice, dev->side));
+    PreWs w = s.w;
+    w.Tmax = n;
+    if (int rc = run_preamble(dev, w)) return rc;
+    HIPCHK(hipEventRecord(s.ready, dev->side));
+    s.utt = utt;
+    s.n = n;
+    return MP_OK;
+}
+// slot b becomes the staged utterance: the decode stream waits for its preamble in-stream
+static int pool_install(mp_dev *dev, PoolRun &r, StageWs &s, int b) {
+    HIPCHK(hipStreamWaitEvent(dev->stream, s.ready, 0));
+    mp::InstallP p{};
+    p.skc = (const uint4 *)s.w.kc; p.svc = (const uint4 *)s.w.vc; p.kc = (uint4 *)dev->kc; p.vc = (uint4 *)dev->vc;
+    p.nlayers = dev->m.dec_layers; p.smax_seq = s.w.max_seq; p.max_seq = dev->max_seq;
+    p.cache_row16 = 768 * (dev->kv16 ? 2 : 4) / 16;
+    p.sxak = (const uint4 *)s.w.xak; p.sxav = (const uint4 *)s.w.xav; p.xak = (uint4 *)dev->xak; p.xav = (uint4 *)dev->xav;
+    if (batch_reads_kp(dev)) { p.skp = (const uint4 *)s.w.kp; p.svp = (const uint4 *)s.w.vp; p.kp = (uint4 *)dev->kp; p.vp = (uint4 *)dev->vp; }
+    p.T = s.n; p.Tmax = dev->Tmax;
+    p.b = b; p.spk = r.speaker[s.utt]; p.stream = r.params.stream_base + s.utt;
+    p.audio_bos = dev->m.audio_bos; p.max_steps = dev->max_steps;
+    p.Tn = dev->T; p.spkn = dev->spk; p.pos = dev->pos; p.step = dev->step; p.done = dev->done; p.nframes = dev->nframes;
+    p.argeos = dev->argeos; p.codes_prev = dev->codes_prev; p.codes_out = dev->codes_out; p.ndone = dev->ndone;
+    p.cfg = dev->smpcfg; p.emb = dev->m.audio_emb; p.pos_emb = dev->m.dec_pos; p.x = dev->x;
+    if (b >= dev->B || s.n > dev->Tmax || s.w.kv16 != dev->kv16 || (dev->kp != nullptr) == s.w.xa_direct)
+        return fail(dev, MP_ERR_STATE, "slot pool: staged utterance does not fit the batch");
+    HIPCHK(mp::op_slot_install(p, dev->stream));
+    HIPCHK(hipEventRecord(s.installed, dev->stream));
+    s.install_pending = true;
+    s.utt = -1;
+    return MP_OK;
+}
+
+static int pool_run(mp_dev *dev, PoolRun &r) {
+    // the first `slots` claimed utterances: an ordinary batch at text stride tmax
+    std::vector<int> occ;  // utterance of each slot, -1 once handed out
+    for (int b = 0; b < r.slots; ++b) {
+        int u;
+        if (int rc = pool_claim(dev, r, &u)) return rc;
+        if (u < 0) break;
+        occ.push_back(u);
+    }
+    const int B = (int)occ.size();
+    r.st.slots = B;
+    if (B == 0) return MP_OK;
+    {
+        std::vector<int32_t> tok((size_t)B * r.tmax, 0), nt(B), spk(B);
+        for (int b = 0; b < B; ++b) {
+            nt[b] = r.n_tokens[occ[b]];
+            spk[b] = r.speaker[occ[b]];
+            memcpy(&tok[(size_t)b * r.tmax], r.tokens + (size_t)occ[b] * r.tmax, (size_t)nt[b] * 4);
+        }
+        if (int rc = begin_batch(dev, tok.data(), nt.data(), spk.data(), B, r.tmax, &r.params, r.tmax)) return rc;
+        // the draw streams follow the utterances, not the slots
+        mp::SmpCfg cfg{r.params.temperature, r.params.top_k, (unsigned long long)r.params.seed, r.params.stream_base, {}};
+        for (int b = 0; b < 16; ++b) cfg.stream[b] = r.params.stream_base + (b < B ? occ[b] : b);
+        HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
+        HIPCHK(hipStreamSynchronize(dev->stream));
+    }
+    dev->batch_ready = false;  // the pool owns the batch: mp_hip_decode needs a new mp_hip_begin_batch
+    if (int rc = prepare_iteration(dev)) return rc;
+    const int NB = dev->NB, S = dev->max_steps;
+    HIPCHK(hipHostMalloc((void **)&r.h, (size_t)(36 + S * 8) * 4, 0));
+    int32_t *h_nd = r.h, *h_done = r.h + 4, *h_nf = r.h + 20, *h_codes = r.h + 36;
+    // one utterance is always staged ahead while any remain
+    int cur = 0;  // the staging workspace the next install reads
+    bool staged = false;
+    auto stage_next = [&](int ws) -> int {
+        int u;
+        if (int rc = pool_claim(dev, r, &u)) return rc;
+        if (u < 0) return MP_OK;
+        if (int rc = ensure_stage(dev, r.tmax)) return rc;
+        if (int rc = pool_stage(dev, r, dev->stage[ws], u)) return rc;
+        cur = ws;
+        staged = true;
+        return MP_OK;
+    };
+    if (int rc = stage_next(0)) return rc;
+    HIPCHK(hipEventCreate(&r.e0));
+    HIPCHK(hipEventCreate(&r.e1));
+    HIPCHK(hipEventRecord(r.e0, dev->stream));
+    int it = 0, live = B;
+    // every utterance leaves its slot within max_steps iterations and a poll round
+    const long long it_max = ((long long)r.N + 1) * ((long long)S + r.poll);
+    while (live > 0) {
+        if (it >= it_max) return fail(dev, MP_ERR_STATE, "slot pool: a slot never finished");
+        if (int rc = launch_iteration(dev)) return rc;
+        ++it;
+        if (it % r.poll != 0) continue;
+        HIPCHK(hipMemcpyAsync(h_nd, dev->ndone, 16, hipMemcpyDeviceToHost, dev->stream));
+        HIPCHK(hipMemcpyAsync(h_done, dev->done, NB * 4, hipMemcpyDeviceToHost, dev->stream));
+        HIPCHK(hipMemcpyAsync(h_nf, dev->nframes, NB * 4, hipMemcpyDeviceToHost, dev->stream));
+        HIPCHK(hipStreamSynchronize(dev->stream));
+        if (int rc = handoff_bits(dev, h_nd[2])) return rc;  // before any codes are returned
+        for (int b = 0; b < B; ++b) {
+            if (occ[b] < 0 || !h_done[b]) continue;
+            const int nf = h_nf[b];
+            if (nf > 0) {
+                HIPCHK(hipMemcpyAsync(h_codes, dev->codes_out + (size_t)b * S * 8, (size_t)nf * 32, hipMemcpyDeviceToHost,
+                                      dev->stream));
+                HIPCHK(hipStreamSynchronize(dev->stream));
+            }
+            if (r.done) r.done(occ[b], h_codes, nf, r.user);
+            r.st.useful_slot_iters += nf;
+            occ[b] = -1;
+            --live;
+            if (!staged) continue;
+            StageWs &s = dev->stage[cur];
+            occ[b] = s.utt;
+            ++live;
+            ++r.st.refills;
+            staged = false;
+            if (int rc = pool_install(dev, r, s, b)) return rc;
+            if (int rc = stage_next(cur ^ 1)) return rc;
+        }
+    }
+    HIPCHK(hipEventRecord(r.e1, dev->stream));
+    HIPCHK(hipEventSynchronize(r.e1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, r.e0, r.e1));
+    r.st.iterations = it;
+    r.st.decode_ms = ms;
+    dev->timing.decode_ms = ms;
+    dev->timing.frames_total = (int)r.st.useful_slot_iters;
+    dev->timing.iterations = it;
+    return MP_OK;
+}
+
+int mp_hip_decode_queue(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int N,
+                        int tmax, int slots, int poll, const mp_params *params, mp_next_cb next, mp_done_cb done,
+                        void *user, mp_queue_stats *stats) {
+    if (!dev) return MP_ERR_ARG;
+    if (stats) *stats = mp_queue_stats{};
+    if (!dev->loaded) return fail(dev, MP_ERR_STATE, "no model loaded");
+    const int bmax = mp_hip_max_batch(dev);
+    if (!tokens || !n_tokens || !speaker || N < 1 || tmax < 1 || !params)
+        return fail(dev, MP_ERR_ARG, "invalid arguments");
+    if (slots < 1 || slots > bmax)
+        return fail(dev, MP_ERR_ARG, "invalid arguments (slots must be 1..mp_hip_max_batch: 8 with f32 weights, 16 in the bf16 / F16 / Q8_0 / Q4_0 modes)");
+    if (params->trace_hidden) return fail(dev, MP_ERR_ARG, "trace_hidden is not available with a slot pool");
+    int Tmax = 0, max_steps = 0;
+    if (int rc = check_params(dev, params, &max_steps)) return rc;
+    if (int rc = check_utterances(dev, tokens, n_tokens, speaker, N, tmax, &Tmax)) return rc;
+    HIPCHK(hipSetDevice(dev->device));
+    PoolRun r{tokens, n_tokens, speaker, N, tmax, slots, poll > 0 ? poll : 8, *params, next, done, user};
+    r.claimed.assign(N, 0);
+    const int rc = pool_run(dev, r);
+    // nothing of this run stays in flight, whatever its end: a refused call leaves the device usable
+    hipStreamSynchronize(dev->stream);
+    if (dev->side) hipStreamSynchronize(dev->side);
+    for (StageWs &s : dev->stage) { s.install_pending = false; s.utt = -1; }
+    if (r.h) hipHostFree(r.h);
+    if (r.e0) hipEventDestroy(r.e0);
+    if (r.e1) hipEventDestroy(r.e1);
+    if (rc == MP_OK && stats) *stats = r.st;
+    return rc;
 }
 
 // Streaming frame loop (magpie_synthesize_sentence_streaming's loop,
@@ -2142,7 +2480,7 @@ int mp_hip_lt_sample(mp_dev *dev, const float *hidden, float temperature, int to
     io.ignore_eos = forbid_eos != 0;
     // step: a call counter >= 4 (so only forbid_eos masks EOS), also the draw's step index
     const int step = 4 + dev->lt_calls++;
-    mp::SmpCfg cfg{temperature, top_k, (unsigned long long)seed, -1};
+    mp::SmpCfg cfg{temperature, top_k, (unsigned long long)seed, -1, {-1}};
     HIPCHK(hipMemcpyAsync(io.hidden, hidden, 768 * 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(io.step, &step, 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(io.cfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));

@@ -55,6 +55,15 @@ class mp_timing(ctypes.Structure):
 AUDIO_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_void_p)
 
 
+class mp_queue_stats(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("slots", ctypes.c_int), ("refills", ctypes.c_int),
+                ("useful_slot_iters", ctypes.c_longlong), ("decode_ms", ctypes.c_double)]
+
+
+# int (*mp_next_cb)(void *user); void (*mp_done_cb)(int utt, const int32_t *codes, int n_frames, void *user)
+NEXT_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
+DONE_CB = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_void_p)
+
 # (name, restype, argtypes) of every symbol include/magpie_hip.h declares
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -73,6 +82,8 @@ SYMBOLS = [
     ("mp_hip_error", ctypes.c_char_p, [_P]),
     ("mp_hip_begin_batch", _I, [_P, _P, _P, _P, _I, _I, ctypes.POINTER(mp_params)]),
     ("mp_hip_decode", _I, [_P, _P, _P]),
+    ("mp_hip_decode_queue", _I, [_P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(mp_params), NEXT_CB, DONE_CB, _P,
+                                 ctypes.POINTER(mp_queue_stats)]),
     ("mp_hip_get_trace", _I, [_P, _P]),
     ("mp_hip_debug_buffer", ctypes.c_int64, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
     ("mp_hip_encode_text", _I, [_P, _P, _I, _P]),
@@ -100,7 +111,7 @@ SYMBOLS = [
 ]
 
 # entry points added after round 4: absent from the A/B baseline libraries
-OPTIONAL = {"mp_hip_encode_text"}
+OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue"}
 
 _lib = None
 
@@ -187,6 +198,22 @@ class SynthResult:
     decode_ms: float
     iterations: int
     hidden: Optional[np.ndarray] = None  # [B][max_steps+1][768] when traced
+
+
+@dataclass
+class QueueResult:
+    codes: List[Optional[np.ndarray]]  # per utterance [n_frames][8] (None: never claimed by this call)
+    n_frames: np.ndarray               # -1 for an utterance this call did not run
+    iterations: int                    # decode iterations (graph replays)
+    slots: int
+    refills: int
+    useful_slot_iters: int             # frames produced
+    decode_ms: float
+
+    @property
+    def utilisation(self) -> float:
+        """useful slot-iterations / (iterations x slots)"""
+        return self.useful_slot_iters / max(1, self.iterations * self.slots)
 
 
 class Device:
@@ -279,6 +306,53 @@ class Device:
         """Batched magpie_synthesize_codes_graph_reuse over independent utterances."""
         B = self.begin(tokens, speakers, max_dec_steps, temperature, top_k, ignore_eos, seed, trace, stream_base)
         return self.decode(B, max_dec_steps, trace)
+
+    def synthesize_queue(self, tokens: Sequence[Sequence[int]], speakers: Optional[Sequence[int]] = None,
+                         slots: int = 8, poll: int = 8, next=None, max_dec_steps: int = 500,
+                         temperature: float = 0.0, top_k: int = 80, ignore_eos: bool = False, seed: int = 0,
+                         stream_base: int = 0, emit_eos_frame: bool = False, trace: bool = False) -> QueueResult:
+        """mp_hip_decode_queue (continuous batching): every utterance of `tokens` through
+        `slots` decode slots, a finished slot refilled from the queue between two graph
+        replays. next() -> index of the next utterance to run, or -1 once drained (None:
+        0, 1, ... in order). Utterance i draws from stream stream_base + i and equals its
+        single run. Returns the per-utterance codes plus the loop's counts."""
+        n = len(tokens)
+        tmax = max((len(t) for t in tokens), default=1)
+        tok = np.zeros((max(n, 1), max(tmax, 1)), np.int32)
+        for b, t in enumerate(tokens):
+            tok[b, :len(t)] = np.asarray(t, np.int32)
+        nt = np.array([len(t) for t in tokens], np.int32)
+        spk = np.zeros(n, np.int32) if speakers is None else np.asarray(speakers, np.int32)
+        if len(spk) != n:
+            raise ValueError("speakers must match tokens")
+        p = mp_params(temperature, top_k, max_dec_steps, int(ignore_eos), seed, int(trace), int(stream_base),
+                      int(emit_eos_frame))
+        codes: List[Optional[np.ndarray]] = [None] * n
+        nf = np.full(n, -1, np.int32)
+        raised = []
+
+        def _next(_user):
+            try:
+                u = next()
+                return -1 if u is None else int(u)
+            except BaseException as e:  # an exception cannot cross the C frames: end the queue, re-raise after
+                raised.append(e)
+                return -1
+
+        def _done(utt, ptr, n_frames, _user):
+            codes[utt] = (np.ctypeslib.as_array(ptr, shape=(n_frames, 8)).copy() if n_frames > 0
+                          else np.zeros((0, 8), np.int32))
+            nf[utt] = n_frames
+
+        ncb = NEXT_CB(_next) if next is not None else ctypes.cast(None, NEXT_CB)
+        dcb = DONE_CB(_done)
+        st = mp_queue_stats()
+        rc = self.lib.mp_hip_decode_queue(self.h, tok.ctypes.data, nt.ctypes.data, spk.ctypes.data, n, tmax, slots, poll,
+                                          ctypes.byref(p), ncb, dcb, None, ctypes.byref(st))
+        if raised:
+            raise raised[0]
+        self._check(rc)
+        return QueueResult(codes, nf, st.iterations, st.slots, st.refills, int(st.useful_slot_iters), st.decode_ms)
 
     def synthesize_stream(self, codec: "Codec", tokens: Sequence[Sequence[int]], on_audio,
                           speakers: Optional[Sequence[int]] = None, max_dec_steps: int = 500,

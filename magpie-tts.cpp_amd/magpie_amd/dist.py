@@ -14,10 +14,15 @@ Two ways to split:
     rank instead claims the next `batch` utterances from an atomic counter in the
     process group's store whenever its device batch is free, longest text first (the
     longest-processing-time rule: a text's length is the host's best predictor of its
-    frame count), so the ranks finish within about one batch of each other.
+    frame count), so the ranks finish within about one batch of each other;
+  * synthesize_pool: the same queue feeding the device's slot pool
+    (Device.synthesize_queue, continuous batching): one position per claim, whenever a
+    decode slot needs its next utterance. simulate_pool restates that schedule on the
+    host.
 """
 from __future__ import annotations
 
+import dataclasses
 import itertools
 from typing import Callable, Dict, List, Optional, Sequence
 
@@ -123,6 +128,69 @@ def synthesize_queue(synth: Callable[[List[Sequence[int]], List[int]], List], to
         for u, r in zip(utt, out):
             mine[u] = r
     return mine
+
+
+def synthesize_pool(dev, tokens: Sequence[Sequence[int]], speakers: Optional[Sequence[int]] = None, slots: int = 8,
+                    queue: Optional[WorkQueue] = None, **kw) -> Dict[int, object]:
+    """This rank's share of `tokens` through dev.synthesize_queue (continuous batching):
+    the device's slot pool claims ONE position at a time from the shared queue, longest
+    text first, whenever a slot needs its next utterance, so a rank never holds more
+    than its resident slots plus the one staged ahead. kw goes to synthesize_queue
+    (poll, max_dec_steps, sampling). Returns {utterance index: codes} like
+    synthesize_queue, for gather_results; the loop's counts are in `.stats` of the
+    returned dict (a QueueResult without the codes)."""
+    n = len(tokens)
+    spk = [0] * n if speakers is None else list(speakers)
+    if len(spk) != n:
+        raise ValueError("speakers must match tokens")
+    order = longest_first(tokens)
+    q = queue if queue is not None else WorkQueue(n)
+
+    def claim():
+        pos = q.claim(1)
+        return order[pos[0]] if pos else -1
+
+    res = dev.synthesize_queue(tokens, speakers=spk, slots=slots, next=claim, **kw)
+    mine = PoolResults((u, c) for u, c in enumerate(res.codes) if c is not None)
+    mine.stats = dataclasses.replace(res, codes=[]) if dataclasses.is_dataclass(res) else res
+    return mine
+
+
+class PoolResults(dict):
+    """{utterance index: codes} of synthesize_pool, with the loop's counts in .stats"""
+    stats = None
+
+
+def simulate_pool(frames: Sequence[int], slots: int, poll: int, max_dec_steps: int, emit_eos: bool = False):
+    """The slot pool's schedule restated on the host: utterances with the given frame
+    counts, in claim order, through `slots` slots polled every `poll` iterations.
+    Returns (iterations, useful_slot_iters).
+
+    An utterance of f frames holds its slot for f iterations when it ran into
+    max_dec_steps (or the EOS frame is emitted), else f + 1: the iteration that finds the
+    EOS emits nothing. The host sees a finished slot at the next multiple of `poll` and
+    installs the next claimed utterance there (slot order), which starts with the
+    following iteration; the loop ends at the poll that finds every slot finished and
+    the queue drained. With fewer utterances than slots the surplus slots do not exist."""
+    if slots < 1 or poll < 1 or max_dec_steps < 1:
+        raise ValueError("slots, poll and max_dec_steps must be >= 1")
+    frames = list(frames)
+    if any(f < 0 or f > max_dec_steps for f in frames):
+        raise ValueError("frame counts must be in 0..max_dec_steps")
+    busy = [f if (emit_eos or f >= max_dec_steps) else f + 1 for f in frames]
+    nxt = min(slots, len(frames))
+    end = busy[:nxt]  # iteration after which each slot's utterance is finished (None: empty)
+    it = 0
+    while any(e is not None for e in end):
+        it += poll
+        for b, e in enumerate(end):
+            if e is None or e > it:
+                continue
+            end[b] = None
+            if nxt < len(frames):
+                end[b] = it + busy[nxt]
+                nxt += 1
+    return it, sum(frames)
 
 
 def gather_results(mine: Dict[int, object], n_total: int) -> List[object]:
