@@ -44,6 +44,7 @@
 #include "../../include/magpie_hip.h"
 #include "mp_device.hpp"
 #include "mp_gguf.hpp"
+#include "mp_own.hpp"
 
 namespace mpc {
 
@@ -1159,30 +1160,30 @@ __global__ __launch_bounds__(256) void post_conv_kernel(PostP p) {
 struct mp_codec {
     int device = 0;
     std::string err;
-    hipStream_t stream = nullptr;
+    mp::Stream stream;  // declared first: it outlives every buffer below
     // weights
     struct Conv { _Float16 *w = nullptr, *wf = nullptr; float *b = nullptr; int ks = 0, cin = 0, cout = 0, cinp = 0, coutp = 0; };
     Conv pre, rb[5][3][3][2];  // [stage][kernel j][dilation k][in/skip]
     float *rb_alpha[5][3][3][2] = {};
     float *up_alpha[5] = {}, *up_w[5] = {}, *up_b[5] = {};
     float *post_alpha = nullptr, *post_w = nullptr, *post_b = nullptr;
-    std::vector<void *> weight_allocs;
-    // activations (grown on demand)
+    mp::DevBlocks weights;
+    // activations (grown on demand: all of `act` together, codes and audio each on its own)
+    mp::DevBlocks act, codes_mem, audio_mem;
     size_t cap_elems = 0;
     float *x_pre = nullptr, *x0 = nullptr, *brb[3] = {}, *audio = nullptr;
     float *rbt[3] = {};  // fused residual blocks: block 1's output (block 2 reads its halo)
     _Float16 *a16[3] = {}, *b16[3] = {};  // f16 conv operands: in_conv (HS_in x), sk_conv (HS_sk h)
     int *codes = nullptr;
     size_t codes_cap = 0, audio_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    mp::Event ev0, ev1;
     // pinned host staging of the codes in / audio out: a copy from or to pageable memory is
     // staged synchronously by the runtime and waited for the decode's queued work too
     // (configs[2]: each overlapped round's codec finished only after the decode's next chunk)
-    int32_t *h_codes_pin = nullptr;
-    float *h_audio_pin = nullptr;
-    size_t h_codes_cap = 0, h_audio_cap = 0;
+    mp::Pinned codes_pin, audio_pin;
     float last_ms = 0.f;  // device time of the last decode (launch sequence only)
     // diagnostics (MAGPIE_CODEC_TS=stage,block,file): the phase stamps of one rb_kernel launch
+    mp::DevBlocks ts_mem;
     unsigned long long *ts_dev = nullptr;
     int ts_stage = -1, ts_block = -1;
     std::string ts_file;
@@ -1190,21 +1191,11 @@ struct mp_codec {
 
 namespace {
 
-#define CHK(expr)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            c->err = std::string(#expr) + " failed: " + hipGetErrorString(e_);                     \
-            return MP_ERR_HIP;                                                                     \
-        }                                                                                          \
-    } while (0)
+#define CHK(expr) MP_HIPCHK_TO(c->err, expr)
 
 template <class T> int upload(mp_codec *c, T **dst, const std::vector<T> &h) {
-    void *p = nullptr;
-    CHK(hipMalloc(&p, h.size() * sizeof(T) + 64));
-    CHK(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    c->weight_allocs.push_back(p);
-    *dst = (T *)p;
+    CHK(c->weights.bytes(dst, h.size() * sizeof(T) + 64));
+    CHK(hipMemcpy(*dst, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     return MP_OK;
 }
 
@@ -1297,22 +1288,24 @@ int ensure_buffers(mp_codec *c, int nchunk, int F) {
     need = std::max(need, (size_t)nchunk * F * CP_PRE);
     if (need > c->cap_elems) {
         float **bufs[8] = {&c->x_pre, &c->x0, &c->brb[0], &c->brb[1], &c->brb[2], &c->rbt[0], &c->rbt[1], &c->rbt[2]};
-        for (auto b : bufs) if (*b) { hipFree(*b); *b = nullptr; }
-        for (auto b : bufs) CHK(hipMalloc((void **)b, need * 4 + 256));
         _Float16 **hb[6] = {&c->a16[0], &c->a16[1], &c->a16[2], &c->b16[0], &c->b16[1], &c->b16[2]};
-        for (auto b : hb) if (*b) { hipFree(*b); *b = nullptr; }
-        for (auto b : hb) CHK(hipMalloc((void **)b, need * 2 + 256));
+        c->act.clear();
+        c->cap_elems = 0;
+        for (auto b : bufs) CHK(c->act.get(b, need));
+        for (auto b : hb) CHK(c->act.get(b, need));
         c->cap_elems = need;
     }
     const size_t ncodes = (size_t)nchunk * 8 * F, naudio = (size_t)nchunk * F * HOP;
     if (ncodes > c->codes_cap) {
-        if (c->codes) hipFree(c->codes);
-        CHK(hipMalloc((void **)&c->codes, ncodes * 4));
+        c->codes_mem.clear();
+        c->codes_cap = 0;
+        CHK(c->codes_mem.bytes(&c->codes, ncodes * 4));
         c->codes_cap = ncodes;
     }
     if (naudio > c->audio_cap) {
-        if (c->audio) hipFree(c->audio);
-        CHK(hipMalloc((void **)&c->audio, naudio * 4));
+        c->audio_mem.clear();
+        c->audio_cap = 0;
+        CHK(c->audio_mem.bytes(&c->audio, naudio * 4));
         c->audio_cap = naudio;
     }
     return MP_OK;
@@ -1549,7 +1542,7 @@ int mp_hip_codec_init(int device, const char *path, mp_codec **out) {
     c->device = device;
     int least = 0, greatest = 0;  // the codec's stream at the least priority (see mp_hip_init)
     if (hipSetDevice(device) != hipSuccess || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
-        hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, least) != hipSuccess) {
+        c->stream.create(least) != hipSuccess) {
         delete c;
         return MP_ERR_HIP;
     }
@@ -1568,23 +1561,12 @@ int mp_hip_codec_decode_chunks(mp_codec *c, const int32_t *codes, int n_chunks, 
     CHK(hipSetDevice(c->device));
     if (int rc = ensure_buffers(c, n_chunks, chunk_frames)) return rc;
     const size_t ncodes = (size_t)n_chunks * 8 * chunk_frames, nsamp = (size_t)n_chunks * chunk_frames * mpc::HOP;
-    if (c->h_codes_cap < ncodes) {
-        if (c->h_codes_pin) hipHostFree(c->h_codes_pin);
-        c->h_codes_pin = nullptr;
-        c->h_codes_cap = 0;
-        CHK(hipHostMalloc((void **)&c->h_codes_pin, ncodes * 4, hipHostMallocDefault));
-        c->h_codes_cap = ncodes;
-    }
-    if (c->h_audio_cap < nsamp) {
-        if (c->h_audio_pin) hipHostFree(c->h_audio_pin);
-        c->h_audio_pin = nullptr;
-        c->h_audio_cap = 0;
-        CHK(hipHostMalloc((void **)&c->h_audio_pin, nsamp * 4, hipHostMallocDefault));
-        c->h_audio_cap = nsamp;
-    }
-    memcpy(c->h_codes_pin, codes, ncodes * 4);
-    CHK(hipMemcpyAsync(c->codes, c->h_codes_pin, ncodes * 4, hipMemcpyHostToDevice, c->stream));
-    if (!c->ev0) { CHK(hipEventCreate(&c->ev0)); CHK(hipEventCreate(&c->ev1)); }
+    CHK(c->codes_pin.reserve(ncodes * 4));
+    CHK(c->audio_pin.reserve(nsamp * 4));
+    memcpy(c->codes_pin.p, codes, ncodes * 4);
+    CHK(hipMemcpyAsync(c->codes, c->codes_pin.p, ncodes * 4, hipMemcpyHostToDevice, c->stream));
+    CHK(c->ev0.create());
+    CHK(c->ev1.create());
     // diagnostics: MAGPIE_CODEC_TS=stage,block,file -> the phase stamps of that stage's
     // rb_kernel launch for residual block `block` (tools_dev/codec_rb_timeline.py)
     constexpr size_t TS_N = (size_t)3 * mpc::RB_TS_GX * mpc::RB_TS_N;
@@ -1598,7 +1580,7 @@ int mp_hip_codec_decode_chunks(mp_codec *c, const int32_t *codes, int n_chunks, 
             c->ts_stage = st;
             c->ts_block = bl;
             c->ts_file = file;
-            if (!c->ts_dev) CHK(hipMalloc((void **)&c->ts_dev, TS_N * 8));
+            if (!c->ts_dev) CHK(c->ts_mem.bytes(&c->ts_dev, TS_N * 8));
             CHK(hipMemsetAsync(c->ts_dev, 0, TS_N * 8, c->stream));
         } else {
             c->ts_stage = c->ts_block = -1;
@@ -1608,9 +1590,9 @@ int mp_hip_codec_decode_chunks(mp_codec *c, const int32_t *codes, int n_chunks, 
     CHK(hipEventRecord(c->ev0, c->stream));
     if (int rc = codec_run(c, n_chunks, chunk_frames)) return rc;
     CHK(hipEventRecord(c->ev1, c->stream));
-    CHK(hipMemcpyAsync(c->h_audio_pin, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
+    CHK(hipMemcpyAsync(c->audio_pin.p, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
     CHK(hipStreamSynchronize(c->stream));
-    memcpy(audio_out, c->h_audio_pin, nsamp * 4);
+    memcpy(audio_out, c->audio_pin.p, nsamp * 4);
     CHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     if (c->ts_dev && !c->ts_file.empty()) {
         std::vector<unsigned long long> h(TS_N);
@@ -1637,21 +1619,6 @@ void mp_hip_codec_free(mp_codec *c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->h_codes_pin) hipHostFree(c->h_codes_pin);
-    if (c->h_audio_pin) hipHostFree(c->h_audio_pin);
-    for (void *p : c->weight_allocs) hipFree(p);
-    if (c->ts_dev) hipFree(c->ts_dev);
-    float *bufs[5] = {c->x_pre, c->x0, c->brb[0], c->brb[1], c->brb[2]};
-    for (float *b : bufs) if (b) hipFree(b);
-    for (int j = 0; j < 3; ++j) {
-        if (c->a16[j]) hipFree(c->a16[j]);
-        if (c->b16[j]) hipFree(c->b16[j]);
-    }
-    if (c->codes) hipFree(c->codes);
-    if (c->audio) hipFree(c->audio);
-    if (c->ev0) hipEventDestroy(c->ev0);
-    if (c->ev1) hipEventDestroy(c->ev1);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 

@@ -18,22 +18,18 @@
 #include <cstdlib>
 #include <cstring>
 #include <future>
-#include <memory>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/magpie_hip.h"
-#include "mp_gguf.hpp"
 #include "mp_device.hpp"
+#include "mp_model.hpp"
 #include "mp_params.hpp"
 #include "mp_ops.hpp"
 #include "mp_prefill_api.hpp"
 
 namespace mp {
 
-// the 16-bit MFMA family serves the bf16 and F16 weight modes
-static bool h16_mode(int weight_mode) { return weight_mode == MP_WEIGHTS_BF16 || weight_mode == MP_WEIGHTS_F16; }
 // The weight mode's op table at NB slots (mp_ops.hpp). f32 and Q8_0 modes: the f32 family
 // (a Q8_0 file's quantised tensors take q8_ops(NB) instead, tensor by tensor). bf16 mode:
 // every projection on MFMA except the f32 LT in_proj and the direct XA's f32 q_net. F16
@@ -47,72 +43,6 @@ static OpTable table_for(int NB, int weight_mode) {
     }
     return t;
 }
-
-// A Q8_0 tensor (weight mode MP_WEIGHTS_Q8): as stored, int8 [N][K] + fp16 scales
-// [N][K/32] (the preamble GEMMs), and for the decode projections also in int8 MFMA
-// fragment order (pq, pd: mp_decode_q8.hip)
-struct QW {
-    const signed char *q = nullptr;
-    const unsigned short *d = nullptr;
-    const signed char *pq = nullptr;
-    const unsigned short *pd = nullptr;
-    int nib = 0;        // a Q4_0 tensor: pq holds nibble fragments (pack_q4, 18 B per 32 weights)
-    size_t head_q = 0;  // bytes between consecutive heads' fragments (the 8 LT output heads)
-    explicit operator bool() const { return q != nullptr; }
-};
-// bytes of a packed Q8_0 tensor: fragments and scales (Q4_0: half the fragment bytes)
-static size_t q8p_qbytes(int N, int K) { return (size_t)((N + 15) / 16) * (K / 64) * 1024; }
-static size_t q4p_qbytes(int N, int K) { return (size_t)((N + 15) / 16) * (K / 64) * 512; }
-static size_t q8p_dbytes(int N, int K) { return (size_t)((N + 15) / 16) * (K / 64) * 64; }
-
-struct EncLayerW { const float *norm_self, *qkv, *o, *norm_ff, *ff1, *ff2; QW qkv8, o8; };
-struct DecLayerW {
-    const float *norm_self, *qkv, *o, *norm_xq, *xq, *xkv, *xo, *norm_xmem, *norm_ff, *ff1, *ff2;
-    QW qkv8, o8, xq8, xkv8, xo8;
-};
-
-struct Model {
-    int enc_layers = 6, dec_layers = 12, n_spk = 5, dec_pos_rows = 0, text_vocab = 2380;
-    int audio_bos = 2016, audio_eos = 2017, max_dec_steps = 500;
-    float eps = 1e-5f;
-    const float *text_emb = nullptr, *enc_pos = nullptr, *enc_norm_out = nullptr, *dec_pos = nullptr;
-    const float *dec_norm_out = nullptr, *baked = nullptr, *audio_emb = nullptr;
-    std::vector<EncLayerW> enc;
-    std::vector<DecLayerW> dec;
-    const float *lt_in_w, *lt_in_b, *lt_pos, *lt_norm_self, *lt_qkv, *lt_o, *lt_norm_ff, *lt_ff1, *lt_ff2, *lt_out_w,
-        *lt_out_b;
-    float *lt_ptab = nullptr;  // [8][2024][256] = in_proj(audio_emb[c][v]) + b, built at load
-    float *lt_qkvtab = nullptr;  // [7][2024][768] = qkv_net(LN(ptab[c][v] + lt_pos[c+1])), built at load
-    // f32 weight mode (lt_ffn2_kernel): [7][2024][256] = o_net(v third of lt_qkvtab), and
-    // [512][256] = [W_k ; W_o W_v] for position 0 (W_o W_v formed in double on the host)
-    float *lt_votab = nullptr, *lt_kvo = nullptr;
-    // the LT FFN-down weights [256][1024] re-laid slice-major [LT_FFN_P][256][16]: the FFN
-    // workgroup that owns hidden units [16p, 16p+16) reads one contiguous 16 KiB block
-    // instead of 256 half cache lines (whose other halves sit with workgroup p +- 1 on
-    // another XCD: every line was fetched twice)
-    float *lt_ff2s = nullptr;
-    // bf16 weight mode (lt_slot_kernel): the LT FFN weights rounded to bf16, W1 row-major
-    // [1024][256] and W2 slice-major [LTS_P][256][1024 / LTS_P]
-    unsigned short *lt_ff1h = nullptr, *lt_ff2h = nullptr;
-    // Q8_0 weight mode (lt_slot_q8_kernel): the F32 FFN-down weights slice-major [LTQ_P][256][1024 / LTQ_P]
-    float *lt_ff2q = nullptr;
-    std::vector<float *> xq_t;  // per layer W_q^T [768][128] (for K' = K W_q)
-    // weight mode MP_WEIGHTS_BF16: decode projections repacked as bf16 MFMA fragments
-    int weight_mode = 0;
-    unsigned short *pk_arena = nullptr;
-    std::vector<const unsigned short *> pk_qkv, pk_o, pk_ff1, pk_ff2;
-    const unsigned short *pk_lt_qkv = nullptr, *pk_lt_o = nullptr, *pk_lt_ff1 = nullptr, *pk_lt_ff2 = nullptr,
-                         *pk_lt_out = nullptr,  // lt_out: [8][127 tiles][8][64][8]
-                         *pk_lt_in = nullptr;   // F16 mode only: the LT in_proj [256][768]
-    // weight mode MP_WEIGHTS_Q8: the file's Q8_0 tensors as stored (ggml's quantised mul_mat)
-    void *q8_arena = nullptr, *q8p_arena = nullptr;
-    size_t q8_bytes = 0;
-    bool q8_all = false;  // every decode projection is Q8_0 / Q4_0: batches up to 16
-    QW lt_in8, lt_qkv8, lt_o8, lt_out8;  // lt_out8: [8][2024][256] (+ [8][2024][8] scales)
-    const signed char *lt_o8t = nullptr;  // lt_o8's int8 transposed by 16-byte chunks [16][256][16] (lt_slot_q8_kernel)
-    float *arena = nullptr;
-    size_t arena_bytes = 0;
-};
 
 enum OpKind { K_GEMV = 0, K_ATTN = 1, K_FIN = 2, K_XA = 3, K_XAQ8 = 5, K_LTFFN = 6, K_LTMERGE = 7, K_LTPICK = 8,
               K_LTFFN2 = 10, K_LTKVO = 11, K_LTSLOT = 12, K_LTFRONT = 13, K_LTSLOTQ8 = 14 };
@@ -178,17 +108,19 @@ struct PreWs {
 // only after that event has completed).
 struct StageWs {
     PreWs w{};
-    std::vector<void *> allocs;
+    mp::DevBlocks mem;
     int32_t *tok = nullptr, *T = nullptr, *spk = nullptr;  // device
-    int32_t *h = nullptr;                                  // pinned [tmax + 2]: tokens, length, speaker
-    hipEvent_t ready = nullptr, installed = nullptr;
+    mp::Pinned pin;  // int32 [tmax + 2]: tokens, length, speaker
+    mp::Event ready, installed;
     bool install_pending = false;
     int utt = -1, n = 0;
 };
 
 struct mp_dev {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // the decode stream, and the side stream the slot pool's preambles run on (made by the
+    // first mp_hip_decode_queue). Declared first: they outlive every buffer below.
+    mp::Stream stream, side;
     std::string err;
     mp::Model m;
     bool loaded = false;
@@ -200,15 +132,17 @@ struct mp_dev {
     bool xa_direct = false;    // this batch runs the direct XA form (f32 / bf16 modes)
     int kv16 = 0;             // the current batch's SA cache holds bf16
     // device state (one allocation per buffer, sized for the configuration)
-    std::vector<void *> allocs;
+    mp::DevBlocks mem;
+    // the hand-off granule buffers among them, with their element counts: reset_decode_state
+    // clears exactly what alloc_batch made
+    std::vector<std::pair<unsigned long long *, size_t>> granules;
     float *x = nullptr, *x2 = nullptr, *kp = nullptr, *vp = nullptr, *q = nullptr, *sa_out = nullptr,
           *h = nullptr, *hidden = nullptr;
     float *xqb = nullptr;  // Q8 mode: q_net output [NB][128]
     unsigned short *h_b16 = nullptr;  // bf16 mode: GELU(FFN up) as the bf16 FFN-down operand [NB][3072]
     float *gpart = nullptr;            // preamble split-K partial sums (mp::gemm_splits)
-    hipEvent_t sev[2] = {nullptr, nullptr};  // streaming: the two chunk snapshots landed
-    int32_t *h_codes = nullptr;              // streaming: pinned host mirror of codes_out [NB][S][8] + snapshots
-    size_t h_codes_n = 0;
+    mp::Event sev[2];           // streaming: the two chunk snapshots landed
+    mp::Pinned h_codes_pin;     // streaming: pinned host mirror of codes_out [NB][S][8] + snapshots
     float *sa_part = nullptr, *xa_part = nullptr;  // split-K attention states [NB][12][4][68], [NB][4][772]
     unsigned long long *sagh = nullptr, *xagh = nullptr;  // 16-slot merges: split-state granules
     unsigned long long *kgh = nullptr;  // split-K FFN-down partial tiles (16-bit modes): [48][KS][256]
@@ -225,7 +159,7 @@ struct mp_dev {
     mp::SmpCfg *smpcfg = nullptr;
     int lt_calls = 0;
     // magpie_local_transformer_sample_all scratch (batch 1, independent of any batch)
-    std::vector<void *> ltio_allocs;
+    mp::DevBlocks ltio_mem;
     mp::LtIo lt_io{};
     // preamble scratch
     float *pX = nullptr, *pH = nullptr, *pQKV = nullptr, *pATT = nullptr, *pF = nullptr, *pXQ = nullptr,
@@ -236,9 +170,10 @@ struct mp_dev {
     std::vector<mp::OpRec> ops;
     bool batch_ready = false;
     mp_timing timing{};
-    int *h_ndone = nullptr;  // pinned
-    // mp_hip_encode_text's private workspace: grows on demand, freed by mp_hip_free (a
+    mp::Pinned h_ndone;  // one int
+    // mp_hip_encode_text's private workspace: grows on demand, kept until mp_hip_free (a
     // per-call hipFree would synchronise the whole device, stalling other streams' work)
+    mp::DevBlocks enc_ws_mem;
     char *enc_ws = nullptr;
     size_t enc_ws_bytes = 0;
     // diagnostics (MAGPIE_Q8DUMP=1 at mp_hip_begin_batch, Q8_0 weights): one dump slot per
@@ -247,37 +182,20 @@ struct mp_dev {
     size_t q8dump_slot = 0;
     int q8dump_cap = 0, q8dump_n = 0;
     std::vector<int> q8dump_index;
-    // slot pool (mp_hip_decode_queue): two staging workspaces and the side stream their
-    // preambles run on, kept between calls while their shape (tmax, cache type, XA form) holds
+    // slot pool (mp_hip_decode_queue): two staging workspaces, kept between calls while their
+    // shape (tmax, cache type, XA form) holds
     StageWs stage[2];
-    hipStream_t side = nullptr;
     int stage_tmax = 0, stage_kv16 = 0;
     bool stage_direct = false;
 };
 
 namespace {
 
-#define HIPCHK(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            dev->err = std::string(#expr) + " failed: " + hipGetErrorString(e_);               \
-            return MP_ERR_HIP;                                                                 \
-        }                                                                                      \
-    } while (0)
+#define HIPCHK(expr) MP_HIPCHK_TO(dev->err, expr)
 
 int fail(mp_dev *dev, int code, const std::string &msg) {
     dev->err = msg;
     return code;
-}
-
-template <class T> int dalloc(mp_dev *dev, T **p, size_t count) {
-    void *v = nullptr;
-    HIPCHK(hipMalloc(&v, count * sizeof(T) + 256));
-    HIPCHK(hipMemsetAsync(v, 0, count * sizeof(T) + 256, dev->stream));
-    dev->allocs.push_back(v);
-    *p = (T *)v;
-    return MP_OK;
 }
 
 void free_batch(mp_dev *dev) {
@@ -285,14 +203,15 @@ void free_batch(mp_dev *dev) {
     if (dev->graph) hipGraphDestroy(dev->graph);
     dev->exec = nullptr;
     dev->graph = nullptr;
-    for (void *p : dev->allocs) hipFree(p);
-    dev->allocs.clear();
+    dev->mem.clear();
+    dev->granules.clear();
     dev->ops.clear();
     dev->batch_ready = false;
     dev->B = dev->NB = dev->Tmax = dev->max_steps = 0;
     dev->xa_direct = false;
     dev->kp = dev->vp = nullptr;
-    dev->q8dump = nullptr;  // (one of allocs)
+    dev->trace = nullptr;  // a batch without a trace must not see (or write) the last one's
+    dev->q8dump = nullptr;
     dev->q8dump_cap = dev->q8dump_n = 0;
     dev->q8dump_index.clear();
 }
@@ -300,13 +219,7 @@ void free_batch(mp_dev *dev) {
 // the slot pool's staging workspaces (the side stream stays until mp_hip_free)
 void free_stage(mp_dev *dev) {
     if (dev->side) hipStreamSynchronize(dev->side);
-    for (StageWs &s : dev->stage) {
-        for (void *p : s.allocs) hipFree(p);
-        if (s.h) hipHostFree(s.h);
-        if (s.ready) hipEventDestroy(s.ready);
-        if (s.installed) hipEventDestroy(s.installed);
-        s = StageWs{};
-    }
+    for (StageWs &s : dev->stage) s = StageWs{};
     dev->stage_tmax = 0;
 }
 
@@ -327,502 +240,6 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// ------------------------------------------------------------------ weights
-// Tensor names and mapping: create_tensors (magpie.cpp:572-672).
-// Size (elements) of one packed [N][K] matrix: [ceil(N/16)][K/32][64][8].
-size_t pk_elems(int N, int K) { return (size_t)((N + 15) / 16) * 16 * K; }
-
-// bf16 weight mode: the f32 weights rounded to bf16 fragments; F16 mode (an F16
-// file): its f16 values (widened exactly at load) repacked as f16 fragments.
-int pack_weights(mp_dev *dev, bool f16) {
-    mp::Model &m = dev->m;
-    if (m.pk_arena) { hipFree(m.pk_arena); m.pk_arena = nullptr; }
-    const int L = m.dec_layers;
-    const size_t per_layer = pk_elems(2304, 768) + pk_elems(768, 768) + pk_elems(3072, 768) + pk_elems(768, 3072);
-    const size_t lt = pk_elems(768, 256) + pk_elems(256, 256) + pk_elems(1024, 256) + pk_elems(256, 1024) +
-                      8 * pk_elems(2024, 256) + (f16 ? pk_elems(256, 768) : 0);
-    HIPCHK(hipMalloc(&m.pk_arena, (per_layer * L + lt) * 2));
-    unsigned short *cur = m.pk_arena;
-    auto pack = [&](const float *W, int N, int K) -> const unsigned short * {
-        unsigned short *dst = cur;
-        cur += pk_elems(N, K);
-        return mp::pack_b16(W, N, K, dst, dev->stream, f16) == hipSuccess ? dst : nullptr;
-    };
-    m.pk_qkv.assign(L, nullptr); m.pk_o.assign(L, nullptr); m.pk_ff1.assign(L, nullptr); m.pk_ff2.assign(L, nullptr);
-    for (int l = 0; l < L; ++l) {
-        m.pk_qkv[l] = pack(m.dec[l].qkv, 2304, 768);
-        m.pk_o[l] = pack(m.dec[l].o, 768, 768);
-        m.pk_ff1[l] = pack(m.dec[l].ff1, 3072, 768);
-        m.pk_ff2[l] = pack(m.dec[l].ff2, 768, 3072);
-        if (!m.pk_qkv[l] || !m.pk_o[l] || !m.pk_ff1[l] || !m.pk_ff2[l]) return fail(dev, MP_ERR_HIP, "bf16 pack failed");
-    }
-    m.pk_lt_qkv = pack(m.lt_qkv, 768, 256);
-    m.pk_lt_o = pack(m.lt_o, 256, 256);
-    m.pk_lt_ff1 = pack(m.lt_ff1, 1024, 256);
-    m.pk_lt_ff2 = pack(m.lt_ff2, 256, 1024);
-    m.pk_lt_out = cur;
-    for (int c = 0; c < 8; ++c)
-        if (!pack(m.lt_out_w + (size_t)c * 2024 * 256, 2024, 256)) return fail(dev, MP_ERR_HIP, "bf16 pack failed");
-    if (!m.pk_lt_qkv || !m.pk_lt_o || !m.pk_lt_ff1 || !m.pk_lt_ff2) return fail(dev, MP_ERR_HIP, "bf16 pack failed");
-    m.pk_lt_in = f16 ? pack(m.lt_in_w, 256, 768) : nullptr;
-    if (f16 && !m.pk_lt_in) return fail(dev, MP_ERR_HIP, "f16 pack failed");
-    HIPCHK(hipStreamSynchronize(dev->stream));
-    return MP_OK;
-}
-
-int load_model(mp_dev *dev, const char *path) {
-    mp::Gguf g;
-    std::string err;
-    if (!g.open(path, err)) return fail(dev, MP_ERR_IO, err);
-    mp::Model &m = dev->m;
-    // read_hparams (magpie.cpp:73-121): the reader's keys, struct defaults otherwise
-    if (g.get_u32("magpie.d_model", 768) != 768 || g.get_u32("magpie.d_ffn", 3072) != 3072 ||
-        g.get_u32("magpie.d_head", 64) != 64 || g.get_u32("magpie.dec_sa_heads", 12) != 12 ||
-        g.get_u32("magpie.dec_xa_heads", 1) != 1 || g.get_u32("magpie.dec_xa_d_head", 128) != 128 ||
-        g.get_u32("magpie.lt_dim", 256) != 256 || g.get_u32("magpie.lt_ffn_dim", 1024) != 1024 ||
-        g.get_u32("magpie.num_codebooks", 8) != 8 || g.get_u32("magpie.vocab_per_cb", 2024) != 2024 ||
-        g.get_u32("magpie.context_frames", 110) != 110 || g.get_u32("magpie.enc_heads", 12) != 12 ||
-        g.get_u32("magpie.enc_kernel", 3) != 3 || g.get_u32("magpie.dec_kernel", 1) != 1 ||
-        g.get_u32("magpie.lt_layers", 1) != 1 || g.get_u32("magpie.lt_heads", 1) != 1)
-        return fail(dev, MP_ERR_UNSUPPORTED, "model dimensions differ from Magpie-357M (kernels are specialised)");
-    m.enc_layers = (int)g.get_u32("magpie.enc_layers", 6);
-    m.dec_layers = (int)g.get_u32("magpie.dec_layers", 12);
-    m.n_spk = (int)g.get_u32("magpie.num_speakers", 5);
-    m.text_vocab = (int)g.get_u32("magpie.text_vocab_size", 2380);
-    m.audio_bos = (int)g.get_u32("magpie.audio_bos_id", 2016);
-    m.audio_eos = (int)g.get_u32("magpie.audio_eos_id", 2017);
-    // the kernels' forbidden-token mask is the range [bos, bos + 7] minus eos, which is
-    // the reference's explicit list (magpie.cpp:1133-1145) only when eos == bos + 1
-    if (m.audio_eos != m.audio_bos + 1 || m.audio_bos < 0 || m.audio_bos + 8 > mp::VCB)
-        return fail(dev, MP_ERR_UNSUPPORTED, "audio_eos_id must be audio_bos_id + 1 (forbidden-token layout)");
-    m.max_dec_steps = (int)g.get_u32("magpie.max_dec_steps", 500);
-    m.eps = (float)g.get_f32("magpie.eps", 1e-5);
-    if (m.enc_layers < 1 || m.dec_layers < 1 || m.enc_layers > 64 || m.dec_layers > 64)
-        return fail(dev, MP_ERR_FORMAT, "bad layer counts");
-
-    struct Want { std::string name; int64_t n; const float **dst; };
-    std::vector<Want> want;
-    auto need = [&](const std::string &name, int64_t n, const float **dst) { want.push_back({name, n, dst}); };
-    const int64_t D = 768;
-    need("text_embedding.weight", (int64_t)m.text_vocab * D, &m.text_emb);
-    need("encoder.position_embeddings.weight", -1, &m.enc_pos);
-    m.enc.assign(m.enc_layers, mp::EncLayerW{});
-    for (int l = 0; l < m.enc_layers; ++l) {
-        const std::string p = "encoder.layers." + std::to_string(l) + ".";
-        mp::EncLayerW &L = m.enc[l];
-        need(p + "norm_self.weight", D, &L.norm_self);
-        need(p + "self_attention.qkv_net.weight", 3 * D * D, &L.qkv);
-        need(p + "self_attention.o_net.weight", D * D, &L.o);
-        need(p + "norm_pos_ff.weight", D, &L.norm_ff);
-        need(p + "pos_ff.proj.conv.weight", 3072 * D * 3, &L.ff1);
-        need(p + "pos_ff.o_net.conv.weight", 3072 * D * 3, &L.ff2);
-    }
-    need("encoder.norm_out.weight", D, &m.enc_norm_out);
-    need("decoder.position_embeddings.weight", -1, &m.dec_pos);
-    m.dec.assign(m.dec_layers, mp::DecLayerW{});
-    for (int l = 0; l < m.dec_layers; ++l) {
-        const std::string p = "decoder.layers." + std::to_string(l) + ".";
-        mp::DecLayerW &L = m.dec[l];
-        need(p + "norm_self.weight", D, &L.norm_self);
-        need(p + "self_attention.qkv_net.weight", 3 * D * D, &L.qkv);
-        need(p + "self_attention.o_net.weight", D * D, &L.o);
-        need(p + "norm_xattn_query.weight", D, &L.norm_xq);
-        need(p + "cross_attention.q_net.weight", 128 * D, &L.xq);
-        need(p + "cross_attention.kv_net.weight", 256 * D, &L.xkv);
-        need(p + "cross_attention.o_net.weight", D * 128, &L.xo);
-        need(p + "norm_xattn_memory.weight", D, &L.norm_xmem);
-        need(p + "norm_pos_ff.weight", D, &L.norm_ff);
-        need(p + "pos_ff.proj.conv.weight", 3072 * D, &L.ff1);
-        need(p + "pos_ff.o_net.conv.weight", 3072 * D, &L.ff2);
-    }
-    need("decoder.norm_out.weight", D, &m.dec_norm_out);
-    need("baked_context_embedding.weight", -1, &m.baked);
-    need("local_transformer_in_projection.weight", 256 * D, &m.lt_in_w);
-    need("local_transformer_in_projection.bias", 256, &m.lt_in_b);
-    need("local_transformer.position_embeddings.weight", -1, &m.lt_pos);
-    need("local_transformer.layers.0.norm_self.weight", 256, &m.lt_norm_self);
-    need("local_transformer.layers.0.self_attention.qkv_net.weight", 768 * 256, &m.lt_qkv);
-    need("local_transformer.layers.0.self_attention.o_net.weight", 256 * 256, &m.lt_o);
-    need("local_transformer.layers.0.norm_pos_ff.weight", 256, &m.lt_norm_ff);
-    need("local_transformer.layers.0.pos_ff.proj.conv.weight", 1024 * 256, &m.lt_ff1);
-    need("local_transformer.layers.0.pos_ff.o_net.conv.weight", 1024 * 256, &m.lt_ff2);
-    // per-codebook tensors become one contiguous [8][...] array each so a kernel
-    // can index them by a codebook read from device memory
-    std::vector<std::string> grouped[3];
-    for (int c = 0; c < 8; ++c) {
-        grouped[0].push_back("audio_embeddings." + std::to_string(c) + ".weight");
-        grouped[1].push_back("local_transformer_out_projections." + std::to_string(c) + ".weight");
-        grouped[2].push_back("local_transformer_out_projections." + std::to_string(c) + ".bias");
-    }
-    const int64_t gsize[3] = {2024 * D, 2024 * 256, 2024};
-    const float **gdst[3] = {&m.audio_emb, &m.lt_out_w, &m.lt_out_b};
-
-    // size the arena
-    auto align_up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t total = 0;
-    for (auto &w : want) {
-        const mp::GgufTensor *t = g.find(w.name);
-        if (!t) return fail(dev, MP_ERR_FORMAT, "missing tensor " + w.name);
-        if (w.n >= 0 && t->nelements() != w.n) return fail(dev, MP_ERR_FORMAT, "unexpected shape for " + w.name);
-        total += align_up((size_t)t->nelements() * 4);
-    }
-    for (int k = 0; k < 3; ++k)
-        for (auto &nm : grouped[k]) {
-            const mp::GgufTensor *t = g.find(nm);
-            if (!t) return fail(dev, MP_ERR_FORMAT, "missing tensor " + nm);
-            if (t->nelements() != gsize[k]) return fail(dev, MP_ERR_FORMAT, "unexpected shape for " + nm);
-        }
-    for (int k = 0; k < 3; ++k) total += align_up((size_t)gsize[k] * 8 * 4);
-    {
-        const mp::GgufTensor *dp = g.find("decoder.position_embeddings.weight");
-        const mp::GgufTensor *bk = g.find("baked_context_embedding.weight");
-        const mp::GgufTensor *ep = g.find("encoder.position_embeddings.weight");
-        const mp::GgufTensor *lp = g.find("local_transformer.position_embeddings.weight");
-        if (dp->ne[0] != D || bk->ne[0] != 110 * D || ep->ne[0] != D || lp->ne[0] != 256 || lp->ne[1] < 8)
-            return fail(dev, MP_ERR_FORMAT, "unexpected embedding table shapes");
-        m.dec_pos_rows = (int)dp->ne[1];
-        m.n_spk = (int)std::min<int64_t>(m.n_spk, bk->ne[1]);
-    }
-    if (m.arena) { hipFree(m.arena); m.arena = nullptr; }
-    HIPCHK(hipMalloc(&m.arena, total));
-    m.arena_bytes = total;
-    std::vector<float> host;
-    size_t off = 0;
-    std::vector<float> tmp;
-    auto upload = [&](const mp::GgufTensor *t, float *dst) -> int {
-        host.resize((size_t)t->nelements());
-        if (!g.to_f32(*t, host.data())) return fail(dev, MP_ERR_FORMAT, "unsupported tensor type in " + t->name);
-        if (t->n_dims == 3 && t->ne[0] == 3 && t->name.rfind("encoder.layers.", 0) == 0) {
-            // causal k=3 conv weight [out][in][k] -> tap-major [out][k][in] (mp_prefill.hip loader)
-            const int64_t K = 3, Cin = t->ne[1], Co = t->ne[2];
-            tmp.resize(host.size());
-            for (int64_t o = 0; o < Co; ++o)
-                for (int64_t i = 0; i < Cin; ++i)
-                    for (int64_t k = 0; k < K; ++k) tmp[(o * K + k) * Cin + i] = host[(o * Cin + i) * K + k];
-            host.swap(tmp);
-        }
-        HIPCHK(hipMemcpy(dst, host.data(), host.size() * 4, hipMemcpyHostToDevice));
-        return MP_OK;
-    };
-    for (auto &w : want) {
-        const mp::GgufTensor *t = g.find(w.name);
-        float *dst = (float *)((char *)m.arena + off);
-        if (int rc = upload(t, dst)) return rc;
-        *w.dst = dst;
-        off += align_up((size_t)t->nelements() * 4);
-    }
-    for (int k = 0; k < 3; ++k) {
-        float *base = (float *)((char *)m.arena + off);
-        for (int c = 0; c < 8; ++c)
-            if (int rc = upload(g.find(grouped[k][c]), base + (size_t)c * gsize[k])) return rc;
-        *gdst[k] = base;
-        off += align_up((size_t)gsize[k] * 8 * 4);
-    }
-    // W_q^T per decoder layer (for the per-utterance K' = K W_q of the fused XA), one
-    // allocation, layer l at l * 768 * 128 (the batched K' GEMM strides over it)
-    if (!m.xq_t.empty() && m.xq_t[0]) hipFree(m.xq_t[0]);
-    m.xq_t.assign(m.dec_layers, nullptr);
-    {
-        std::vector<float> wq((size_t)128 * 768), wt((size_t)768 * 128);
-        float *all = nullptr;
-        HIPCHK(hipMalloc(&all, wt.size() * 4 * m.dec_layers));
-        for (int l = 0; l < m.dec_layers; ++l) {
-            HIPCHK(hipMemcpy(wq.data(), m.dec[l].xq, wq.size() * 4, hipMemcpyDeviceToHost));
-            for (int j = 0; j < 128; ++j)
-                for (int n = 0; n < 768; ++n) wt[(size_t)n * 128 + j] = wq[(size_t)j * 768 + n];
-            m.xq_t[l] = all + (size_t)l * wt.size();
-            HIPCHK(hipMemcpy(m.xq_t[l], wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
-        }
-    }
-    dev->loaded = true;
-    return MP_OK;
-}
-
-// f32 -> bf16 bits, round to nearest even (ggml_compute_fp32_to_bf16; finite weights)
-static unsigned short bf16_bits(float x) {
-    unsigned u;
-    memcpy(&u, &x, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 64);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-// f32 mode's LT (lt_ffn2_kernel) needs o_net applied to v rows ahead of time:
-// VO[c][v] = W_o V[c][v] for every table row, and [W_k ; W_o W_v] for position 0.
-bool f32_lt_mode(const mp::Model &m) { return m.weight_mode == MP_WEIGHTS_AS_STORED; }
-// the LT attention through the load-time q|k|vo tables in f32: the f32 mode, and the bf16
-// mode (whose LT FFN and heads are bf16: lt_slot_kernel + the bf16 head)
-bool lt_table_attn(const mp::Model &m) { return m.weight_mode == MP_WEIGHTS_AS_STORED || m.weight_mode == MP_WEIGHTS_BF16; }
-
-int build_vo_tables(mp_dev *dev) {
-    mp::Model &m = dev->m;
-    if (m.lt_votab) { hipFree(m.lt_votab); m.lt_votab = nullptr; }
-    if (m.lt_kvo) { hipFree(m.lt_kvo); m.lt_kvo = nullptr; }
-    const size_t R = (size_t)7 * 2024;
-    HIPCHK(hipMalloc(&m.lt_votab, R * 256 * 4));
-    mp::GemmP gp{};
-    gp.A = m.lt_qkvtab + 512; gp.lda = 768; gp.W = m.lt_o; gp.C = m.lt_votab; gp.ldc = 256;
-    gp.M = (int)R; gp.N = 256; gp.K = 256; gp.rows_per_utt = (int)R;
-    HIPCHK(mp::pre_gemm(gp, mp::GE_STORE, dev->stream));
-    std::vector<float> qkv((size_t)768 * 256), o((size_t)256 * 256), kvo((size_t)512 * 256);
-    HIPCHK(hipMemcpy(qkv.data(), m.lt_qkv, qkv.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(o.data(), m.lt_o, o.size() * 4, hipMemcpyDeviceToHost));
-    memcpy(kvo.data(), qkv.data() + (size_t)256 * 256, (size_t)256 * 256 * 4);  // W_k rows
-    for (int n = 0; n < 256; ++n)
-        for (int k = 0; k < 256; ++k) {
-            double acc = 0.0;
-            for (int j = 0; j < 256; ++j) acc += (double)o[(size_t)n * 256 + j] * qkv[(size_t)(512 + j) * 256 + k];
-            kvo[(size_t)(256 + n) * 256 + k] = (float)acc;
-        }
-    HIPCHK(hipMalloc(&m.lt_kvo, kvo.size() * 4));
-    HIPCHK(hipMemcpy(m.lt_kvo, kvo.data(), kvo.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipStreamSynchronize(dev->stream));
-    return MP_OK;
-}
-
-// P[c][v] = in_proj(audio_emb[c][v]) + b: the LT's per-codebook re-embedding
-// (magpie.cpp:1274-1313) depends only on (c, v) -> one GEMM at load time (with
-// ggml's Q8_0 arithmetic when in_proj is a Q8_0 tensor in Q8 mode).
-int build_ptab(mp_dev *dev, int weight_mode) {
-    mp::Model &m = dev->m;
-    if (m.lt_ptab) { hipFree(m.lt_ptab); m.lt_ptab = nullptr; }
-    HIPCHK(hipMalloc(&m.lt_ptab, (size_t)8 * 2024 * 256 * 4));
-    mp::GemmP gp{};
-    gp.A = m.audio_emb; gp.lda = 768; gp.W = m.lt_in_w; gp.Wq = m.lt_in8.q; gp.Wd = m.lt_in8.d; gp.bias = m.lt_in_b;
-    gp.C = m.lt_ptab; gp.ldc = 256; gp.M = 8 * 2024; gp.N = 256; gp.K = 768; gp.rows_per_utt = 8 * 2024;
-    gp.xround = weight_mode == MP_WEIGHTS_F16 ? 2 : 0;  // F16 in_proj: the embedding row rounded to f16
-    HIPCHK(mp::pre_gemm(gp, mp::GE_STORE, dev->stream));
-    // LT q|k|v of position c+1 for every code v of codebook c < 7: the rows PRO_LTARG_ATTN
-    // gathers instead of running the q|k|v GEMV per codebook. The projection uses the
-    // weights the decode-time GEMV would (f32, Q8_0 with activations quantised per
-    // block, or bf16 / f16 weights and activations, f32 accumulation).
-    if (m.lt_qkvtab) { hipFree(m.lt_qkvtab); m.lt_qkvtab = nullptr; }
-    const size_t R = (size_t)7 * 2024;
-    HIPCHK(hipMalloc(&m.lt_qkvtab, R * 768 * 4));
-    float *rows = nullptr, *wq = nullptr;
-    HIPCHK(hipMalloc(&rows, R * 256 * 4));
-    // the bf16 mode's LT attention is f32 (lt_table_attn); F16: the file's weights are already f16 values
-    const bool b16 = false;
-    HIPCHK(mp::pre_lt_tab_rows(m.lt_ptab, m.lt_pos, m.lt_norm_self, m.eps, rows,
-                               weight_mode == MP_WEIGHTS_F16 ? 2 : 0, dev->stream));
-    if (b16) {
-        HIPCHK(hipMalloc(&wq, (size_t)768 * 256 * 4));
-        HIPCHK(mp::pre_round_bf16(m.lt_qkv, wq, (size_t)768 * 256, dev->stream));
-    }
-    gp = mp::GemmP{};
-    gp.A = rows; gp.lda = 256; gp.W = b16 ? wq : m.lt_qkv; gp.Wq = m.lt_qkv8.q; gp.Wd = m.lt_qkv8.d;
-    gp.C = m.lt_qkvtab; gp.ldc = 768; gp.M = (int)R; gp.N = 768; gp.K = 256; gp.rows_per_utt = (int)R;
-    const hipError_t ge = mp::pre_gemm(gp, mp::GE_STORE, dev->stream);
-    const hipError_t se = hipStreamSynchronize(dev->stream);
-    hipFree(rows);
-    if (wq) hipFree(wq);
-    HIPCHK(ge);
-    HIPCHK(se);
-    if (!m.lt_ff2s) {
-        constexpr int U = 1024 / mp::LT_FFN_P;
-        std::vector<float> w2((size_t)256 * 1024), w2s(w2.size());
-        HIPCHK(hipMemcpy(w2.data(), m.lt_ff2, w2.size() * 4, hipMemcpyDeviceToHost));
-        for (int p = 0; p < mp::LT_FFN_P; ++p)
-            for (int n = 0; n < 256; ++n)
-                memcpy(&w2s[((size_t)p * 256 + n) * U], &w2[(size_t)n * 1024 + p * U], U * 4);
-        HIPCHK(hipMalloc(&m.lt_ff2s, w2s.size() * 4));
-        HIPCHK(hipMemcpy(m.lt_ff2s, w2s.data(), w2s.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (weight_mode == MP_WEIGHTS_BF16 && !m.lt_ff1h) {
-        std::vector<float> w1((size_t)1024 * 256), w2((size_t)256 * 1024);
-        HIPCHK(hipMemcpy(w1.data(), m.lt_ff1, w1.size() * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(w2.data(), m.lt_ff2, w2.size() * 4, hipMemcpyDeviceToHost));
-        constexpr int U = 1024 / mp::LTS_P;
-        std::vector<unsigned short> h1(w1.size()), h2(w2.size());
-        for (size_t i = 0; i < w1.size(); ++i) h1[i] = bf16_bits(w1[i]);
-        for (int q = 0; q < mp::LTS_P; ++q)
-            for (int n = 0; n < 256; ++n)
-                for (int u = 0; u < U; ++u) h2[((size_t)q * 256 + n) * U + u] = bf16_bits(w2[(size_t)n * 1024 + q * U + u]);
-        HIPCHK(hipMalloc(&m.lt_ff1h, h1.size() * 2));
-        HIPCHK(hipMemcpy(m.lt_ff1h, h1.data(), h1.size() * 2, hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc(&m.lt_ff2h, h2.size() * 2));
-        HIPCHK(hipMemcpy(m.lt_ff2h, h2.data(), h2.size() * 2, hipMemcpyHostToDevice));
-    }
-    if (weight_mode == MP_WEIGHTS_Q8 && !m.lt_ff2q) {
-        constexpr int U = 1024 / mp::LTQ_P;
-        std::vector<float> w2((size_t)256 * 1024), w2q(w2.size());
-        HIPCHK(hipMemcpy(w2.data(), m.lt_ff2, w2.size() * 4, hipMemcpyDeviceToHost));
-        for (int q = 0; q < mp::LTQ_P; ++q)
-            for (int n = 0; n < 256; ++n)
-                memcpy(&w2q[((size_t)q * 256 + n) * U], &w2[(size_t)n * 1024 + q * U], U * 4);
-        HIPCHK(hipMalloc(&m.lt_ff2q, w2q.size() * 4));
-        HIPCHK(hipMemcpy(m.lt_ff2q, w2q.data(), w2q.size() * 4, hipMemcpyHostToDevice));
-    }
-    return lt_table_attn(m) ? build_vo_tables(dev) : MP_OK;
-}
-
-// Weight mode MP_WEIGHTS_Q8: upload every block-quantised tensor the decode path
-// uses (scripts/convert_magpie_to_gguf.py:155-176 decides which: attention,
-// cross-attention and LT projections), repacked to int8 [N][K] + fp16 scales
-// [N][K/32] (34 B per 32 weights). Q8_0 blocks are copied; Q4_0 blocks
-// (convert_magpie_to_gguf.py:107-138: q in 0..15, byte j = q_j | q_{j+16} << 4) become
-// the int8 values q - 8 with the same scale, so the Q8_0 kernels compute exactly
-// ggml's vec_dot_q4_0_q8_0: the integer dot of (q - 8) with the Q8_0-quantised
-// activation times d_w * d_a. F32 tensors keep the f32 path.
-int load_q8(mp_dev *dev, const char *path) {
-    mp::Gguf g;
-    std::string err;
-    if (!g.open(path, err)) return fail(dev, MP_ERR_IO, err);
-    mp::Model &m = dev->m;
-    struct Item { const mp::GgufTensor *t; mp::QW *dst; int group; };
-    // a Q4_0 tensor's decode fragments stream its nibbles (MAGPIE_Q4_AS_Q8=1: as int8 q - 8,
-    // the same integers at 34 B per 32 weights; both compute the same bits)
-    const bool q4_nib = mp::env_int("MAGPIE_Q4_AS_Q8", 0) == 0;
-    std::vector<Item> items;
-    auto want = [&](const std::string &name, mp::QW *dst) {
-        const mp::GgufTensor *t = g.find(name);
-        if (t && (t->type == 8 || t->type == 2) && t->ne[0] % 32 == 0) items.push_back({t, dst, -1});
-    };
-    for (int l = 0; l < m.enc_layers; ++l) {
-        const std::string p = "encoder.layers." + std::to_string(l) + ".self_attention.";
-        want(p + "qkv_net.weight", &m.enc[l].qkv8);
-        want(p + "o_net.weight", &m.enc[l].o8);
-    }
-    for (int l = 0; l < m.dec_layers; ++l) {
-        const std::string p = "decoder.layers." + std::to_string(l) + ".";
-        want(p + "self_attention.qkv_net.weight", &m.dec[l].qkv8);
-        want(p + "self_attention.o_net.weight", &m.dec[l].o8);
-        want(p + "cross_attention.q_net.weight", &m.dec[l].xq8);
-        want(p + "cross_attention.kv_net.weight", &m.dec[l].xkv8);
-        want(p + "cross_attention.o_net.weight", &m.dec[l].xo8);
-    }
-    want("local_transformer_in_projection.weight", &m.lt_in8);
-    want("local_transformer.layers.0.self_attention.qkv_net.weight", &m.lt_qkv8);
-    want("local_transformer.layers.0.self_attention.o_net.weight", &m.lt_o8);
-    int nout = 0;
-    for (int c = 0; c < 8; ++c) {
-        const mp::GgufTensor *t = g.find("local_transformer_out_projections." + std::to_string(c) + ".weight");
-        if (t && (t->type == 8 || t->type == 2)) { items.push_back({t, &m.lt_out8, c}); ++nout; }
-    }
-    if (nout != 0 && nout != 8) return fail(dev, MP_ERR_UNSUPPORTED, "mixed quantised/F32 LT output projections");
-    if (items.empty()) return fail(dev, MP_ERR_UNSUPPORTED, "Q8 weight mode needs a GGUF with Q8_0 or Q4_0 tensors");
-    // the reassociated XA (K' = K W_q, V' = W_o V) is an f32 identity: with Q8_0
-    // q_net / o_net the activations must be quantised where ggml quantises them
-    for (int l = 0; l < m.dec_layers; ++l)
-        if ((bool)m.dec[l].xq8 != (bool)m.dec[l].xo8)
-            return fail(dev, MP_ERR_UNSUPPORTED, "cross-attention q_net / o_net must both be Q8_0 or both F32");
-    auto align_up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t total = 0;
-    for (auto &it : items) {
-        const size_t n = (size_t)it.t->nelements();
-        total += align_up(n) + align_up(n / 32 * 2);
-        if (it.dst == &m.lt_o8) total += align_up(n);  // the transposed copy
-    }
-    if (m.q8_arena) { hipFree(m.q8_arena); m.q8_arena = nullptr; }
-    HIPCHK(hipMalloc(&m.q8_arena, total));
-    m.q8_bytes = total;
-    char *cur = (char *)m.q8_arena;
-    std::vector<signed char> hq;
-    std::vector<unsigned short> hd;
-    signed char *out_q = nullptr;
-    unsigned short *out_d = nullptr;
-    const size_t out_n = (size_t)2024 * 256;
-    for (auto &it : items) {
-        const size_t n = (size_t)it.t->nelements();
-        const uint8_t *src = g.data(*it.t);
-        hq.resize(n);
-        hd.resize(n / 32);
-        for (size_t b = 0; b < n / 32; ++b) {
-            if (it.t->type == 8) {
-                memcpy(&hd[b], src + b * 34, 2);
-                memcpy(&hq[b * 32], src + b * 34 + 2, 32);
-            } else {  // Q4_0
-                const uint8_t *blk = src + b * 18;
-                memcpy(&hd[b], blk, 2);
-                for (int j = 0; j < 16; ++j) {
-                    hq[b * 32 + j] = (signed char)((blk[2 + j] & 0x0F) - 8);
-                    hq[b * 32 + j + 16] = (signed char)((blk[2 + j] >> 4) - 8);
-                }
-            }
-        }
-        signed char *dq;
-        unsigned short *dd;
-        if (it.group < 0) {
-            dq = (signed char *)cur; cur += align_up(n);
-            dd = (unsigned short *)cur; cur += align_up(n / 32 * 2);
-            it.dst->q = dq; it.dst->d = dd;
-            it.dst->nib = q4_nib && it.t->type == 2;
-        } else {  // the 8 LT heads as one [8][2024][256] array (indexed by a device codebook)
-            if (n != out_n) return fail(dev, MP_ERR_FORMAT, "unexpected LT output projection shape");
-            if (!out_q) {
-                out_q = (signed char *)cur; cur += align_up(8 * n);
-                out_d = (unsigned short *)cur; cur += align_up(8 * (n / 32) * 2);
-            }
-            dq = out_q + (size_t)it.group * n;
-            dd = out_d + (size_t)it.group * (n / 32);
-            it.dst->q = out_q; it.dst->d = out_d;
-            if (it.group == 0) it.dst->nib = q4_nib && it.t->type == 2;
-            else if (it.dst->nib != (int)(q4_nib && it.t->type == 2))
-                return fail(dev, MP_ERR_UNSUPPORTED, "mixed Q4_0 / Q8_0 LT output projections");
-        }
-        HIPCHK(hipMemcpy(dq, hq.data(), n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dd, hd.data(), n / 32 * 2, hipMemcpyHostToDevice));
-        if (it.dst == &m.lt_o8) {  // chunk i of row r at [i][r]: thread r's 16 loads coalesce across the wave
-            if (n != (size_t)256 * 256) return fail(dev, MP_ERR_FORMAT, "unexpected LT o_net shape");
-            std::vector<signed char> ht(n);
-            for (int r = 0; r < 256; ++r)
-                for (int i = 0; i < 16; ++i) memcpy(&ht[((size_t)i * 256 + r) * 16], &hq[(size_t)r * 256 + i * 16], 16);
-            signed char *dt = (signed char *)cur;
-            cur += align_up(n);
-            HIPCHK(hipMemcpy(dt, ht.data(), n, hipMemcpyHostToDevice));
-            m.lt_o8t = dt;
-        }
-    }
-    // the decode projections once more in int8 MFMA fragment order
-    struct Dec { mp::QW *w; int N, K, heads; };
-    std::vector<Dec> dec;
-    bool all = true;
-    auto add = [&](mp::QW &w, int N, int K, int heads) {
-        if (w) dec.push_back({&w, N, K, heads});
-        else all = false;
-    };
-    for (int l = 0; l < m.dec_layers; ++l) {
-        add(m.dec[l].qkv8, 2304, 768, 1);
-        add(m.dec[l].o8, 768, 768, 1);
-        add(m.dec[l].xq8, 128, 768, 1);
-        if (!m.dec[l].xo8) all = false;
-    }
-    add(m.lt_in8, 256, 768, 1);
-    add(m.lt_qkv8, 768, 256, 1);
-    add(m.lt_o8, 256, 256, 1);
-    add(m.lt_out8, 2024, 256, 8);
-    size_t ptotal = 0;
-    auto frag_bytes = [&](const Dec &d) {
-        return align_up(d.w->nib ? mp::q4p_qbytes(d.N, d.K) : mp::q8p_qbytes(d.N, d.K));
-    };
-    for (auto &d : dec) ptotal += d.heads * (frag_bytes(d) + align_up(mp::q8p_dbytes(d.N, d.K)));
-    if (m.q8p_arena) { hipFree(m.q8p_arena); m.q8p_arena = nullptr; }
-    if (ptotal) HIPCHK(hipMalloc(&m.q8p_arena, ptotal));
-    char *pc = (char *)m.q8p_arena;
-    for (auto &d : dec) {
-        const size_t qb = frag_bytes(d), db = align_up(mp::q8p_dbytes(d.N, d.K));
-        signed char *oq = (signed char *)pc;
-        pc += d.heads * qb;
-        unsigned short *od = (unsigned short *)pc;
-        pc += d.heads * db;
-        for (int h = 0; h < d.heads; ++h) {
-            const signed char *hq = d.w->q + (size_t)h * d.N * d.K;
-            // the scales (and, for Q8_0, the int8 fragments) in fragment order
-            HIPCHK(mp::pack_q8(hq, d.w->d + (size_t)h * d.N * (d.K / 32), d.N, d.K,
-                               d.w->nib ? nullptr : (unsigned char *)oq + h * qb,
-                               (unsigned short *)((char *)od + h * db), nullptr));
-            if (d.w->nib) HIPCHK(mp::pack_q4(hq, d.N, d.K, (unsigned char *)oq + h * qb, nullptr));
-        }
-        d.w->pq = oq;
-        d.w->pd = od;
-        d.w->head_q = qb;
-    }
-    HIPCHK(hipDeviceSynchronize());
-    m.q8_all = all;
-    return MP_OK;
-}
-// stride between the 8 packed LT heads' scales, as laid out above (fragments: QW::head_q)
-static size_t q8p_head_d() { return (mp::q8p_dbytes(2024, 256) + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------ batch state
 // the cross-attention form of a batch (mp_hip_set_xa_mode): direct where it reads fewer
 // bytes (Tmax > MP_XA_DIRECT_T); F16 keeps the reassociated form, Q8_0 has its own
@@ -833,6 +250,26 @@ bool want_xa_direct(const mp_dev *dev, int Tmax) {
 }
 
 static size_t enc_gpart_elems(size_t Me);
+// The preamble's split-K partial-sum capacity (elements) for Me rows of text, Mc rows of
+// context and L decoder layers: the largest S x M x N of its GEMMs (encoder FFN up/down,
+// prefill FFN)
+static size_t pre_gpart_elems(size_t Me, size_t Mc, int L) {
+    size_t cap = enc_gpart_elems(Me);
+    auto need = [&](size_t M, int N, int K) { cap = std::max(cap, (size_t)mp::gemm_splits_max(K) * M * N); };
+    need(Mc, 2304, 768); need(Mc, 3072, 768); need(Mc, 768, 3072); need(Mc, 768, 768);
+    need(Me, 256 * L, 768);  // the XA K/V GEMMs batched over layers
+    return cap;
+}
+// The preamble's scratch set {pX, pH, pQKV, pATT, pF, pXQ, pXAO, enc_out}: `rows` rows (text
+// or context, whichever is more) and enc_rows of encoder output; zero-filled on *zero when
+// given (the batch's buffers are)
+static hipError_t alloc_pre_scratch(mp::DevBlocks &mem, float **const (&p)[8], size_t rows, size_t enc_rows,
+                                    const hipStream_t *zero) {
+    const size_t n[8] = {rows * 768, rows * 768, rows * 3 * 768, rows * 768, rows * 3072, rows * 128, rows * 128, enc_rows * 768};
+    for (int i = 0; i < 8; ++i)
+        if (hipError_t e = zero ? mem.get_zeroed(p[i], n[i], *zero) : mem.get(p[i], n[i])) return e;
+    return hipSuccess;
+}
 int alloc_batch(mp_dev *dev, int B, int Tmax, int max_steps, bool trace) {
     free_batch(dev);
     const int NB = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16;
@@ -845,49 +282,43 @@ int alloc_batch(mp_dev *dev, int B, int Tmax, int max_steps, bool trace) {
     dev->nch = (dev->max_seq + mp::SA_CHUNK - 1) / mp::SA_CHUNK;
     dev->max_seq = dev->nch * mp::SA_CHUNK;  // whole chunks: attention loads never leave the cache slab
     const size_t D = 768;
-    int rc = MP_OK;
-#define A(ptr, n) if ((rc = dalloc(dev, &dev->ptr, (size_t)(n))) != MP_OK) return rc
+    const hipStream_t st = dev->stream;
+#define A(ptr, n) HIPCHK(dev->mem.get_zeroed(&dev->ptr, (size_t)(n), st))
+    // a hand-off granule buffer: noted with its size for reset_decode_state
+#define G(ptr, n) do { A(ptr, n); dev->granules.push_back({dev->ptr, (size_t)(n)}); } while (0)
     // this batch's KV width and XA form first: the allocations below depend on them
     // (a batch must never inherit the previous batch's form)
     dev->kv16 = dev->kv_mode == MP_KV_BF16;
     dev->xa_direct = want_xa_direct(dev, Tmax);
     A(x, NB * D); A(x2, NB * D); A(q, NB * D);
-    if (!dev->xa_direct) { A(kp, (size_t)NB * L * Tmax * D); A(vp, (size_t)NB * L * Tmax * D); }
-    else dev->kp = dev->vp = nullptr;
+    if (!dev->xa_direct) { A(kp, (size_t)NB * L * Tmax * D); A(vp, (size_t)NB * L * Tmax * D); }  // else null (free_batch)
     A(sa_out, NB * 768);
     A(h, NB * 3072); A(hidden, NB * D); A(xqb, NB * 128); A(h_b16, NB * 3072);
     A(sa_part, (size_t)NB * mp::NH * mp::SA_SPLITS * mp::SA_PART); A(xa_part, (size_t)NB * mp::XA_SPLITS * mp::XA_PART);
-    A(sagh, (size_t)NB * mp::NH * mp::SA_SPLITS * mp::SA_PART); A(xagh, (size_t)NB * mp::XA_SPLITS * mp::XA_PART);
-    A(kgh, (size_t)2 * (768 / 16) * mp::KGH_MAX_KS * 256);  // [O-projection | FFN down]
-    A(xh, (size_t)NB * D); A(qh, (size_t)NB * 3 * D); A(xqh, (size_t)NB * 128);
+    G(sagh, (size_t)NB * mp::NH * mp::SA_SPLITS * mp::SA_PART); G(xagh, (size_t)NB * mp::XA_SPLITS * mp::XA_PART);
+    G(kgh, (size_t)2 * (768 / 16) * mp::KGH_MAX_KS * 256);  // [O-projection | FFN down]
+    G(xh, (size_t)NB * D); G(qh, (size_t)NB * 3 * D); G(xqh, (size_t)NB * 128);
     const size_t kvn = (size_t)NB * L * dev->max_seq * D;  // elements; bf16 mode: 2 per float slot
     A(kc, dev->kv16 ? kvn / 2 : kvn); A(vc, dev->kv16 ? kvn / 2 : kvn);
     A(xak, (size_t)NB * L * Tmax * 128); A(xav, (size_t)NB * L * Tmax * 128);
     A(lt_s, NB * 9 * 256); A(ltX, NB * 256); A(ltY, NB * 256); A(lty2, NB * 256); A(ltq, NB * 256);
     A(ltk, NB * 8 * 256); A(ltv, NB * 8 * 256); A(ltf, NB * 1024); A(logits, NB * 2024);
-    A(ltp, (size_t)NB * std::max({mp::LT_FFN_P, mp::LTS_P, mp::LTQ_P}) * 256); A(ltgh, (size_t)NB * std::max(mp::LTS_P, mp::LTQ_P) * 256); A(ltfg, mp::LTFG_TOTAL); A(ltyg, (size_t)NB * 256);
+    A(ltp, (size_t)NB * std::max({mp::LT_FFN_P, mp::LTS_P, mp::LTQ_P}) * 256); G(ltgh, (size_t)NB * std::max(mp::LTS_P, mp::LTQ_P) * 256); G(ltfg, mp::LTFG_TOTAL); G(ltyg, (size_t)NB * 256);
     if (trace) A(trace, (size_t)NB * (max_steps + 1) * D);
     A(T, NB); A(spk, NB); A(pos, NB); A(step, NB); A(done, NB); A(nframes, NB); A(ndone, 4);  // ndone: [done count, iteration, hand-off timeout, -]
     A(argeos, NB); A(amax, NB * 8); A(smpcfg, 1);
     A(codes_cur, NB * 8); A(codes_prev, NB * 8); A(codes_out, (size_t)NB * max_steps * 8); A(tok, (size_t)NB * Tmax);
-    const size_t rows = (size_t)NB * std::max(Tmax, mp::CTX);
-    A(pX, rows * D); A(pH, rows * D); A(pQKV, rows * 3 * D); A(pATT, rows * D); A(pF, rows * 3072);
-    A(pXQ, rows * 128); A(pXAO, rows * 128); A(enc_out, (size_t)NB * Tmax * D);
-    {   // largest S x M x N of the preamble GEMMs (encoder FFN up/down, prefill FFN)
-        const size_t Me = (size_t)NB * Tmax, Mc = (size_t)NB * mp::CTX;
-        size_t cap = enc_gpart_elems(Me);
-        auto need = [&](size_t M, int N, int K) { cap = std::max(cap, (size_t)mp::gemm_splits_max(K) * M * N); };
-        need(Mc, 2304, 768); need(Mc, 3072, 768); need(Mc, 768, 3072); need(Mc, 768, 768);
-        need(Me, 256 * L, 768);  // the XA K/V GEMMs batched over layers
-        A(gpart, cap);
-    }
+    float **const pre[8] = {&dev->pX, &dev->pH, &dev->pQKV, &dev->pATT, &dev->pF, &dev->pXQ, &dev->pXAO, &dev->enc_out};
+    HIPCHK(alloc_pre_scratch(dev->mem, pre, (size_t)NB * std::max(Tmax, mp::CTX), (size_t)NB * Tmax, &st));
+    A(gpart, pre_gpart_elems((size_t)NB * Tmax, (size_t)NB * mp::CTX, L));
     if (mp::env_int("MAGPIE_Q8DUMP", 0) != 0 && dev->m.weight_mode == MP_WEIGHTS_Q8) {
         // the largest launch: K = 768, N = 2304 (QKV): rows, blocks, d, dots
         const size_t slot = ((size_t)NB * 768 * 5 + (size_t)NB * 24 * 4 + (size_t)2304 * 24 * NB * 4 + 255) / 256 * 256;
         dev->q8dump_cap = 4 * L + 16;
         dev->q8dump_slot = slot;
-        if ((rc = dalloc(dev, &dev->q8dump, slot * dev->q8dump_cap)) != MP_OK) return rc;
+        A(q8dump, slot * dev->q8dump_cap);
     }
+#undef G
 #undef A
     return MP_OK;
 }
@@ -1023,11 +454,11 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
     auto head = [&](int cb, mp::GemvFn fn, bool merged, int src_elems) {
         mp::GemvP g = base(cb);
         g.W = m.lt_out_w + (size_t)cb * 2024 * 256; g.N = 2024; g.bias = m.lt_out_b + (size_t)cb * 2024;
-        g.Wb = b16 ? m.pk_lt_out + (size_t)cb * pk_elems(2024, 256) : nullptr;
+        g.Wb = b16 ? m.pk_lt_out + (size_t)cb * mp::pk_elems(2024, 256) : nullptr;
         g.src = io.lty2; g.src_ld = 256; g.out = io.logits; g.out_ld = 2024;
         if (m.lt_out8) {
             g.Wq = m.lt_out8.pq + (size_t)cb * m.lt_out8.head_q; g.q4 = m.lt_out8.nib;
-            g.Wd = (const unsigned short *)((const char *)m.lt_out8.pd + (size_t)cb * q8p_head_d());
+            g.Wd = (const unsigned short *)((const char *)m.lt_out8.pd + (size_t)cb * mp::q8p_head_d());
         }
         if (merged) { g.part = io.ltp; g.addsrc = io.ltY; }
         return e.gemv("lt_e", fn, g,
@@ -1631,8 +1062,7 @@ int mp_hip_init(int device, mp_dev **out) {
     int least = 0, greatest = 0;
     const bool prio = mp::env_int("MAGPIE_STREAM_PRIO", 1) != 0;
     if (hipSetDevice(device) != hipSuccess || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
-        hipStreamCreateWithPriority(&dev->stream, hipStreamNonBlocking, prio ? greatest : 0) != hipSuccess ||
-        hipHostMalloc((void **)&dev->h_ndone, 64, 0) != hipSuccess) {
+        dev->stream.create(prio ? greatest : 0) != hipSuccess || dev->h_ndone.reserve(64) != hipSuccess) {
         delete dev;
         return MP_ERR_HIP;
     }
@@ -1648,47 +1078,13 @@ int mp_hip_load_model_ex(mp_dev *dev, const char *path, int weight_mode) {
     HIPCHK(hipSetDevice(dev->device));
     free_batch(dev);
     free_stage(dev);  // sized for the previous model's layers
+    // the old model goes before the new one is allocated (peak memory: one model); from here
+    // to a completed load the handle holds an empty Model
     dev->loaded = false;
-    dev->m.weight_mode = MP_WEIGHTS_AS_STORED;
-    // drop the Q8_0 views of a previous model
-    if (dev->m.q8_arena) { hipFree(dev->m.q8_arena); dev->m.q8_arena = nullptr; dev->m.q8_bytes = 0; }
-    if (dev->m.q8p_arena) { hipFree(dev->m.q8p_arena); dev->m.q8p_arena = nullptr; }
-    dev->m.q8_all = false;
-    dev->m.lt_in8 = dev->m.lt_qkv8 = dev->m.lt_o8 = dev->m.lt_out8 = mp::QW{};
-    dev->m.lt_o8t = nullptr;
-    dev->m.pk_lt_in = nullptr;  // set again by an F16 load
-    // derived LT weight layouts of a previous model (rebuilt by build_ptab)
-    for (void **pp : {(void **)&dev->m.lt_ff2s, (void **)&dev->m.lt_ff1h, (void **)&dev->m.lt_ff2h, (void **)&dev->m.lt_ff2q})
-        if (*pp) { hipFree(*pp); *pp = nullptr; }
-    if (weight_mode == MP_WEIGHTS_Q8 || weight_mode == MP_WEIGHTS_F16) {  // cheap header check before any upload
-        mp::Gguf g;
-        std::string err;
-        if (!g.open(path, err)) return fail(dev, MP_ERR_IO, err);
-        const mp::GgufTensor *t = g.find("decoder.layers.0.self_attention.qkv_net.weight");
-        if (weight_mode == MP_WEIGHTS_Q8 && (!t || (t->type != 8 && t->type != 2)))
-            return fail(dev, MP_ERR_UNSUPPORTED, "Q8 weight mode needs a GGUF with Q8_0 or Q4_0 tensors");
-        // every tensor the F16 mode streams as f16 must be stored F16 (the converter's
-        // pattern set, convert_magpie_to_gguf.py:155-176, 311-327)
-        if (weight_mode == MP_WEIGHTS_F16)
-            for (const auto &kv : g.tensors()) {
-                const std::string &n = kv.first;
-                const bool proj = n.find(".self_attention.") != std::string::npos ||
-                                  n.find(".pos_ff.") != std::string::npos ||
-                                  n.find("local_transformer_out_projections.") == 0 ||
-                                  n == "local_transformer_in_projection.weight";
-                if (proj && n.size() > 7 && n.compare(n.size() - 7, 7, ".weight") == 0 && kv.second.type != 1)
-                    return fail(dev, MP_ERR_UNSUPPORTED, "F16 weight mode needs a GGUF with F16 projections (" + n + ")");
-            }
-    }
-    if (int rc = load_model(dev, path)) return rc;
-    dev->loaded = false;
-    if (weight_mode == MP_WEIGHTS_BF16 || weight_mode == MP_WEIGHTS_F16) {
-        if (int rc = pack_weights(dev, weight_mode == MP_WEIGHTS_F16)) return rc;
-    } else if (weight_mode == MP_WEIGHTS_Q8) {
-        if (int rc = load_q8(dev, path)) return rc;
-    }
-    dev->m.weight_mode = weight_mode;  // the load-time LT tables depend on it
-    if (int rc = build_ptab(dev, weight_mode)) return rc;
+    dev->m = mp::Model{};
+    mp::Model m;
+    if (int rc = mp::load_model(path, weight_mode, dev->stream, m, dev->err)) return rc;
+    dev->m = std::move(m);
     dev->loaded = true;
     return MP_OK;
 }
@@ -1725,29 +1121,8 @@ void mp_hip_free(mp_dev *dev) {
     if (!dev) return;
     hipSetDevice(dev->device);
     if (dev->stream) hipStreamSynchronize(dev->stream);
-    free_batch(dev);
-    free_stage(dev);
-    if (dev->side) hipStreamDestroy(dev->side);
-    if (dev->m.arena) hipFree(dev->m.arena);
-    if (dev->m.lt_ptab) hipFree(dev->m.lt_ptab);
-    if (dev->m.lt_qkvtab) hipFree(dev->m.lt_qkvtab);
-    if (dev->m.lt_votab) hipFree(dev->m.lt_votab);
-    if (dev->m.lt_kvo) hipFree(dev->m.lt_kvo);
-    if (dev->m.lt_ff2s) hipFree(dev->m.lt_ff2s);
-    if (dev->m.lt_ff1h) hipFree(dev->m.lt_ff1h);
-    if (dev->m.lt_ff2h) hipFree(dev->m.lt_ff2h);
-    if (dev->m.lt_ff2q) hipFree(dev->m.lt_ff2q);
-    if (dev->m.pk_arena) hipFree(dev->m.pk_arena);
-    if (dev->m.q8_arena) hipFree(dev->m.q8_arena);
-    if (dev->m.q8p_arena) hipFree(dev->m.q8p_arena);
-    for (void *p : dev->ltio_allocs) hipFree(p);
-    if (!dev->m.xq_t.empty() && dev->m.xq_t[0]) hipFree(dev->m.xq_t[0]);  // one allocation (load_model)
-    if (dev->h_ndone) hipHostFree(dev->h_ndone);
-    for (hipEvent_t e : dev->sev)
-        if (e) hipEventDestroy(e);
-    if (dev->h_codes) hipHostFree(dev->h_codes);
-    if (dev->enc_ws) hipFree(dev->enc_ws);
-    if (dev->stream) hipStreamDestroy(dev->stream);
+    if (dev->side) hipStreamSynchronize(dev->side);
+    free_batch(dev);  // the graph; every owner releases in ~mp_dev, the streams last
     delete dev;
 }
 
@@ -1856,10 +1231,10 @@ int mp_hip_encode_text(mp_dev *dev, const int32_t *tokens, int n_tokens, float *
         // the old workspace may still be read by this stream's earlier encode: wait for it
         // (the stream only, not the device) before it goes
         HIPCHK(hipStreamSynchronize(dev->stream));
-        if (dev->enc_ws) hipFree(dev->enc_ws);
+        dev->enc_ws_mem.clear();
         dev->enc_ws = nullptr;
         dev->enc_ws_bytes = 0;
-        HIPCHK(hipMalloc(&dev->enc_ws, need));
+        HIPCHK(dev->enc_ws_mem.bytes(&dev->enc_ws, need));
         dev->enc_ws_bytes = need;
     }
     char *ws = dev->enc_ws;
@@ -1897,15 +1272,7 @@ int reset_decode_state(mp_dev *dev) {
     HIPCHK(hipMemsetAsync(dev->codes_out, 0, (size_t)NB * dev->max_steps * 8 * 4, dev->stream));
     HIPCHK(hipMemsetAsync(dev->argeos, 0, NB * 4, dev->stream));
     // hand-off tags restart with the iteration counter (ndone[1]): no stale tag may match
-    HIPCHK(hipMemsetAsync(dev->xh, 0, (size_t)NB * 768 * 8, dev->stream));
-    HIPCHK(hipMemsetAsync(dev->qh, 0, (size_t)NB * 3 * 768 * 8, dev->stream));
-    HIPCHK(hipMemsetAsync(dev->xqh, 0, (size_t)NB * 128 * 8, dev->stream));
-    HIPCHK(hipMemsetAsync(dev->ltgh, 0, (size_t)NB * std::max(mp::LTS_P, mp::LTQ_P) * 256 * 8, dev->stream));
-    HIPCHK(hipMemsetAsync(dev->ltfg, 0, mp::LTFG_TOTAL * 8, dev->stream));
-    HIPCHK(hipMemsetAsync(dev->ltyg, 0, (size_t)NB * 256 * 8, dev->stream));
-    HIPCHK(hipMemsetAsync(dev->sagh, 0, (size_t)NB * mp::NH * mp::SA_SPLITS * mp::SA_PART * 8, dev->stream));
-    HIPCHK(hipMemsetAsync(dev->xagh, 0, (size_t)NB * mp::XA_SPLITS * mp::XA_PART * 8, dev->stream));
-    HIPCHK(hipMemsetAsync(dev->kgh, 0, (size_t)2 * (768 / 16) * mp::KGH_MAX_KS * 256 * 8, dev->stream));
+    for (const auto &g : dev->granules) HIPCHK(hipMemsetAsync(g.first, 0, g.second * 8, dev->stream));
     // the first frame's decoder input (the BOS codes); later frames' by lt_finalize_kernel
     HIPCHK(mp::op_embed(mp::EmbP{dev->m.audio_emb, dev->codes_prev, dev->m.dec_pos, dev->pos, dev->x}, NB, dev->stream));
     // the host copies are stack/heap temporaries: finish the uploads before they go
@@ -1974,9 +1341,9 @@ int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames) {
     HIPCHK(hipSetDevice(dev->device));
     const int NB = dev->NB, B = dev->B;
     if (int rc = prepare_iteration(dev)) return rc;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    mp::Event e0, e1;
+    HIPCHK(e0.create());
+    HIPCHK(e1.create());
     HIPCHK(hipEventRecord(e0, dev->stream));
     // one graph replay per frame: capturing 4 to 64 iterations per graph measured the same
     // frames/s (2619 vs 2617-2626, tools_dev/graph_iters_ab.py), replay boundaries cost nothing
@@ -1986,17 +1353,15 @@ int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames) {
         if (int rc = launch_iteration(dev)) return rc;
         ++it;
         if (!dev->params.ignore_eos && it % poll == 0 && it < dev->max_steps) {
-            HIPCHK(hipMemcpyAsync(dev->h_ndone, dev->ndone, 4, hipMemcpyDeviceToHost, dev->stream));
+            HIPCHK(hipMemcpyAsync(dev->h_ndone.p, dev->ndone, 4, hipMemcpyDeviceToHost, dev->stream));
             HIPCHK(hipStreamSynchronize(dev->stream));
-            if (*dev->h_ndone >= NB) break;
+            if (*dev->h_ndone.as<int>() >= NB) break;
         }
     }
     HIPCHK(hipEventRecord(e1, dev->stream));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     if (int rc = check_handoff(dev)) return rc;
     std::vector<int> h_nf(NB);
     HIPCHK(hipMemcpy(h_nf.data(), dev->nframes, NB * 4, hipMemcpyDeviceToHost));
@@ -2029,43 +1394,33 @@ static bool batch_reads_kp(const mp_dev *dev) {
 static int ensure_stage(mp_dev *dev, int tmax) {
     if (dev->stage_tmax == tmax && dev->stage_kv16 == dev->kv16 && dev->stage_direct == dev->xa_direct) return MP_OK;
     free_stage(dev);
-    if (!dev->side) HIPCHK(hipStreamCreateWithFlags(&dev->side, hipStreamNonBlocking));
-    const size_t L = dev->m.dec_layers, D = 768, T = tmax, rows = std::max(tmax, (int)mp::CTX);
+    HIPCHK(dev->side.create());
+    const size_t L = dev->m.dec_layers, D = 768, T = tmax;
     const int smax_seq = (mp::CTX + mp::SA_CHUNK - 1) / mp::SA_CHUNK * mp::SA_CHUNK;
-    size_t gcap = enc_gpart_elems(T);
-    auto need = [&](size_t M, int N, int K) { gcap = std::max(gcap, (size_t)mp::gemm_splits_max(K) * M * N); };
-    need(mp::CTX, 2304, 768); need(mp::CTX, 3072, 768); need(mp::CTX, 768, 3072); need(mp::CTX, 768, 768);
-    need(T, 256 * (int)L, 768);
-    for (StageWs &s : dev->stage) {
-        auto al = [&](auto **p, size_t n) -> int {  // n 4-byte elements
-            void *v = nullptr;
-            HIPCHK(hipMalloc(&v, n * 4 + 256));
-            s.allocs.push_back(v);
-            *p = (std::remove_reference_t<decltype(**p)> *)v;
-            return MP_OK;
-        };
+    const size_t kvn = L * smax_seq * D / (dev->kv16 ? 2 : 1);
+    // (not zero-filled: the preamble writes every row the install reads)
+    auto fill = [&](StageWs &s) -> hipError_t {
         PreWs &w = s.w;
-        int rc = MP_OK;
-        const size_t kvn = L * smax_seq * D / (dev->kv16 ? 2 : 1);
-        if ((rc = al(&s.tok, T)) || (rc = al(&s.T, 1)) || (rc = al(&s.spk, 1)) || (rc = al(&w.pX, rows * D)) ||
-            (rc = al(&w.pH, rows * D)) || (rc = al(&w.pQKV, rows * 3 * D)) || (rc = al(&w.pATT, rows * D)) ||
-            (rc = al(&w.pF, rows * 3072)) || (rc = al(&w.pXQ, rows * 128)) || (rc = al(&w.pXAO, rows * 128)) ||
-            (rc = al(&w.gpart, gcap)) || (rc = al(&w.enc_out, T * D)) || (rc = al(&w.xak, L * T * 128)) ||
-            (rc = al(&w.xav, L * T * 128)) || (rc = al(&w.kc, kvn)) || (rc = al(&w.vc, kvn)) ||
-            (batch_reads_kp(dev) && ((rc = al(&w.kp, L * T * D)) || (rc = al(&w.vp, L * T * D))))) {
-            free_stage(dev);
-            return rc;
-        }
+        float **const pre[8] = {&w.pX, &w.pH, &w.pQKV, &w.pATT, &w.pF, &w.pXQ, &w.pXAO, &w.enc_out};
+        hipError_t e;
+        if ((e = s.mem.get(&s.tok, T)) || (e = s.mem.get(&s.T, 1)) || (e = s.mem.get(&s.spk, 1)) ||
+            (e = alloc_pre_scratch(s.mem, pre, std::max(tmax, (int)mp::CTX), T, nullptr)) ||
+            (e = s.mem.get(&w.gpart, pre_gpart_elems(T, mp::CTX, (int)L))) || (e = s.mem.get(&w.xak, L * T * 128)) ||
+            (e = s.mem.get(&w.xav, L * T * 128)) || (e = s.mem.get(&w.kc, kvn)) || (e = s.mem.get(&w.vc, kvn)) ||
+            (batch_reads_kp(dev) && ((e = s.mem.get(&w.kp, L * T * D)) || (e = s.mem.get(&w.vp, L * T * D)))) ||
+            (e = s.pin.reserve((T + 2) * 4)) || (e = s.ready.create(hipEventDisableTiming)) ||
+            (e = s.installed.create(hipEventDisableTiming)))
+            return e;
         w.tok = s.tok; w.T = s.T; w.spk = s.spk;
         w.NB = 1; w.Tmax = tmax; w.max_seq = smax_seq; w.kv16 = dev->kv16; w.xa_direct = dev->xa_direct;
         w.stream = dev->side;
-        if (hipHostMalloc((void **)&s.h, (T + 2) * 4, 0) != hipSuccess ||
-            hipEventCreateWithFlags(&s.ready, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s.installed, hipEventDisableTiming) != hipSuccess) {
+        return hipSuccess;
+    };
+    for (StageWs &s : dev->stage)
+        if (hipError_t e = fill(s)) {
             free_stage(dev);
-            return fail(dev, MP_ERR_HIP, "slot pool: staging workspace allocation failed");
+            return fail(dev, MP_ERR_HIP, std::string("slot pool: staging workspace allocation failed: ") + hipGetErrorString(e));
         }
-    }
     dev->stage_tmax = tmax;
     dev->stage_kv16 = dev->kv16;
     dev->stage_direct = dev->xa_direct;
@@ -2083,8 +1438,8 @@ struct PoolRun {
     int seq = 0;
     bool drained = false;
     std::vector<char> claimed;
-    int32_t *h = nullptr;  // pinned: [ndone 4 | done 16 | nframes 16 | codes max_steps x 8]
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    mp::Pinned h;  // [ndone 4 | done 16 | nframes 16 | codes max_steps x 8]
+    mp::Event e0, e1;
     mp_queue_stats st{};
 };
 // the next utterance to run (-1: drained; out: MP_OK or an error)
@@ -2107,12 +1462,13 @@ static int pool_stage(mp_dev *dev, PoolRun &r, StageWs &s, int utt) {
         s.install_pending = false;
     }
     const int n = r.n_tokens[utt];
-    memcpy(s.h, r.tokens + (size_t)utt * r.tmax, (size_t)n * 4);
-    s.h[r.tmax] = n;
-    s.h[r.tmax + 1] = r.speaker[utt];
-    HIPCHK(hipMemcpyAsync(s.tok, s.h, (size_t)n * 4, hipMemcpyHostToDevice, dev->side));
-    HIPCHK(hipMemcpyAsync(s.T, s.h + r.tmax, 4, hipMemcpyHostToDevice, dev->side));
-    HIPCHK(hipMemcpyAsync(s.spk, s.h + r.tmax + 1, 4, hipMemcpyHostToDevice, dev->side));
+    int32_t *const h = s.pin.as<int32_t>();
+    memcpy(h, r.tokens + (size_t)utt * r.tmax, (size_t)n * 4);
+    h[r.tmax] = n;
+    h[r.tmax + 1] = r.speaker[utt];
+    HIPCHK(hipMemcpyAsync(s.tok, h, (size_t)n * 4, hipMemcpyHostToDevice, dev->side));
+    HIPCHK(hipMemcpyAsync(s.T, h + r.tmax, 4, hipMemcpyHostToDevice, dev->side));
+    HIPCHK(hipMemcpyAsync(s.spk, h + r.tmax + 1, 4, hipMemcpyHostToDevice, dev->side));
     PreWs w = s.w;
     w.Tmax = n;
     if (int rc = run_preamble(dev, w)) return rc;
@@ -2174,8 +1530,8 @@ static int pool_run(mp_dev *dev, PoolRun &r) {
     dev->batch_ready = false;  // the pool owns the batch: mp_hip_decode needs a new mp_hip_begin_batch
     if (int rc = prepare_iteration(dev)) return rc;
     const int NB = dev->NB, S = dev->max_steps;
-    HIPCHK(hipHostMalloc((void **)&r.h, (size_t)(36 + S * 8) * 4, 0));
-    int32_t *h_nd = r.h, *h_done = r.h + 4, *h_nf = r.h + 20, *h_codes = r.h + 36;
+    HIPCHK(r.h.reserve((size_t)(36 + S * 8) * 4));
+    int32_t *h_nd = r.h.as<int32_t>(), *h_done = h_nd + 4, *h_nf = h_nd + 20, *h_codes = h_nd + 36;
     // one utterance is always staged ahead while any remain
     int cur = 0;  // the staging workspace the next install reads
     bool staged = false;
@@ -2190,8 +1546,8 @@ static int pool_run(mp_dev *dev, PoolRun &r) {
         return MP_OK;
     };
     if (int rc = stage_next(0)) return rc;
-    HIPCHK(hipEventCreate(&r.e0));
-    HIPCHK(hipEventCreate(&r.e1));
+    HIPCHK(r.e0.create());
+    HIPCHK(r.e1.create());
     HIPCHK(hipEventRecord(r.e0, dev->stream));
     int it = 0, live = B;
     // every utterance leaves its slot within max_steps iterations and a poll round
@@ -2256,16 +1612,13 @@ int mp_hip_decode_queue(mp_dev *dev, const int32_t *tokens, const int32_t *n_tok
     if (int rc = check_params(dev, params, &max_steps)) return rc;
     if (int rc = check_utterances(dev, tokens, n_tokens, speaker, N, tmax, &Tmax)) return rc;
     HIPCHK(hipSetDevice(dev->device));
-    PoolRun r{tokens, n_tokens, speaker, N, tmax, slots, poll > 0 ? poll : 8, *params, next, done, user};
+    PoolRun r{tokens, n_tokens, speaker, N, tmax, slots, poll > 0 ? poll : 8, *params, next, done, user};  // released on return
     r.claimed.assign(N, 0);
     const int rc = pool_run(dev, r);
     // nothing of this run stays in flight, whatever its end: a refused call leaves the device usable
     hipStreamSynchronize(dev->stream);
     if (dev->side) hipStreamSynchronize(dev->side);
     for (StageWs &s : dev->stage) { s.install_pending = false; s.utt = -1; }
-    if (r.h) hipHostFree(r.h);
-    if (r.e0) hipEventDestroy(r.e0);
-    if (r.e1) hipEventDestroy(r.e1);
     if (rc == MP_OK && stats) *stats = r.st;
     return rc;
 }
@@ -2296,19 +1649,11 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
     HIPCHK(hipSetDevice(dev->device));
     const int NB = dev->NB, B = dev->B, S = dev->max_steps;
     if (int rc = prepare_iteration(dev)) return rc;
-    if (!dev->sev[0]) {
-        HIPCHK(hipEventCreateWithFlags(&dev->sev[0], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&dev->sev[1], hipEventDisableTiming));
-    }
+    for (mp::Event &e : dev->sev) HIPCHK(e.create(hipEventDisableTiming));
     // pinned: a copy into pageable memory would block the host until the chunk's kernels finish
-    if (dev->h_codes_n < (size_t)NB * S * 8 + 6 * NB) {
-        if (dev->h_codes) hipHostFree(dev->h_codes);
-        dev->h_codes = nullptr;
-        dev->h_codes_n = 0;
-        HIPCHK(hipHostMalloc((void **)&dev->h_codes, ((size_t)NB * S * 8 + 6 * NB) * 4, hipHostMallocDefault));
-        dev->h_codes_n = (size_t)NB * S * 8 + 6 * NB;
-    }
-    int *const snap = dev->h_codes + (size_t)NB * S * 8;  // two snapshots of (step, done, nframes)
+    HIPCHK(dev->h_codes_pin.reserve(((size_t)NB * S * 8 + 6 * NB) * 4));
+    int32_t *const h_codes = dev->h_codes_pin.as<int32_t>();
+    int *const snap = h_codes + (size_t)NB * S * 8;  // two snapshots of (step, done, nframes)
     auto t0 = std::chrono::steady_clock::now();
     // two snapshots of (step, done, nframes): the host reads one while the next chunk's land in the other
     std::vector<int> delivered(B, 0), stopped(B, 0), ended(B, 0);
@@ -2325,7 +1670,7 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
             if (int rc = launch_iteration(dev, st)) return rc;
         // the frames these iterations wrote (columns it..it+n_it of every slot) to the
         // pinned mirror, on the decode stream: no host copy waits on the GPU later
-        HIPCHK(hipMemcpy2DAsync(dev->h_codes + (size_t)it * 8, (size_t)S * 32, dev->codes_out + (size_t)it * 8,
+        HIPCHK(hipMemcpy2DAsync(h_codes + (size_t)it * 8, (size_t)S * 32, dev->codes_out + (size_t)it * 8,
                                 (size_t)S * 32, (size_t)n_it * 32, NB, hipMemcpyDeviceToHost, st));
         it += n_it;
         int *h = snap + (size_t)slot * 3 * NB;
@@ -2392,7 +1737,7 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
         }
         for (size_t q = 0; q < jobs.size(); ++q) {
             const Job &j = jobs[q];
-            const int32_t *fm = dev->h_codes + ((size_t)j.b * S + j.f0) * 8;
+            const int32_t *fm = h_codes + ((size_t)j.b * S + j.f0) * 8;
             int32_t *dst = cbm.data() + at[q] * 8 * fpc;
             for (int t = 0; t < j.n; ++t)  // frame-major -> codebook-major (decode_frames_to_audio, 4468-4473)
                 for (int c = 0; c < 8; ++c) dst[(size_t)c * j.n + t] = fm[(size_t)t * 8 + c];
@@ -2456,23 +1801,21 @@ int mp_hip_lt_sample(mp_dev *dev, const float *hidden, float temperature, int to
     if (temperature >= 0.01f && (top_k < 1 || top_k > mp::VCB)) return fail(dev, MP_ERR_ARG, "top_k must be in 1..2024");
     HIPCHK(hipSetDevice(dev->device));
     mp::LtIo &io = dev->lt_io;
-    if (dev->ltio_allocs.empty()) {
-        auto al = [&](auto **p, size_t n) -> int {
-            void *v = nullptr;
-            HIPCHK(hipMalloc(&v, n * 4 + 256));
-            HIPCHK(hipMemset(v, 0, n * 4 + 256));
-            dev->ltio_allocs.push_back(v);
-            *p = (std::remove_reference_t<decltype(**p)> *)v;
-            return MP_OK;
+    if (dev->ltio_mem.empty()) {
+        bool ok = true;
+        auto al = [&](auto **p, size_t n) {  // n 4-byte elements and the tail, zeroed
+            ok = ok && dev->ltio_mem.bytes(p, n * 4 + 256) == hipSuccess &&
+                 hipMemsetAsync(*p, 0, n * 4 + 256, dev->stream) == hipSuccess;
         };
-        int rc = MP_OK;
-        if ((rc = al(&io.hidden, 768)) || (rc = al(&io.lt_s, 9 * 256)) || (rc = al(&io.ltX, 256)) ||
-            (rc = al(&io.ltY, 256)) || (rc = al(&io.lty2, 256)) || (rc = al(&io.ltq, 256)) ||
-            (rc = al(&io.ltk, 8 * 256)) || (rc = al(&io.ltv, 8 * 256)) || (rc = al(&io.ltf, 1024)) || (rc = al(&io.ltp, std::max({mp::LT_FFN_P, mp::LTS_P, mp::LTQ_P}) * 256)) ||
-
-            (rc = al(&io.logits, 2024)) || (rc = al(&io.codes_cur, 8)) || (rc = al(&io.step, 1)) ||
-            (rc = al(&io.done, 1)) || (rc = al(&io.argeos, 1)) || (rc = al(&io.amax, 8)) || (rc = al(&io.cfg, 8)))
-            return rc;
+        al(&io.hidden, 768); al(&io.lt_s, 9 * 256); al(&io.ltX, 256); al(&io.ltY, 256); al(&io.lty2, 256); al(&io.ltq, 256);
+        al(&io.ltk, 8 * 256); al(&io.ltv, 8 * 256); al(&io.ltf, 1024);
+        al(&io.ltp, std::max({mp::LT_FFN_P, mp::LTS_P, mp::LTQ_P}) * 256);
+        al(&io.logits, 2024); al(&io.codes_cur, 8); al(&io.step, 1); al(&io.done, 1); al(&io.argeos, 1); al(&io.amax, 8);
+        al(&io.cfg, 8);
+        if (!ok) {
+            dev->ltio_mem.clear();
+            return fail(dev, MP_ERR_HIP, "LT sample scratch allocation failed");
+        }
         io.lt_only = 1;
         io.max_steps = 1;
     }
@@ -2565,8 +1908,8 @@ int mp_hip_profile_ops_ex(mp_dev *dev, int iters, float *avg_us, float *pair_us)
         return fail(dev, MP_ERR_STATE, "mp_hip_profile_ops needs a decoded batch (mp_hip_decode first)");
     HIPCHK(hipSetDevice(dev->device));
     const int n = (int)dev->ops.size();
-    std::vector<hipEvent_t> ev(3 * (size_t)n);  // [before, after, after + an empty pair's second event]
-    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+    std::vector<mp::Event> ev(3 * (size_t)n);  // [before, after, after + an empty pair's second event]
+    for (auto &e : ev) HIPCHK(e.create());
     std::vector<double> sum(n, 0.0), psum(n, 0.0);
     int rc = MP_OK;
     for (int it = 0; it < iters && rc == MP_OK; ++it) {
@@ -2589,7 +1932,6 @@ int mp_hip_profile_ops_ex(mp_dev *dev, int iters, float *avg_us, float *pair_us)
             }
         }
     }
-    for (auto &e : ev) hipEventDestroy(e);
     for (int i = 0; i < n; ++i) avg_us[i] = (float)(sum[i] * 1000.0 / iters);
     if (pair_us)
         for (int i = 0; i < n; ++i) pair_us[i] = (float)(psum[i] * 1000.0 / iters);
@@ -2603,8 +1945,9 @@ int mp_hip_profile_ops_ts(mp_dev *dev, int iters, float *avg_us) {
     HIPCHK(hipSetDevice(dev->device));
     const int n = (int)dev->ops.size();
     const size_t per = (size_t)2 * TS_BLOCKS * TS_WAVES;  // u64 per op
+    mp::DevBlocks ts_mem;
     unsigned long long *ts = nullptr;
-    HIPCHK(hipMalloc(&ts, (size_t)n * per * 8));
+    HIPCHK(ts_mem.bytes(&ts, (size_t)n * per * 8));
     std::vector<unsigned long long> h((size_t)n * per);
     std::vector<double> sum(n, 0.0);
     std::vector<int> cnt(n, 0);
@@ -2635,7 +1978,6 @@ int mp_hip_profile_ops_ts(mp_dev *dev, int iters, float *avg_us) {
             if (t1 > t0 && t0 != ~0ull) { sum[i] += (double)(t1 - t0); ++cnt[i]; }
         }
     }
-    hipFree(ts);
     // s_memrealtime counts at 100 MHz: 10 ns per tick; -1 for ops without timestamps
     for (int i = 0; i < n; ++i) avg_us[i] = cnt[i] ? (float)(sum[i] / cnt[i] * 0.01) : -1.f;
     return rc;
@@ -2652,8 +1994,8 @@ int mp_hip_profile_ops_kev(mp_dev *dev, int iters, float *avg_us) {
         return fail(dev, MP_ERR_STATE, "mp_hip_profile_ops_kev needs a decoded batch (mp_hip_decode first)");
     HIPCHK(hipSetDevice(dev->device));
     const int n = (int)dev->ops.size();
-    std::vector<hipEvent_t> ev(2 * (size_t)n);
-    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+    std::vector<mp::Event> ev(2 * (size_t)n);
+    for (auto &e : ev) HIPCHK(e.create());
     std::vector<double> sum(n, 0.0);
     int rc = MP_OK;
     hipLaunchKernelGGL(profile_mark_kernel, dim3(1), dim3(64), 0, dev->stream);
@@ -2675,7 +2017,6 @@ int mp_hip_profile_ops_kev(mp_dev *dev, int iters, float *avg_us) {
     }
     hipLaunchKernelGGL(profile_mark_kernel, dim3(1), dim3(64), 0, dev->stream);
     HIPCHK(hipStreamSynchronize(dev->stream));
-    for (auto &e : ev) hipEventDestroy(e);
     for (int i = 0; i < n; ++i) avg_us[i] = (float)(sum[i] * 1000.0 / iters);
     return rc;
 }
@@ -2698,17 +2039,15 @@ int mp_hip_time_op(mp_dev *dev, int op, int reps, float *avg_us) {
     if (handoff)
         return fail(dev, MP_ERR_ARG, "op carries an in-launch hand-off: back-to-back timing would not wait for it");
     HIPCHK(launch());  // warm
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    mp::Event e0, e1;
+    HIPCHK(e0.create());
+    HIPCHK(e1.create());
     HIPCHK(hipEventRecord(e0, dev->stream));
     for (int i = 0; i < reps; ++i) HIPCHK(launch());
     HIPCHK(hipEventRecord(e1, dev->stream));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     *avg_us = ms * 1000.f / reps;
     return MP_OK;
 }
