@@ -129,9 +129,13 @@ struct magpie_context {
     // added: magpie_synthesize_streaming runs up to this many sentences as one device
     // batch (audio still delivered in sentence order, identical samples); 1 = one by one
     int max_parallel_sentences;
+    // added: the streaming calls decode each sentence's chunks on a lane of a stateful codec
+    // stream (MP_STREAM_CODEC_CONTINUOUS), so a sentence's audio is one magpie_codec_decode of
+    // its frames; false (default): stateless chunks, as the reference streams
+    bool continuous_codec;
     magpie_context()
         : n_threads(4), temperature(0.7f), top_k(80), speaker_id(0), codec(nullptr), seed(0),
-          max_parallel_sentences(8) {}
+          max_parallel_sentences(8), continuous_codec(false) {}
 };
 
 // magpie.h:310-313
@@ -216,6 +220,15 @@ void magpie_codec_free(magpie_codec *codec);
 bool magpie_codec_load(const std::string &path, magpie_codec &codec, magpie_backend_type backend = MAGPIE_BACKEND_AUTO);
 // codes: [num_codebooks][n_frames] codebook-major; returns n_frames * 1024 samples
 std::vector<float> magpie_codec_decode(magpie_codec *codec, const int32_t *codes, int n_frames);
+// Added: a stateful streaming decode of one utterance (one lane of mp_hip_codec_stream_*).
+// Consecutive chunks (codes [num_codebooks][n_frames] each) give, concatenated, the samples
+// one magpie_codec_decode of all the frames gives, bit for bit. reset: the next chunk starts
+// an utterance. Free the stream before its codec. nullptr / empty vector on failure.
+struct magpie_codec_stream;
+magpie_codec_stream *magpie_codec_stream_init(magpie_codec *codec);
+std::vector<float> magpie_codec_stream_decode(magpie_codec_stream *s, const int32_t *codes, int n_frames);
+void magpie_codec_stream_reset(magpie_codec_stream *s);
+void magpie_codec_stream_free(magpie_codec_stream *s);
 
 // magpie.h:372-377: the 8-codebook local transformer for one normalised decoder
 // hidden state [768] (sampled + argmax codes), on the device.

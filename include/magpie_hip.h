@@ -131,6 +131,14 @@ int mp_hip_set_kv_mode(mp_dev *dev, int kv_mode);
 #define MP_XA_DIRECT 2
 #define MP_XA_DIRECT_T 160
 int mp_hip_set_xa_mode(mp_dev *dev, int xa_mode);
+/* How mp_hip_decode_stream decodes its chunks, applied from the next call. STATELESS
+ * (default): each chunk on its own, as the reference does (magpie.cpp:4458-4476).
+ * CONTINUOUS: utterance b's chunks on lane b of a stateful codec stream
+ * (mp_hip_codec_stream_*), so its concatenated audio is, bit for bit, one
+ * mp_hip_codec_decode of its frames. */
+#define MP_STREAM_CODEC_STATELESS 0
+#define MP_STREAM_CODEC_CONTINUOUS 1
+int mp_hip_set_stream_codec_mode(mp_dev *dev, int mode);
 int mp_hip_weight_mode(mp_dev *dev);
 /* the largest batch mp_hip_begin_batch accepts for the loaded model: 16 in the
  * bf16 / F16 modes and for a Q8_0 / Q4_0 file whose decode projections are all
@@ -275,6 +283,27 @@ int mp_hip_codec_decode(mp_codec *c, const int32_t *codes, int n_frames, float *
 int mp_hip_codec_decode_chunks(mp_codec *c, const int32_t *codes, int n_chunks, int chunk_frames, float *audio_out);
 /* device time (hipEvents) of the last decode's kernel sequence, ms */
 int mp_hip_codec_last_ms(mp_codec *c, float *ms);
+/* Stateful streaming decode (no reference counterpart: the reference's streaming decodes
+ * stateless chunks, magpie.cpp:4458-4476, each as if nothing preceded it). A stream has
+ * `lanes` independent lanes; consecutive chunks of one utterance decoded on one lane give,
+ * bit for bit, the samples one mp_hip_codec_decode of all the utterance's frames gives. A
+ * lane keeps only what the next chunk's first outputs read from before it: each causal
+ * conv's last (ks - 1) * dilation operand rows, each transposed conv's last input step, the
+ * pre-conv's last 6 frames of codes (about 0.4 MB, kept twice); no past frame is decoded
+ * again. The stream borrows the codec's weights, buffers and stream: free it before the
+ * codec, and use the two from one host thread at a time. */
+typedef struct mp_codec_stream mp_codec_stream;
+int mp_hip_codec_stream_create(mp_codec *c, int lanes, mp_codec_stream **out); /* 1 <= lanes <= 4096 */
+/* One chunk of n_frames frames on each of n distinct lanes: lane_ids [n]; codes
+ * [n][8][n_frames] codebook-major; audio_out [n][n_frames * 1024]. Each lane's state
+ * advances by n_frames; a failed call advances nothing. MP_ERR_ARG (message:
+ * mp_hip_codec_error) for a duplicate or out-of-range lane or n_frames < 1.
+ * mp_hip_codec_last_ms reports this decode too. */
+int mp_hip_codec_stream_decode(mp_codec_stream *s, const int32_t *lane_ids, int n, const int32_t *codes, int n_frames,
+                               float *audio_out);
+/* back to the start of an utterance; lane < 0: all lanes */
+int mp_hip_codec_stream_reset(mp_codec_stream *s, int lane);
+void mp_hip_codec_stream_free(mp_codec_stream *s);
 void mp_hip_codec_free(mp_codec *c);
 const char *mp_hip_codec_error(mp_codec *c);
 

@@ -260,6 +260,44 @@ std::vector<float> magpie_codec_decode(magpie_codec *codec, const int32_t *codes
     return audio;
 }
 
+struct magpie_codec_stream {
+    magpie_codec *codec = nullptr;
+    mp_codec_stream *dev = nullptr;
+};
+magpie_codec_stream *magpie_codec_stream_init(magpie_codec *codec) {
+    if (!codec || !codec->dev) return nullptr;
+    magpie_codec_stream *s = new magpie_codec_stream();
+    s->codec = codec;
+    if (mp_hip_codec_stream_create(codec->dev, 1, &s->dev) != MP_OK) {
+        fprintf(stderr, "magpie_codec_stream_init: %s\n", mp_hip_codec_error(codec->dev));
+        delete s;
+        return nullptr;
+    }
+    return s;
+}
+std::vector<float> magpie_codec_stream_decode(magpie_codec_stream *s, const int32_t *codes, int n_frames) {
+    if (!s || !s->dev || !codes || n_frames <= 0) {
+        fprintf(stderr, "magpie_codec_stream_decode: invalid args\n");
+        return {};
+    }
+    const int32_t lane = 0;
+    std::vector<float> audio((size_t)n_frames * s->codec->hparams.hop_length);
+    if (mp_hip_codec_stream_decode(s->dev, &lane, 1, codes, n_frames, audio.data()) != MP_OK) {
+        fprintf(stderr, "magpie_codec_stream_decode: %s\n", mp_hip_codec_error(s->codec->dev));
+        return {};
+    }
+    return audio;
+}
+void magpie_codec_stream_reset(magpie_codec_stream *s) {
+    if (s && s->dev && mp_hip_codec_stream_reset(s->dev, 0) != MP_OK)
+        fprintf(stderr, "magpie_codec_stream_reset: %s\n", mp_hip_codec_error(s->codec->dev));
+}
+void magpie_codec_stream_free(magpie_codec_stream *s) {
+    if (!s) return;
+    mp_hip_codec_stream_free(s->dev);
+    delete s;
+}
+
 bool magpie_is_eos(const std::vector<int32_t> &frame_codes, int32_t eos_id) {
     for (int32_t c : frame_codes)
         if (c == eos_id) return true;
@@ -364,6 +402,7 @@ long long stream_batch(magpie_context *ctx, magpie_codec *codec, const std::vect
         fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));
         return -1;
     }
+    mp_hip_set_stream_codec_mode(ctx->model.dev, ctx->continuous_codec ? MP_STREAM_CODEC_CONTINUOUS : MP_STREAM_CODEC_STATELESS);
     OrderedStream os;
     os.prm = &prm;
     os.B = B;

@@ -147,12 +147,44 @@ __device__ __forceinline__ float fsq(int code, int d) {
     return (float)((code / base) % lev - half) / (float)half;
 }
 
+// Stream lanes (mp_codec_stream): chunk q of a stateful call is lane lanes[q] >> 2 of the
+// stream. What a chunk's first outputs need from before the chunk is read from that lane's
+// state instead of zeros, and the chunk's own last rows are left there for the next call.
+// Every piece of state is kept twice ("parities"): a call reads parity lanes[q] & 1 and
+// writes the other one, so no workgroup ever reads what another one of the same launch
+// writes, and a call that fails has changed nothing the next call reads (the host flips a
+// lane's parity only after a call succeeded).
+struct HistP {
+    const int *lanes;   // [chunks of the call]: lane * 4 + 2 * (the lane has decoded a chunk) + parity
+    int nlanes;         // lanes of the stream
+    size_t lbytes;      // bytes of one lane's whole state: the state is [parity][lane][lbytes]
+    // this launch's piece of the state, in parity 0's lane 0:
+    _Float16 *tail[3];  // conv, per branch: [Cinp/32][pad][32] f16, the operand's last pad rows
+    float *f32;         // convT: [Cinp] HalfSnake'd last input step; post: [2][28] operand rows
+    template <class T> __device__ T *rd(T *base, int ent) const {  // the piece a call reads, of table entry ent
+        return (T *)((char *)base + ((size_t)(ent & 1) * nlanes + (ent >> 2)) * lbytes);
+    }
+    template <class T> __device__ T *wr(T *base, int ent) const { return rd(base, ent ^ 1); }  // ... and writes
+};
+// The kernels that take history are the stateless kernels' templates with a trailing HistP
+// argument (a parameter pack H, empty or {HistP}): without it the signature, the body after
+// `if constexpr` and the generated code are what they were.
+__device__ __forceinline__ HistP hist_of() { return HistP{}; }
+__device__ __forceinline__ const HistP &hist_of(const HistP &h) { return h; }
+
 // Implicit-GEMM causal conv. Block tile BM (out ch) x BN (time), 4 waves.
 constexpr int MAXTAPS = 11;
 // PIPE: the software-pipelined channel loop (twice the registers: 2 waves/SIMD),
 // for grids too small to hide latency by occupancy; same arithmetic either way.
-template <int BM, int BN, int MODE, bool PIPE>
-__global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
+// HIST: rows t < 0 come from the lane's tail (IN_FSQ: from the 6 frames of codes the host
+// puts in front of the chunk's, [chunk][8][6 + T], -1 where no frame exists yet: a zero
+// operand). The workgroup of output-channel tile 0 that stages the chunk's last rows
+// writes rows [T - pad, T) of (tail ++ chunk), the next call's tail, as it stages them:
+// a chunk shorter than pad rolls the tail. Fragments and accumulation are untouched.
+template <int BM, int BN, int MODE, bool PIPE, class... H>
+__global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p, H... hh) {
+    constexpr bool HIST = sizeof...(H) != 0;
+    [[maybe_unused]] const HistP &h = hist_of(hh...);
     constexpr int RW = BM / 16;          // row blocks of 16
     constexpr int CWN = 4 / RW;          // column groups
     constexpr int WCOLS = BN / CWN;      // columns per wave
@@ -175,6 +207,18 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
     const _Float16 *W = p.W[br];
     const int Kw = ks * p.Cinp;
     const int orow = m0 + rw * 16 + l16;
+    const _Float16 *tin = nullptr;
+    _Float16 *tout = nullptr;
+    if constexpr (HIST && MODE == IN_F16) {
+        const int ent = h.lanes[chunk];
+        tin = h.rd(h.tail[br], ent);
+        if (blockIdx.x == 0 && t0 + BN >= p.T) tout = h.wr(h.tail[br], ent);
+    }
+    // HIST: piece q of row t of channel block cb, from the tail where t < 0, and into the new tail
+    auto hist_row = [&](int cb, int t, int q, uint4 &v) {
+        if (t < 0) v = *(const uint4 *)(tin + ((size_t)cb * pad + (t + pad)) * 32 + 8 * q);
+        if (tout && t >= p.T - pad && t < p.T) *(uint4 *)(tout + ((size_t)cb * pad + (t - (p.T - pad))) * 32 + 8 * q) = v;
+    };
 
     floatx4 acc[NT];
 #pragma unroll
@@ -208,6 +252,11 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int c = i0 + c4 + u;
+                        if constexpr (HIST) {  // t >= -6: the chunk's codes follow the lane's last 6 frames'
+                            const int code = t < p.T ? p.codes[((size_t)chunk * 8 + (c >> 2)) * (p.T + 6) + t + 6] : -1;
+                            dst[u] = code >= 0 ? (_Float16)fsq(code, c & 3) : (_Float16)0.f;
+                            continue;
+                        }
                         dst[u] = (t >= 0 && t < p.T)
                                      ? (_Float16)fsq(p.codes[((size_t)chunk * 8 + (c >> 2)) * p.T + t], c & 3)
                                      : (_Float16)0.f;
@@ -219,6 +268,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
                     const int t = t0 - pad + r;
                     uint4 v = make_uint4(0u, 0u, 0u, 0u);
                     if (t >= 0 && t < p.T) v = *(const uint4 *)(xin + ((size_t)(i0 >> 5) * p.T + t) * 32 + 8 * q);
+                    if constexpr (HIST) hist_row(i0 >> 5, t, q, v);
                     *(uint4 *)(xs[0] + r * ROWB + 16 * q) = v;
                 }
             }
@@ -255,6 +305,8 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
                 const int t = t0 - pad + (e >> 2);
                 xv[u] = make_uint4(0u, 0u, 0u, 0u);
                 if (e < items && t >= 0 && t < p.T) xv[u] = *(const uint4 *)(xin + ((size_t)(i0 >> 5) * p.T + t) * 32 + 8 * (e & 3));
+                if constexpr (HIST)
+                    if (e < items) hist_row(i0 >> 5, t, e & 3, xv[u]);
             }
         };
         load_blk(0);
@@ -320,8 +372,10 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
 // block. Accumulation order (block, tap ascending) equals conv_mfma_kernel's, so
 // the two kernels give the same bits.
 constexpr int C2_WR = 2, C2_NT = 4;
-template <int KS, int RWV, int CWV, int NCB, int R>
-__device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
+// HIST: conv_mfma_kernel's (rows t < 0 from the lane's tail, the new tail left by the
+// workgroup of channel tile 0 that stages the chunk's last rows).
+template <int KS, int RWV, int CWV, int NCB, int R, bool HIST>
+__device__ __forceinline__ void conv2_body(const ConvP &p, const HistP &h, char *xs) {
     constexpr int NTH = 64 * RWV * CWV;
     constexpr int BN = CWV * 16 * C2_NT;
     constexpr int ROWB = LDS_ROWB;       // LDS bytes per time row: 32 halves + pad
@@ -342,6 +396,13 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
     const _Float16 *wrow0 = p.Wf[br] + (size_t)((m0 >> 4) + rw * 2) * NCB * KS * 512 + lane * 8;
     const _Float16 *wrow1 = wrow0 + (size_t)NCB * KS * 512;
     const int rows = BN + pad, items = rows * 4;
+    const _Float16 *tin = nullptr;
+    _Float16 *tout = nullptr;
+    if constexpr (HIST) {
+        const int ent = h.lanes[chunk];
+        tin = h.rd(h.tail[br], ent);
+        if (blockIdx.x == 0 && t0 + BN >= p.T) tout = h.wr(h.tail[br], ent);
+    }
 
     floatx4 acc[C2_WR][C2_NT];
 #pragma unroll
@@ -384,6 +445,12 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
             const int t = t0 - pad + (e >> 2);
             xv[u] = make_uint4(0u, 0u, 0u, 0u);
             if (e < items && t >= 0 && t < p.T) xv[u] = *(const uint4 *)(xin + ((size_t)cb * p.T + t) * 32 + 8 * (e & 3));
+            if constexpr (HIST)
+                if (e < items) {
+                    if (t < 0) xv[u] = *(const uint4 *)(tin + ((size_t)cb * pad + (t + pad)) * 32 + 8 * (e & 3));
+                    if (tout && t >= p.T - pad && t < p.T)
+                        *(uint4 *)(tout + ((size_t)cb * pad + (t - (p.T - pad))) * 32 + 8 * (e & 3)) = xv[u];
+                }
         }
     };
     load_x(0);
@@ -477,15 +544,17 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, char *xs) {
 // NCB = Cinp / 32 channel blocks (unrolled); DEEP: an A ring of max(KS, 6) slots
 // (a block or more of lead, for grids of about one wave per SIMD whose weights come
 // from the Infinity Cache) instead of 3 (occupancy-hidden latency, <= 128 VGPRs).
-template <int RWV, int CWV, int NCB, bool DEEP>
-__global__ __launch_bounds__(64 * RWV * CWV, DEEP ? 1 : 2) void conv2_kernel(ConvP p) {
+template <int RWV, int CWV, int NCB, bool DEEP, class... H>
+__global__ __launch_bounds__(64 * RWV * CWV, DEEP ? 1 : 2) void conv2_kernel(ConvP p, H... hh) {
+    constexpr bool HIST = sizeof...(H) != 0;
+    [[maybe_unused]] const HistP &h = hist_of(hh...);
     constexpr int BN = CWV * 16 * C2_NT;
     constexpr int XSB = 2 * (BN + 50) * LDS_ROWB, CTB = BN * (RWV * 32 + 4) * 4;  // input buffers / epilogue tile
     __shared__ __attribute__((aligned(16))) char xs[XSB > CTB ? XSB : CTB];
     switch (p.ks[p.zorder[blockIdx.z]]) {
-        case 3: conv2_body<3, RWV, CWV, NCB, DEEP ? 6 : 3>(p, xs); break;
-        case 7: conv2_body<7, RWV, CWV, NCB, DEEP ? 7 : 3>(p, xs); break;
-        default: conv2_body<11, RWV, CWV, NCB, DEEP ? 11 : 3>(p, xs); break;
+        case 3: conv2_body<3, RWV, CWV, NCB, DEEP ? 6 : 3, HIST>(p, h, xs); break;
+        case 7: conv2_body<7, RWV, CWV, NCB, DEEP ? 7 : 3, HIST>(p, h, xs); break;
+        default: conv2_body<11, RWV, CWV, NCB, DEEP ? 11 : 3, HIST>(p, h, xs); break;
     }
 }
 
@@ -1014,8 +1083,14 @@ constexpr int CT_R = 8;
 // ggml's summation order: channel c outer, tau = t/s - 1 then t/s inner.
 // ACT: also emit the 3 branches' k=0 in_conv operands (the stages whose residual
 // blocks are fused compute them from the f32 output instead).
-template <int CINP, int COUTP, int S, bool AVG, int R, bool ACT>
-__global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p) {
+// HIST (stream lanes): input step -1 of a chunk is the lane's previous chunk's last step,
+// kept HalfSnake'd as this kernel computed it then (`cur` of that step: the bits a one-shot
+// decode keeps in `prev`); the thread of the chunk's last step leaves its own. A lane's
+// first chunk skips the tau - 1 term, as step 0 of a one-shot decode does.
+template <int CINP, int COUTP, int S, bool AVG, int R, bool ACT, class... H>
+__global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p, H... hh) {
+    constexpr bool HIST = sizeof...(H) != 0;
+    [[maybe_unused]] const HistP &h = hist_of(hh...);
     constexpr int NG = COUTP / 2, K = 2 * S;
     const int e = blockIdx.x * 256 + threadIdx.x;
     const int gp = e % NG, rest = e / NG;
@@ -1063,6 +1138,19 @@ __global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p) {
     };
     const int tau0 = tt * R;
     float prev[4] = {0.f, 0.f, 0.f, 0.f}, cur[4];
+    bool has_prev = false;
+    float *hout = nullptr;
+    if constexpr (HIST) {
+        const int ent = h.lanes[chunk];
+        hout = h.wr(h.f32, ent);
+        if (tau0 == 0 && (ent & 2)) {
+            has_prev = true;
+            if (c0 < CINP) {
+                const float4 q = *(const float4 *)(h.rd(h.f32, ent) + c0);
+                prev[0] = q.x; prev[1] = q.y; prev[2] = q.z; prev[3] = q.w;
+            }
+        }
+    }
     if (tau0 >= 1) load_in(tau0 - 1, prev);
     const int Tout = p.Tin * S;
     const size_t cout_base = (size_t)chunk * Tout * COUTP;
@@ -1079,7 +1167,7 @@ __global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p) {
             // ggml order: channel c outer, tau = t/s - 1 then t/s inner
 #pragma unroll
             for (int ci = 0; ci < 2; ++ci) {
-                if (tau >= 1) {
+                if (tau >= 1 || (HIST && has_prev)) {
                     a0 = fmaf(prev[ci], w[ci][u + S], a0);
                     a1 = fmaf(prev[2 + ci], w[2 + ci][u + S], a1);
                 }
@@ -1099,6 +1187,8 @@ __global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p) {
                 *(half2v *)(p.act[j] + act_base + (size_t)t * 32) = h;
             }
         }
+        if constexpr (HIST)
+            if (tau == p.Tin - 1 && c0 < CINP) *(float4 *)(hout + c0) = make_float4(cur[0], cur[1], cur[2], cur[3]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) prev[i] = cur[i];
     }
@@ -1118,7 +1208,13 @@ struct PostP {
 // 3-branch mean is computed once per (time, channel) into LDS (with the 2-sample
 // causal halo), rounded to f16 like ggml's im2col, then each thread dots its 3
 // taps x 27 channels against the f16-rounded weights.
-__global__ __launch_bounds__(256) void post_conv_kernel(PostP p) {
+// HIST (stream lanes): the 2-row halo of a chunk's first tile is the lane's previous chunk's
+// last two operand rows (f16-rounded HalfSnake of the mean, as staged then; zeros before the
+// lane's first chunk, the causal padding); the chunk's last tile leaves its own.
+template <class... H>
+__global__ __launch_bounds__(256) void post_conv_kernel(PostP p, H... hh) {
+    constexpr bool HIST = sizeof...(H) != 0;
+    [[maybe_unused]] const HistP &h = hist_of(hh...);
     __shared__ __attribute__((aligned(16))) float hs[258][28];
     __shared__ float wh[27 * 3];
     const int tiles = (p.T + 255) / 256;
@@ -1142,9 +1238,19 @@ __global__ __launch_bounds__(256) void post_conv_kernel(PostP p) {
             for (int u = 0; u < 4; ++u) hv[u] = i0 + u < 27 ? (float)(_Float16)half_snake(m[u], i0 + u, 13, 27, p.alpha) : 0.f;
             v = make_float4(hv[0], hv[1], hv[2], hv[3]);
         }
+        if constexpr (HIST)
+            if (t < 0) {
+                const int ent = h.lanes[chunk];
+                v = *(const float4 *)(h.rd(h.f32, ent) + (t + 2) * 28 + i0);
+            }
         *(float4 *)&hs[r][i0] = v;
     }
     __syncthreads();
+    if constexpr (HIST)
+        if (t0 + 256 >= p.T && threadIdx.x < 56) {  // rows T - 2, T - 1 (T >= 1024: this tile holds both)
+            const int ent = h.lanes[chunk];
+            h.wr(h.f32, ent)[threadIdx.x] = hs[p.T - t0 + threadIdx.x / 28][threadIdx.x % 28];
+        }
     const int t = t0 + threadIdx.x;
     if (t >= p.T) return;
     float acc = 0.f;
@@ -1187,6 +1293,26 @@ struct mp_codec {
     unsigned long long *ts_dev = nullptr;
     int ts_stage = -1, ts_block = -1;
     std::string ts_file;
+    int *lane_tab = nullptr;  // stream decodes: the call's lane table (mpc::HistP::lanes), behind its codes
+};
+
+// Stateful streaming decode: per lane, what the next chunk's first outputs need from the
+// frames before it, and nothing else (mpc::HistP): every conv's last (ks - 1) dil operand rows,
+// every convT's last input step, the post conv's last two operand rows (device, both
+// parities) and the pre-conv's last 6 frames of codes (host). It borrows the codec's
+// weights, activation buffers and stream.
+struct mp_codec_stream {
+    mp_codec *c = nullptr;
+    int device = 0, lanes = 0;
+    mp::DevBlocks mem;
+    char *state = nullptr;  // [2 parities][lanes][lbytes]; the pieces below point into parity 0's lane 0
+    size_t lbytes = 0;
+    _Float16 *tail[mpc::NSTAGE][3][3][2] = {};  // [stage][branch][block][in / skip]: Cp * pad halves
+    float *ct_prev[mpc::NSTAGE] = {};           // Cin_p floats
+    float *post_hs = nullptr;                   // [2][28] floats
+    std::vector<int> parity, started;           // per lane: the parity the next call reads; a chunk was decoded
+    std::vector<int32_t> hist;                  // per lane [8][6]: the last 6 frames of codes, -1 before the first
+    static int pad(int j, int k, int sk) { return (mpc::KS[j] - 1) * (sk ? 1 : mpc::DIL[k]); }
 };
 
 namespace {
@@ -1277,7 +1403,8 @@ int load_codec(mp_codec *c, const char *path) {
     return upload(c, &c->post_b, v);
 }
 
-int ensure_buffers(mp_codec *c, int nchunk, int F) {
+// codes_extra: ints behind the chunks' codes (a stream decode's code history and lane table)
+int ensure_buffers(mp_codec *c, int nchunk, int F, size_t codes_extra = 0) {
     using namespace mpc;
     size_t need = 0;
     for (int i = 0; i < NSTAGE; ++i) {
@@ -1295,7 +1422,7 @@ int ensure_buffers(mp_codec *c, int nchunk, int F) {
         for (auto b : hb) CHK(c->act.get(b, need));
         c->cap_elems = need;
     }
-    const size_t ncodes = (size_t)nchunk * 8 * F, naudio = (size_t)nchunk * F * HOP;
+    const size_t ncodes = (size_t)nchunk * 8 * F + codes_extra, naudio = (size_t)nchunk * F * HOP;
     if (ncodes > c->codes_cap) {
         c->codes_mem.clear();
         c->codes_cap = 0;
@@ -1322,8 +1449,9 @@ hipError_t launch_conv(const mpc::ConvP &p, int nchunk, int nbranch, hipStream_t
     return hipGetLastError();
 }
 
+// h: a stream decode's history (null: stateless chunks)
 template <int RWV, int CWV, int NCB, bool DEEP>
-hipError_t launch_conv2(mpc::ConvP p, int nchunk, int nbranch, hipStream_t s) {
+hipError_t launch_conv2(mpc::ConvP p, int nchunk, int nbranch, hipStream_t s, const mpc::HistP *h = nullptr) {
     constexpr int BN = CWV * 16 * mpc::C2_NT;
     if (p.Cinp != NCB * 32) return hipErrorInvalidValue;
     p.tiles_per_chunk = (p.T + BN - 1) / BN;
@@ -1331,7 +1459,8 @@ hipError_t launch_conv2(mpc::ConvP p, int nchunk, int nbranch, hipStream_t s) {
     for (int j = 0; j < 3; ++j) p.zorder[j] = j;
     std::sort(p.zorder, p.zorder + nbranch, [&](int a, int b) { return p.ks[a] > p.ks[b]; });
     dim3 grid(p.Coutp / (RWV * 32), nchunk * p.tiles_per_chunk, nbranch);
-    hipLaunchKernelGGL((mpc::conv2_kernel<RWV, CWV, NCB, DEEP>), grid, dim3(64 * RWV * CWV), 0, s, p);
+    if (h) hipLaunchKernelGGL((mpc::conv2_kernel<RWV, CWV, NCB, DEEP, mpc::HistP>), grid, dim3(64 * RWV * CWV), 0, s, p, *h);
+    else hipLaunchKernelGGL((mpc::conv2_kernel<RWV, CWV, NCB, DEEP>), grid, dim3(64 * RWV * CWV), 0, s, p);
     return hipGetLastError();
 }
 
@@ -1399,18 +1528,36 @@ hipError_t run_rl(const mpc::RlP &p, int Cp, int nchunk, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-hipError_t run_conv(const mpc::ConvP &p, int BM, int mode, int nchunk, int nbranch, hipStream_t s) {
+// conv_mfma_kernel with a stream decode's history
+template <int BM, int BN, int MODE>
+hipError_t launch_conv_stream(const mpc::ConvP &p, const mpc::HistP &h, int nchunk, int nbranch, hipStream_t s) {
+    dim3 grid(p.Coutp / BM, nchunk * p.tiles_per_chunk, nbranch);
+    const bool pipe = MODE == mpc::IN_F16 && (size_t)grid.x * grid.y * grid.z < 1024;  // launch_conv's rule
+    if (pipe) hipLaunchKernelGGL((mpc::conv_mfma_kernel<BM, BN, mpc::IN_F16, true, mpc::HistP>), grid, dim3(256), 0, s, p, h);
+    else hipLaunchKernelGGL((mpc::conv_mfma_kernel<BM, BN, MODE, false, mpc::HistP>), grid, dim3(256), 0, s, p, h);
+    return hipGetLastError();
+}
+// h: a stream decode's history (null: stateless chunks); the same kernel choice either way
+hipError_t run_conv(const mpc::ConvP &p, int BM, int mode, int nchunk, int nbranch, hipStream_t s,
+                    const mpc::HistP *h = nullptr) {
     using namespace mpc;
     // ResLayer convs: the wide-tile kernel once a chunk fills at least half a tile
     // (per-chunk length decides, so a chunk decodes the same alone or batched)
     if (mode == IN_F16) {
         switch (p.Coutp) {
-            case 448: if (p.T >= 64) return launch_conv2<2, 2, 14, true>(p, nchunk, nbranch, s); break;
-            case 224: if (p.T >= 128) return launch_conv2<1, 4, 7, true>(p, nchunk, nbranch, s); break;
-            case 128: if (p.T >= 64) return launch_conv2<4, 2, 4, false>(p, nchunk, nbranch, s); break;
-            case 64: if (p.T >= 128) return launch_conv2<2, 4, 2, false>(p, nchunk, nbranch, s); break;
-            case 32: if (p.T >= 128) return launch_conv2<1, 4, 1, false>(p, nchunk, nbranch, s); break;
+            case 448: if (p.T >= 64) return launch_conv2<2, 2, 14, true>(p, nchunk, nbranch, s, h); break;
+            case 224: if (p.T >= 128) return launch_conv2<1, 4, 7, true>(p, nchunk, nbranch, s, h); break;
+            case 128: if (p.T >= 64) return launch_conv2<4, 2, 4, false>(p, nchunk, nbranch, s, h); break;
+            case 64: if (p.T >= 128) return launch_conv2<2, 4, 2, false>(p, nchunk, nbranch, s, h); break;
+            case 32: if (p.T >= 128) return launch_conv2<1, 4, 1, false>(p, nchunk, nbranch, s, h); break;
         }
+    }
+    if (h) {
+        if (BM == 64) {
+            if (mode == IN_FSQ) return launch_conv_stream<64, 64, IN_FSQ>(p, *h, nchunk, nbranch, s);
+            return launch_conv_stream<64, 64, IN_F16>(p, *h, nchunk, nbranch, s);
+        }
+        return launch_conv_stream<32, 128, IN_F16>(p, *h, nchunk, nbranch, s);
     }
     if (BM == 64) {
         if (mode == IN_FSQ) return launch_conv<64, 64, IN_FSQ>(p, nchunk, nbranch, s);
@@ -1524,8 +1671,93 @@ int codec_run(mp_codec *c, int nchunk, int F) {
         }
     }
     PostP pp{c->brb[0], c->brb[1], c->brb[2], c->post_alpha, c->post_w, c->post_b, c->audio, T, nchunk};
-    hipLaunchKernelGGL(post_conv_kernel, dim3(nchunk * ((T + 255) / 256)), dim3(256), 0, s, pp);
+    hipLaunchKernelGGL(post_conv_kernel<>, dim3(nchunk * ((T + 255) / 256)), dim3(256), 0, s, pp);
     CHK(hipGetLastError());
+    return MP_OK;
+}
+
+// ---- stream lanes: the per-conv launch sequence with history (run_conv's choice between
+// conv_mfma_kernel and conv2_kernel, in their HistP forms; their bits are the fused kernels',
+// tests/test_codec_gpu.py)
+template <int CINP, int COUTP, int S, bool AVG, int R>
+hipError_t launch_convt_stream(const mpc::ConvTP &p, const mpc::HistP &h, hipStream_t s) {
+    const dim3 grid((p.nchunk * ((p.Tin + R - 1) / R) * (COUTP / 2) + 255) / 256);
+    hipLaunchKernelGGL((mpc::conv_transpose2_kernel<CINP, COUTP, S, AVG, R, true, mpc::HistP>), grid, dim3(256), 0, s, p, h);
+    return hipGetLastError();
+}
+
+// One chunk of F frames on each of n lanes (c->lane_tab; c->codes [n][8][6 + F]): codec_run's
+// two-launch residual blocks with every loader reading the lane's state and leaving the next.
+int codec_stream_run(mp_codec_stream *st, int n, int F) {
+    using namespace mpc;
+    mp_codec *c = st->c;
+    hipStream_t s = c->stream;
+    HistP h{};
+    h.lanes = c->lane_tab;
+    h.nlanes = st->lanes;
+    h.lbytes = st->lbytes;
+    {
+        ConvP p{};
+        p.W[0] = c->pre.w; p.bias[0] = c->pre.b; p.x[0] = nullptr; p.out[0] = c->x_pre;
+        p.resid[0] = nullptr; p.act[0] = nullptr; p.ks[0] = 7; p.codes = c->codes; p.cout_real = 864;
+        p.Cinp = 32; p.Coutp = CP_PRE; p.T = F; p.dil = 1; p.tiles_per_chunk = (F + 63) / 64;
+        CHK(run_conv(p, 64, IN_FSQ, n, 1, s, &h));
+    }
+    int T = F;
+    for (int i = 0; i < NSTAGE; ++i) {
+        const int cin = CH[i], C = CH[i + 1], Cin_p = i == 0 ? CP_PRE : CP[i - 1], Cp = CP[i];
+        ConvTP tp{};
+        tp.x = i == 0 ? c->x_pre : c->brb[0];
+        tp.xa = c->brb[1]; tp.xb = c->brb[2];
+        tp.alpha = c->up_alpha[i]; tp.n_snake = cin / 2; tp.cin_real = cin; tp.Cinp = Cin_p;
+        tp.w = c->up_w[i]; tp.bias = c->up_b[i]; tp.out = c->x0; tp.cout_real = C; tp.Coutp = Cp;
+        for (int j = 0; j < 3; ++j) { tp.act[j] = c->a16[j]; tp.act_alpha[j] = c->rb_alpha[i][j][0][0]; }
+        tp.Tin = T; tp.s = RATE[i]; tp.nchunk = n;
+        h.f32 = st->ct_prev[i];
+        switch (i) {  // codec_run's steps per thread
+            case 0: CHK((launch_convt_stream<896, 448, 8, false, 1>(tp, h, s))); break;
+            case 1: CHK((launch_convt_stream<448, 224, 8, true, 2>(tp, h, s))); break;
+            case 2: CHK((launch_convt_stream<224, 128, 4, true, CT_R>(tp, h, s))); break;
+            case 3: CHK((launch_convt_stream<128, 64, 2, true, CT_R>(tp, h, s))); break;
+            default: CHK((launch_convt_stream<64, 32, 2, true, CT_R>(tp, h, s))); break;
+        }
+        T *= RATE[i];
+        const int BM = BMS[i], BN = BM == 64 ? 64 : 128;
+        for (int k = 0; k < 3; ++k)
+            for (int sk = 0; sk < 2; ++sk) {
+                ConvP p{};
+                for (int j = 0; j < 3; ++j) {
+                    const mp_codec::Conv &cv = c->rb[i][j][k][sk];
+                    p.W[j] = cv.w; p.Wf[j] = cv.wf; p.bias[j] = cv.b; p.ks[j] = KS[j];
+                    h.tail[j] = st->tail[i][j][k][sk];
+                    if (!sk) {  // h = conv_{ks_j, d_k}(HS_in(x)); only HS_sk(h) (f16) is kept
+                        p.x[j] = c->a16[j]; p.out[j] = nullptr; p.resid[j] = nullptr;
+                        p.act[j] = c->b16[j]; p.act_alpha[j] = c->rb_alpha[i][j][k][1];
+                    } else {  // x' = x + conv_{ks_j, 1}(HS_sk(h)); plus the next block's operand HS_in(x')
+                        p.x[j] = c->b16[j]; p.out[j] = c->brb[j]; p.resid[j] = k == 0 ? c->x0 : c->brb[j];
+                        p.act[j] = k < 2 ? c->a16[j] : nullptr;
+                        p.act_alpha[j] = k < 2 ? c->rb_alpha[i][j][k + 1][0] : nullptr;
+                    }
+                }
+                p.act_nsnake = C / 2; p.cout_real = C; p.Cinp = Cp; p.Coutp = Cp; p.T = T; p.dil = sk ? 1 : DIL[k];
+                p.tiles_per_chunk = (T + BN - 1) / BN;
+                CHK(run_conv(p, BM, IN_F16, n, 3, s, &h));
+            }
+    }
+    h.f32 = st->post_hs;
+    PostP pp{c->brb[0], c->brb[1], c->brb[2], c->post_alpha, c->post_w, c->post_b, c->audio, T, n};
+    hipLaunchKernelGGL(post_conv_kernel<HistP>, dim3(n * ((T + 255) / 256)), dim3(256), 0, s, pp, h);
+    CHK(hipGetLastError());
+    return MP_OK;
+}
+
+// zero the state of lane `lane` (both parities): the causal padding of a first chunk
+int stream_reset_lane(mp_codec_stream *st, int lane) {
+    mp_codec *c = st->c;
+    for (int par = 0; par < 2; ++par)
+        CHK(hipMemsetAsync(st->state + ((size_t)par * st->lanes + lane) * st->lbytes, 0, st->lbytes, c->stream));
+    st->parity[lane] = st->started[lane] = 0;
+    std::fill(st->hist.begin() + (size_t)lane * 48, st->hist.begin() + (size_t)(lane + 1) * 48, -1);
     return MP_OK;
 }
 
@@ -1613,6 +1845,124 @@ int mp_hip_codec_last_ms(mp_codec *c, float *ms) {
 
 int mp_hip_codec_decode(mp_codec *c, const int32_t *codes, int n_frames, float *audio_out) {
     return mp_hip_codec_decode_chunks(c, codes, 1, n_frames, audio_out);
+}
+
+int mp_hip_codec_stream_create(mp_codec *c, int lanes, mp_codec_stream **out) {
+    using namespace mpc;
+    if (!c) return MP_ERR_ARG;
+    if (!out || lanes < 1 || lanes > 4096) { c->err = "stream: lanes must be in 1..4096"; return MP_ERR_ARG; }
+    *out = nullptr;
+    CHK(hipSetDevice(c->device));
+    mp_codec_stream *st = new mp_codec_stream();
+    st->c = c;
+    st->device = c->device;
+    st->lanes = lanes;
+    // one lane's state: every piece at a 16-byte multiple (tails are 64 pad bytes per channel block)
+    size_t off = 0;
+    auto piece = [&](size_t bytes) { const size_t at = off; off += bytes; return at; };
+    size_t at_tail[NSTAGE][3][3][2], at_ct[NSTAGE];
+    for (int i = 0; i < NSTAGE; ++i) {
+        at_ct[i] = piece((size_t)(i == 0 ? CP_PRE : CP[i - 1]) * 4);
+        for (int j = 0; j < 3; ++j)
+            for (int k = 0; k < 3; ++k)
+                for (int sk = 0; sk < 2; ++sk) at_tail[i][j][k][sk] = piece((size_t)CP[i] * mp_codec_stream::pad(j, k, sk) * 2);
+    }
+    const size_t at_post = piece(56 * 4);
+    st->lbytes = off;
+    const size_t total = 2 * (size_t)lanes * off;
+    hipError_t e = st->mem.bytes(&st->state, total);
+    if (e == hipSuccess) e = hipMemsetAsync(st->state, 0, total, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        delete st;
+        c->err = std::string("stream state allocation failed: ") + hipGetErrorString(e);
+        return MP_ERR_HIP;
+    }
+    for (int i = 0; i < NSTAGE; ++i) {
+        st->ct_prev[i] = (float *)(st->state + at_ct[i]);
+        for (int j = 0; j < 3; ++j)
+            for (int k = 0; k < 3; ++k)
+                for (int sk = 0; sk < 2; ++sk) st->tail[i][j][k][sk] = (_Float16 *)(st->state + at_tail[i][j][k][sk]);
+    }
+    st->post_hs = (float *)(st->state + at_post);
+    st->parity.assign(lanes, 0);
+    st->started.assign(lanes, 0);
+    st->hist.assign((size_t)lanes * 48, -1);
+    *out = st;
+    return MP_OK;
+}
+
+int mp_hip_codec_stream_decode(mp_codec_stream *st, const int32_t *lane_ids, int n, const int32_t *codes, int n_frames,
+                               float *audio_out) {
+    if (!st) return MP_ERR_ARG;
+    mp_codec *c = st->c;
+    if (!lane_ids || !codes || !audio_out || n < 1 || n_frames < 1) { c->err = "stream decode: invalid arguments"; return MP_ERR_ARG; }
+    if (n > st->lanes) { c->err = "stream decode: more lanes than the stream has"; return MP_ERR_ARG; }
+    for (int q = 0; q < n; ++q) {
+        if (lane_ids[q] < 0 || lane_ids[q] >= st->lanes) {
+            c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " out of range";
+            return MP_ERR_ARG;
+        }
+        for (int r = 0; r < q; ++r)
+            if (lane_ids[r] == lane_ids[q]) {
+                c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " given twice";
+                return MP_ERR_ARG;
+            }
+    }
+    const int F = n_frames, FH = F + 6;
+    CHK(hipSetDevice(c->device));
+    const size_t ncodes = (size_t)n * 8 * FH, nsamp = (size_t)n * F * mpc::HOP;
+    if (int rc = ensure_buffers(c, n, F, (size_t)n * 8 * 6 + n)) return rc;
+    c->lane_tab = c->codes + ncodes;
+    CHK(c->codes_pin.reserve((ncodes + n) * 4));
+    CHK(c->audio_pin.reserve(nsamp * 4));
+    int32_t *hc = (int32_t *)c->codes_pin.p;
+    for (int q = 0; q < n; ++q) {
+        const int ln = lane_ids[q];
+        for (int cb = 0; cb < 8; ++cb) {
+            int32_t *row = hc + ((size_t)q * 8 + cb) * FH;
+            memcpy(row, st->hist.data() + (size_t)ln * 48 + cb * 6, 6 * 4);
+            memcpy(row + 6, codes + ((size_t)q * 8 + cb) * F, (size_t)F * 4);
+        }
+        hc[ncodes + q] = ln * 4 + 2 * st->started[ln] + st->parity[ln];
+    }
+    CHK(hipMemcpyAsync(c->codes, hc, (ncodes + n) * 4, hipMemcpyHostToDevice, c->stream));
+    CHK(c->ev0.create());
+    CHK(c->ev1.create());
+    CHK(hipEventRecord(c->ev0, c->stream));
+    if (int rc = codec_stream_run(st, n, F)) return rc;
+    CHK(hipEventRecord(c->ev1, c->stream));
+    CHK(hipMemcpyAsync(c->audio_pin.p, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
+    CHK(hipStreamSynchronize(c->stream));
+    memcpy(audio_out, c->audio_pin.p, nsamp * 4);
+    CHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+    // the call succeeded: every lane's state advances (the parity just written becomes the one read)
+    for (int q = 0; q < n; ++q) {
+        const int ln = lane_ids[q];
+        st->parity[ln] ^= 1;
+        st->started[ln] = 1;
+        for (int cb = 0; cb < 8; ++cb)  // the last 6 of (history ++ chunk)
+            memcpy(st->hist.data() + (size_t)ln * 48 + cb * 6, hc + ((size_t)q * 8 + cb) * FH + F, 6 * 4);
+    }
+    return MP_OK;
+}
+
+int mp_hip_codec_stream_reset(mp_codec_stream *st, int lane) {
+    if (!st) return MP_ERR_ARG;
+    mp_codec *c = st->c;
+    if (lane >= st->lanes) { c->err = "stream reset: lane " + std::to_string(lane) + " out of range"; return MP_ERR_ARG; }
+    CHK(hipSetDevice(c->device));
+    for (int ln = lane < 0 ? 0 : lane; ln < (lane < 0 ? st->lanes : lane + 1); ++ln)
+        if (int rc = stream_reset_lane(st, ln)) return rc;
+    return MP_OK;
+}
+
+void mp_hip_codec_stream_free(mp_codec_stream *st) {
+    if (!st) return;
+    // the codec is not touched (a device's stream may outlive it): every decode has been
+    // waited for before it returned, and a reset's memsets are waited for by hipFree
+    hipSetDevice(st->device);
+    delete st;
 }
 
 void mp_hip_codec_free(mp_codec *c) {

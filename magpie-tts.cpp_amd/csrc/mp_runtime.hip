@@ -129,6 +129,13 @@ struct mp_dev {
     mp_params params{};
     int kv_mode = MP_KV_F32;  // mp_hip_set_kv_mode: applies from the next mp_hip_begin_batch
     int xa_mode = MP_XA_AUTO;  // mp_hip_set_xa_mode: likewise
+    // mp_hip_set_stream_codec_mode: applies from the next mp_hip_decode_stream. CONTINUOUS:
+    // slot b is lane b of `cstream`, made on the first use of a codec and kept while the
+    // codec and the lane count hold (released by mp_hip_free, which does not touch the codec)
+    int stream_codec_mode = MP_STREAM_CODEC_STATELESS;
+    mp_codec_stream *cstream = nullptr;
+    mp_codec *cstream_codec = nullptr;
+    int cstream_lanes = 0;
     bool xa_direct = false;    // this batch runs the direct XA form (f32 / bf16 modes)
     int kv16 = 0;             // the current batch's SA cache holds bf16
     // device state (one allocation per buffer, sized for the configuration)
@@ -1111,6 +1118,12 @@ int mp_hip_set_xa_mode(mp_dev *dev, int xa_mode) {
     return MP_OK;
 }
 
+int mp_hip_set_stream_codec_mode(mp_dev *dev, int mode) {
+    if (!dev || (mode != MP_STREAM_CODEC_STATELESS && mode != MP_STREAM_CODEC_CONTINUOUS)) return MP_ERR_ARG;
+    dev->stream_codec_mode = mode;
+    return MP_OK;
+}
+
 int mp_hip_set_kv_mode(mp_dev *dev, int kv_mode) {
     if (!dev || (kv_mode != MP_KV_F32 && kv_mode != MP_KV_BF16)) return MP_ERR_ARG;
     dev->kv_mode = kv_mode;
@@ -1123,6 +1136,7 @@ void mp_hip_free(mp_dev *dev) {
     if (dev->stream) hipStreamSynchronize(dev->stream);
     if (dev->side) hipStreamSynchronize(dev->side);
     free_batch(dev);  // the graph; every owner releases in ~mp_dev, the streams last
+    mp_hip_codec_stream_free(dev->cstream);  // its own memory only: the codec may be gone already
     delete dev;
 }
 
@@ -1648,6 +1662,23 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
     const int fpc = frames_per_chunk > 0 ? frames_per_chunk : 4;  // default 4 (magpie.h:621)
     HIPCHK(hipSetDevice(dev->device));
     const int NB = dev->NB, B = dev->B, S = dev->max_steps;
+    // continuous codec: slot b decodes on lane b, every lane at the start of an utterance
+    const bool cont = dev->stream_codec_mode == MP_STREAM_CODEC_CONTINUOUS;
+    if (cont) {
+        if (!dev->cstream || dev->cstream_codec != codec || dev->cstream_lanes < B) {
+            mp_hip_codec_stream_free(dev->cstream);
+            dev->cstream = nullptr;
+            if (int rc = mp_hip_codec_stream_create(codec, B, &dev->cstream))
+                return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
+            dev->cstream_codec = codec;
+            dev->cstream_lanes = B;
+        }
+        if (int rc = mp_hip_codec_stream_reset(dev->cstream, -1))
+            return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
+    }
+    std::vector<int32_t> wave_ids, wave_codes;  // continuous: one stream decode's lanes and codes
+    std::vector<float> wave_audio;
+    std::vector<int> nth;
     if (int rc = prepare_iteration(dev)) return rc;
     for (mp::Event &e : dev->sev) HIPCHK(e.create(hipEventDisableTiming));
     // pinned: a copy into pageable memory would block the host until the chunk's kernels finish
@@ -1742,14 +1773,51 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
             for (int t = 0; t < j.n; ++t)  // frame-major -> codebook-major (decode_frames_to_audio, 4468-4473)
                 for (int c = 0; c < 8; ++c) dst[(size_t)c * j.n + t] = fm[(size_t)t * 8 + c];
         }
-        if (nfull)
-            if (int rc = mp_hip_codec_decode_chunks(codec, cbm.data(), (int)nfull, fpc, audio.data()))
-                return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-        for (size_t q = 0; q < jobs.size(); ++q)
-            if (jobs[q].n != fpc)
-                if (int rc = mp_hip_codec_decode(codec, cbm.data() + at[q] * 8 * fpc, jobs[q].n,
-                                                 audio.data() + at[q] * fpc * 1024))
+        if (cont) {
+            // a lane's chunks go in frame order, one per call: call w takes the w-th chunk of
+            // every slot that has one, the full ones together, a shorter final one on its own
+            nth.assign(jobs.size(), 0);
+            int calls = 0;
+            for (size_t q = 0; q < jobs.size(); ++q) {
+                nth[q] = q && jobs[q - 1].b == jobs[q].b ? nth[q - 1] + 1 : 0;
+                calls = std::max(calls, nth[q] + 1);
+            }
+            for (int w = 0; w < calls; ++w) {
+                wave_ids.clear();
+                wave_codes.clear();
+                for (size_t q = 0; q < jobs.size(); ++q)
+                    if (nth[q] == w && jobs[q].n == fpc) {
+                        wave_ids.push_back(jobs[q].b);
+                        wave_codes.insert(wave_codes.end(), cbm.begin() + at[q] * 8 * fpc, cbm.begin() + (at[q] + 1) * 8 * fpc);
+                    }
+                if (!wave_ids.empty()) {
+                    wave_audio.resize(wave_ids.size() * fpc * 1024);
+                    if (int rc = mp_hip_codec_stream_decode(dev->cstream, wave_ids.data(), (int)wave_ids.size(),
+                                                            wave_codes.data(), fpc, wave_audio.data()))
+                        return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
+                    size_t k = 0;
+                    for (size_t q = 0; q < jobs.size(); ++q)
+                        if (nth[q] == w && jobs[q].n == fpc)
+                            memcpy(audio.data() + at[q] * fpc * 1024, wave_audio.data() + k++ * fpc * 1024, (size_t)fpc * 4096);
+                }
+                for (size_t q = 0; q < jobs.size(); ++q)
+                    if (nth[q] == w && jobs[q].n != fpc) {
+                        const int32_t lane = jobs[q].b;
+                        if (int rc = mp_hip_codec_stream_decode(dev->cstream, &lane, 1, cbm.data() + at[q] * 8 * fpc, jobs[q].n,
+                                                                audio.data() + at[q] * fpc * 1024))
+                            return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
+                    }
+            }
+        } else {
+            if (nfull)
+                if (int rc = mp_hip_codec_decode_chunks(codec, cbm.data(), (int)nfull, fpc, audio.data()))
                     return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
+            for (size_t q = 0; q < jobs.size(); ++q)
+                if (jobs[q].n != fpc)
+                    if (int rc = mp_hip_codec_decode(codec, cbm.data() + at[q] * 8 * fpc, jobs[q].n,
+                                                     audio.data() + at[q] * fpc * 1024))
+                        return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
+        }
         if (stream_trace()) fprintf(stderr, "[stream]   codec of %zu chunks done at %.3f ms\n", jobs.size(), ms_since(t0));
         if (queued.valid())
             if (int rc = queued.get()) return rc;

@@ -108,10 +108,16 @@ SYMBOLS = [
     ("mp_hip_codec_last_ms", _I, [_P, ctypes.POINTER(ctypes.c_float)]),
     ("mp_hip_codec_free", None, [_P]),
     ("mp_hip_codec_error", ctypes.c_char_p, [_P]),
+    ("mp_hip_codec_stream_create", _I, [_P, _I, ctypes.POINTER(_P)]),
+    ("mp_hip_codec_stream_decode", _I, [_P, _P, _I, _P, _I, _P]),
+    ("mp_hip_codec_stream_reset", _I, [_P, _I]),
+    ("mp_hip_codec_stream_free", None, [_P]),
+    ("mp_hip_set_stream_codec_mode", _I, [_P, _I]),
 ]
 
 # entry points added after round 4: absent from the A/B baseline libraries
-OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue"}
+OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue", "mp_hip_codec_stream_create", "mp_hip_codec_stream_decode",
+            "mp_hip_codec_stream_reset", "mp_hip_codec_stream_free", "mp_hip_set_stream_codec_mode"}
 
 _lib = None
 
@@ -357,17 +363,22 @@ class Device:
     def synthesize_stream(self, codec: "Codec", tokens: Sequence[Sequence[int]], on_audio,
                           speakers: Optional[Sequence[int]] = None, max_dec_steps: int = 500,
                           temperature: float = 0.0, top_k: int = 80, seed: int = 0, frames_per_chunk: int = 4,
-                          stream_base: int = 0, ignore_eos: bool = False):
+                          stream_base: int = 0, ignore_eos: bool = False, continuous: bool = False):
         """magpie_synthesize_sentence_streaming over a batch: on_audio(utt, np.ndarray) -> bool
         (False stops that utterance). The EOS frame is emitted, as the reference's streaming
-        loop does. Returns (codes per utterance, total samples, timing)."""
+        loop does. continuous: every utterance's chunks on a lane of a stateful codec stream,
+        so its concatenated audio is Codec.decode of its frames (default: stateless chunks).
+        Returns (codes per utterance, total samples, timing)."""
         B = self.begin(tokens, speakers, max_dec_steps, temperature, top_k, ignore_eos, seed, False, stream_base, True)
-        return self.decode_stream_only(codec, on_audio, B, max_dec_steps, frames_per_chunk)
+        return self.decode_stream_only(codec, on_audio, B, max_dec_steps, frames_per_chunk, continuous)
 
-    def decode_stream_only(self, codec: "Codec", on_audio, B: int, max_dec_steps: int, frames_per_chunk: int = 4):
+    def decode_stream_only(self, codec: "Codec", on_audio, B: int, max_dec_steps: int, frames_per_chunk: int = 4,
+                           continuous: bool = False):
         """mp_hip_decode_stream on the batch the last begin() prepared (the preamble is not
         re-run): the decode on this device's stream, each chunk through the codec on the
         codec's stream as it completes. Returns (codes per utterance, total samples, timing)."""
+        if continuous or hasattr(self.lib, "mp_hip_set_stream_codec_mode"):
+            self._check(self.lib.mp_hip_set_stream_codec_mode(self.h, 1 if continuous else 0))
         def _cb(utt, ptr, n, _user):
             if n == 0:  # end-of-utterance notice
                 return 1
@@ -554,10 +565,70 @@ class Codec:
         self.lib.mp_hip_codec_last_ms(self.h, ctypes.byref(ms))
         return ms.value
 
+    def stream(self, lanes: int = 1) -> "CodecStream":
+        """A stateful streaming decode of `lanes` independent lanes (mp_hip_codec_stream_*)."""
+        return CodecStream(self, lanes)
+
     def close(self) -> None:
         if getattr(self, "h", None) is not None and self.h.value:
+            for s in list(getattr(self, "_streams", [])):  # a stream borrows the codec: freed first
+                s.close()
             self.lib.mp_hip_codec_free(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CodecStream:
+    """Consecutive chunks of one utterance decoded on one lane give, bit for bit, the samples
+    Codec.decode of all its frames gives: a lane carries every conv's left context from chunk
+    to chunk (include/magpie_hip.h, mp_hip_codec_stream_*)."""
+
+    def __init__(self, codec: Codec, lanes: int = 1):
+        self.codec, self.lib, self.lanes = codec, codec.lib, lanes
+        if not hasattr(self.lib, "mp_hip_codec_stream_create"):
+            raise MagpieError("this libmagpie_hip.so has no stateful codec stream")
+        h = ctypes.c_void_p()
+        self.h = None
+        self._check(self.lib.mp_hip_codec_stream_create(codec.h, lanes, ctypes.byref(h)))
+        self.h = h
+        if not hasattr(codec, "_streams"):
+            codec._streams = []
+        codec._streams.append(self)
+
+    def _check(self, rc: int) -> None:
+        if rc != MP_OK:
+            raise MagpieError(f"{_ERRS.get(rc, rc)}: {self.lib.mp_hip_codec_error(self.codec.h).decode(errors='replace')}")
+
+    def decode(self, codes: np.ndarray, lanes: Optional[Sequence[int]] = None) -> np.ndarray:
+        """The next chunk of each given lane. codes [8][F] -> audio [F*1024] on lane 0 (or
+        lanes[0]); codes [n][8][F] -> audio [n][F*1024] on `lanes` (default 0..n-1), distinct."""
+        codes = np.ascontiguousarray(codes, np.int32)
+        single = codes.ndim == 2
+        if single:
+            codes = codes[None]
+        n, eight, F = codes.shape
+        assert eight == 8
+        ids = np.ascontiguousarray(np.arange(n) if lanes is None else lanes, np.int32)
+        assert ids.shape == (n,)
+        out = np.zeros((n, F * 1024), np.float32)
+        self._check(self.lib.mp_hip_codec_stream_decode(self.h, ids.ctypes.data, n, codes.ctypes.data, F, out.ctypes.data))
+        return out[0] if single else out
+
+    def reset(self, lane: int = -1) -> None:
+        """Back to the start of an utterance on `lane` (-1: every lane)."""
+        self._check(self.lib.mp_hip_codec_stream_reset(self.h, lane))
+
+    def close(self) -> None:
+        if getattr(self, "h", None) is not None and self.h.value:
+            self.lib.mp_hip_codec_stream_free(self.h)
+            self.h = None
+            if self in getattr(self.codec, "_streams", []):
+                self.codec._streams.remove(self)
 
     def __del__(self):
         try:

@@ -2,7 +2,9 @@
 // reference CLI's flags, defaults and output (src/magpie-tts.cpp:11-229): text ->
 // tokens -> codes (graph-reuse decode loop) -> 32-frame stateless codec chunks ->
 // 16-bit mono WAV at 22050 Hz. Extra flags: --stream (sentence-chunked streaming
-// synthesis, magpie.cpp:4843-4863), --bf16 (bf16 decode projections), --seed.
+// synthesis, magpie.cpp:4843-4863), --bf16 (bf16 decode projections), --seed,
+// --continuous-codec (the codec carries its conv state from chunk to chunk: the chunks'
+// audio is one decode of all the frames; with --stream, of each sentence's frames).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +28,7 @@ void usage(const char *prog) {
             "  --top-k INT          top-k sampling (default: 80)\n"
             "  --seed N             sampling stream seed (default: 0)\n"
             "  --stream             sentence-chunked streaming synthesis (4-frame codec chunks)\n"
+            "  --continuous-codec   codec chunks carry their conv state: seamless across chunks\n"
             "  --bf16               bf16 decode projections (MFMA)\n"
             "  -q, --quiet          minimal output\n"
             "  -h, --help           this help\n",
@@ -76,7 +79,7 @@ int main(int argc, char **argv) {
     int speaker = 0, top_k = 80;
     float temp = 0.7f;
     unsigned long long seed = 0;
-    bool quiet = false, stream = false, bf16 = false;
+    bool quiet = false, stream = false, bf16 = false, continuous = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&](const char *what) -> const char * {
@@ -96,6 +99,7 @@ int main(int argc, char **argv) {
         else if (a == "--top-k") top_k = atoi(val("--top-k"));
         else if (a == "--seed") seed = strtoull(val("--seed"), nullptr, 10);
         else if (a == "--stream") stream = true;
+        else if (a == "--continuous-codec") continuous = true;
         else if (a == "--bf16") bf16 = true;
         else if (a == "-q" || a == "--quiet") quiet = true;
         else {
@@ -119,6 +123,7 @@ int main(int argc, char **argv) {
     ctx->top_k = top_k;
     ctx->speaker_id = speaker;
     ctx->seed = seed;
+    ctx->continuous_codec = continuous;
     magpie_codec *codec = magpie_codec_init(codec_path);
     if (!codec) {
         fprintf(stderr, "Error: Failed to load codec from %s\n", codec_path);
@@ -145,16 +150,20 @@ int main(int argc, char **argv) {
             const std::vector<int32_t> codes = magpie_synthesize_codes_graph_reuse(ctx, tokens.data(), (int)tokens.size());
             const int n = (int)codes.size() / 8;
             if (codes.empty()) rc = 1;
-            // stateless 32-frame codec chunks, frame-major -> codebook-major (magpie-tts.cpp:181-206)
+            magpie_codec_stream *cs = continuous ? magpie_codec_stream_init(codec) : nullptr;
+            if (continuous && !cs) rc = 1;
+            // stateless 32-frame codec chunks, frame-major -> codebook-major (magpie-tts.cpp:181-206);
+            // --continuous-codec: the same chunks through one stream lane
             for (int c0 = 0; rc == 0 && c0 < n; c0 += 32) {
                 const int f = std::min(32, n - c0);
                 std::vector<int32_t> cb((size_t)8 * f);
                 for (int t = 0; t < f; ++t)
                     for (int k = 0; k < 8; ++k) cb[(size_t)k * f + t] = codes[(size_t)(c0 + t) * 8 + k];
-                const std::vector<float> a = magpie_codec_decode(codec, cb.data(), f);
+                const std::vector<float> a = cs ? magpie_codec_stream_decode(cs, cb.data(), f) : magpie_codec_decode(codec, cb.data(), f);
                 if (a.empty()) rc = 1;
                 audio.insert(audio.end(), a.begin(), a.end());
             }
+            magpie_codec_stream_free(cs);
         }
     }
     if (rc == 0 && !write_wav(out, audio, 22050)) {
