@@ -255,6 +255,18 @@ int magpie_synthesize_streaming(magpie_context *ctx, magpie_codec *codec, const 
                                 const magpie_stream_params &params);
 int magpie_synthesize_sentence_streaming(magpie_context *ctx, magpie_codec *codec, const int32_t *tokens,
                                          int n_tokens, const magpie_stream_params &params);
+// Added: the streaming slot pool (mp_hip_decode_queue_stream). N independent utterances through
+// `slots` refilled decode slots (1..mp_hip_max_batch), each utterance's audio handed to
+// on_audio chunk by chunk as it is produced, under the utterance's index; samples == nullptr
+// marks that utterance's end. Returning false stops that utterance. Temperature, top_k,
+// speaker, frames_per_chunk and user_data come from `params` (its own on_audio is not
+// used), seed and continuous_codec from the context. codes_out (nullable, [N]) receives every
+// utterance's codes. Returns the total number of samples, or -1.
+typedef bool (*magpie_utterance_audio_callback)(int utterance, const float *samples, int n_samples, void *user_data);
+int magpie_synthesize_streaming_queue(magpie_context *ctx, magpie_codec *codec, const int32_t *const *tokens,
+                                      const int *n_tokens, int N, int slots, const magpie_stream_params &params,
+                                      magpie_utterance_audio_callback on_audio,
+                                      std::vector<int32_t> *codes_out /*nullable, [N]*/);
 
 // magpie.h:823 utility
 bool magpie_is_eos(const std::vector<int32_t> &frame_codes, int32_t eos_id);

@@ -58,7 +58,7 @@ typedef struct mp_timing {
     double decode_ms;    /* BOS step + autoregressive loop (gen_time, magpie.cpp:4265,4409) */
     int frames_total;    /* frames produced over all utterances */
     int iterations;      /* decode iterations (graph replays) executed */
-    double first_audio_ms; /* mp_hip_decode_stream: decode start -> first audio callback */
+    double first_audio_ms; /* mp_hip_decode_stream, mp_hip_decode_queue_stream: decode start -> first audio callback */
 } mp_timing;
 
 /* --- device + weights ---------------------------------------------------- */
@@ -131,8 +131,9 @@ int mp_hip_set_kv_mode(mp_dev *dev, int kv_mode);
 #define MP_XA_DIRECT 2
 #define MP_XA_DIRECT_T 160
 int mp_hip_set_xa_mode(mp_dev *dev, int xa_mode);
-/* How mp_hip_decode_stream decodes its chunks, applied from the next call. STATELESS
- * (default): each chunk on its own, as the reference does (magpie.cpp:4458-4476).
+/* How mp_hip_decode_stream and mp_hip_decode_queue_stream decode their chunks, applied from
+ * the next call. STATELESS (default): each chunk on its own, as the reference does
+ * (magpie.cpp:4458-4476).
  * CONTINUOUS: utterance b's chunks on lane b of a stateful codec stream
  * (mp_hip_codec_stream_*), so its concatenated audio is, bit for bit, one
  * mp_hip_codec_decode of its frames. */
@@ -220,6 +221,30 @@ int64_t mp_hip_debug_buffer(mp_dev *dev, const char *name, void *host, int64_t b
 typedef int (*mp_audio_cb)(int utterance, const float *samples, int n_samples, void *user);
 int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_audio_cb on_audio, void *user,
                          int32_t *codes_out, int32_t *n_frames, int64_t *total_samples);
+/* The streaming slot pool: mp_hip_decode_queue's N utterances through `slots` refilled slots,
+ * each utterance's audio handed out chunk by chunk as mp_hip_decode_stream does. No reference
+ * counterpart (the reference streams one sentence at a time). A round is frames_per_chunk
+ * (<= 0: 4) graph replays; at a round end the host takes, in slot order, one chunk of the
+ * 1..frames_per_chunk frames each slot produced in the round, decodes the round's chunks
+ * (CONTINUOUS, mp_hip_set_stream_codec_mode: one ragged stream decode, slot b on lane b, so an
+ * utterance's concatenated audio is bit for bit mp_hip_codec_decode of its frames; STATELESS:
+ * each chunk on its own, the full ones through one mp_hip_codec_decode_chunks) and calls
+ * on_audio(utt, samples, n * 1024, user) with the utterance's index, not the slot's. For a
+ * slot whose utterance ended it then calls on_audio(utt, NULL, 0, user) and done(utt, codes,
+ * n_frames, user) (done may be NULL), resets the slot's lane and installs the staged utterance
+ * as mp_hip_decode_queue does; installs happen at round ends only, and they and the next
+ * round's replays are queued before the round's codec work. on_audio returning 0 ends that
+ * utterance: the frames of the round already queued are not delivered, done reports the
+ * delivered frames, the slot is refilled at the next round end. Codes, draw streams
+ * (stream_base + utterance), SA cache type and XA form as for mp_hip_decode_queue; the
+ * iteration count is that of mp_hip_decode_queue with poll = frames_per_chunk. Arguments are
+ * checked before anything runs (codec and on_audio required, trace_hidden refused, slots
+ * 1..mp_hip_max_batch): a refused call leaves device, codec and stream usable.
+ * mp_hip_get_timing's first_audio_ms runs from the loop's start to the first on_audio. */
+int mp_hip_decode_queue_stream(mp_dev *dev, mp_codec *codec, const int32_t *tokens, const int32_t *n_tokens,
+                               const int32_t *speaker, int N, int tmax, int slots, int frames_per_chunk,
+                               const mp_params *params, mp_next_cb next, mp_audio_cb on_audio, mp_done_cb done,
+                               void *user, mp_queue_stats *stats);
 
 /* magpie_local_transformer_sample_all (magpie.cpp:1113-1317) for one normalised
  * decoder hidden vector [768]: sampled[8] and argmax[8] codes. Independent of any
@@ -301,6 +326,16 @@ int mp_hip_codec_stream_create(mp_codec *c, int lanes, mp_codec_stream **out); /
  * mp_hip_codec_last_ms reports this decode too. */
 int mp_hip_codec_stream_decode(mp_codec_stream *s, const int32_t *lane_ids, int n, const int32_t *codes, int n_frames,
                                float *audio_out);
+/* One chunk on each of n distinct lanes, lane q's chunk n_frames[q] frames long
+ * (1 <= n_frames[q] <= max_frames), in the same launch sequence: a one-frame chunk beside
+ * 32-frame ones costs no call of its own. codes [n][8][max_frames] codebook-major, lane q's
+ * row holding n_frames[q] frames (the rest ignored); audio_out [n][max_frames * 1024], lane
+ * q's first n_frames[q] * 1024 samples valid (the rest unspecified). Lane q's state advances
+ * by n_frames[q], whatever the other lanes of the call do; a failed call advances nothing.
+ * MP_ERR_ARG as above, and for a length outside 1..max_frames. The call above is this one
+ * with every length equal. */
+int mp_hip_codec_stream_decode_ragged(mp_codec_stream *s, const int32_t *lane_ids, int n, const int32_t *codes,
+                                      const int32_t *n_frames, int max_frames, float *audio_out);
 /* back to the start of an utterance; lane < 0: all lanes */
 int mp_hip_codec_stream_reset(mp_codec_stream *s, int lane);
 void mp_hip_codec_stream_free(mp_codec_stream *s);

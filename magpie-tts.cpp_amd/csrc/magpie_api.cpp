@@ -466,3 +466,48 @@ int magpie_synthesize_streaming(magpie_context *ctx, magpie_codec *codec, const 
     }
     return (int)total;
 }
+
+// The streaming slot pool (mp_hip_decode_queue_stream) behind the drop-in types
+int magpie_synthesize_streaming_queue(magpie_context *ctx, magpie_codec *codec, const int32_t *const *tokens,
+                                      const int *n_tokens, int N, int slots, const magpie_stream_params &params,
+                                      magpie_utterance_audio_callback on_audio, std::vector<int32_t> *codes_out) {
+    if (!ctx || !ctx->model.dev || !codec || !codec->dev || !tokens || !n_tokens || N < 1 || !on_audio) return -1;
+    int tmax = 0;
+    for (int i = 0; i < N; ++i) {
+        if (!tokens[i] || n_tokens[i] <= 0) return -1;
+        tmax = std::max(tmax, n_tokens[i]);
+    }
+    ctx->temperature = params.temperature;  // as the streaming calls do
+    ctx->top_k = params.top_k;
+    ctx->speaker_id = params.speaker_id;
+    std::vector<int32_t> tok((size_t)N * tmax, 0), nt(N), spk(N, params.speaker_id);
+    for (int i = 0; i < N; ++i) {
+        nt[i] = n_tokens[i];
+        std::copy(tokens[i], tokens[i] + n_tokens[i], tok.begin() + (size_t)i * tmax);
+    }
+    const mp_params p = params_of(ctx);
+    struct Run {
+        magpie_utterance_audio_callback on_audio;
+        void *user_data;
+        std::vector<int32_t> *codes;
+        long long samples;
+    } run{on_audio, params.user_data, codes_out, 0};
+    if (codes_out)
+        for (int i = 0; i < N; ++i) codes_out[i].clear();
+    auto audio = [](int utt, const float *x, int n, void *user) -> int {
+        Run &r = *(Run *)user;
+        r.samples += n;
+        return r.on_audio(utt, x, n, r.user_data) || !x ? 1 : 0;
+    };
+    auto done = [](int utt, const int32_t *codes, int n_frames, void *user) {
+        Run &r = *(Run *)user;
+        if (r.codes) r.codes[utt].assign(codes, codes + (size_t)n_frames * 8);
+    };
+    mp_hip_set_stream_codec_mode(ctx->model.dev, ctx->continuous_codec ? MP_STREAM_CODEC_CONTINUOUS : MP_STREAM_CODEC_STATELESS);
+    if (mp_hip_decode_queue_stream(ctx->model.dev, codec->dev, tok.data(), nt.data(), spk.data(), N, tmax, slots,
+                                   params.frames_per_chunk, &p, nullptr, audio, done, &run, nullptr) != MP_OK) {
+        fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));
+        return -1;
+    }
+    return (int)run.samples;
+}

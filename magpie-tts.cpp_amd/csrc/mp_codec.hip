@@ -156,6 +156,8 @@ __device__ __forceinline__ float fsq(int code, int d) {
 // lane's parity only after a call succeeded).
 struct HistP {
     const int *lanes;   // [chunks of the call]: lane * 4 + 2 * (the lane has decoded a chunk) + parity
+    const int *nfr;     // [chunks of the call]: the chunk's own frames, 1..maxf (its rows past them are padding)
+    int maxf;           // frames every chunk of the call is laid out for: a launch's T is maxf * (the stage's rate)
     int nlanes;         // lanes of the stream
     size_t lbytes;      // bytes of one lane's whole state: the state is [parity][lane][lbytes]
     // this launch's piece of the state, in parity 0's lane 0:
@@ -165,6 +167,8 @@ struct HistP {
         return (T *)((char *)base + ((size_t)(ent & 1) * nlanes + (ent >> 2)) * lbytes);
     }
     template <class T> __device__ T *wr(T *base, int ent) const { return rd(base, ent ^ 1); }  // ... and writes
+    // the chunk's own rows of a launch over T rows: the state it leaves is taken at their end
+    __device__ int rows_of(int chunk, int T) const { return nfr[chunk] * (T / maxf); }
 };
 // The kernels that take history are the stateless kernels' templates with a trailing HistP
 // argument (a parameter pack H, empty or {HistP}): without it the signature, the body after
@@ -178,8 +182,10 @@ constexpr int MAXTAPS = 11;
 // for grids too small to hide latency by occupancy; same arithmetic either way.
 // HIST: rows t < 0 come from the lane's tail (IN_FSQ: from the 6 frames of codes the host
 // puts in front of the chunk's, [chunk][8][6 + T], -1 where no frame exists yet: a zero
-// operand). The workgroup of output-channel tile 0 that stages the chunk's last rows
-// writes rows [T - pad, T) of (tail ++ chunk), the next call's tail, as it stages them:
+// operand). The chunk's own rows end at Tl <= T (HistP::rows_of; the rows behind them are
+// padding that no row before them reads, the conv being causal). The workgroup of
+// output-channel tile 0 whose time tile holds row Tl - 1 writes rows [Tl - pad, Tl) of
+// (tail ++ chunk), the next call's tail, as it stages them (its halo reaches back pad rows):
 // a chunk shorter than pad rolls the tail. Fragments and accumulation are untouched.
 template <int BM, int BN, int MODE, bool PIPE, class... H>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p, H... hh) {
@@ -209,15 +215,17 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p, H... hh) {
     const int orow = m0 + rw * 16 + l16;
     const _Float16 *tin = nullptr;
     _Float16 *tout = nullptr;
+    [[maybe_unused]] int Tl = p.T;
     if constexpr (HIST && MODE == IN_F16) {
         const int ent = h.lanes[chunk];
         tin = h.rd(h.tail[br], ent);
-        if (blockIdx.x == 0 && t0 + BN >= p.T) tout = h.wr(h.tail[br], ent);
+        Tl = h.rows_of(chunk, p.T);
+        if (blockIdx.x == 0 && t0 < Tl && t0 + BN >= Tl) tout = h.wr(h.tail[br], ent);
     }
     // HIST: piece q of row t of channel block cb, from the tail where t < 0, and into the new tail
     auto hist_row = [&](int cb, int t, int q, uint4 &v) {
         if (t < 0) v = *(const uint4 *)(tin + ((size_t)cb * pad + (t + pad)) * 32 + 8 * q);
-        if (tout && t >= p.T - pad && t < p.T) *(uint4 *)(tout + ((size_t)cb * pad + (t - (p.T - pad))) * 32 + 8 * q) = v;
+        if (tout && t >= Tl - pad && t < Tl) *(uint4 *)(tout + ((size_t)cb * pad + (t - (Tl - pad))) * 32 + 8 * q) = v;
     };
 
     floatx4 acc[NT];
@@ -373,7 +381,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p, H... hh) {
 // the two kernels give the same bits.
 constexpr int C2_WR = 2, C2_NT = 4;
 // HIST: conv_mfma_kernel's (rows t < 0 from the lane's tail, the new tail left by the
-// workgroup of channel tile 0 that stages the chunk's last rows).
+// workgroup of channel tile 0 whose time tile holds the chunk's own last row).
 template <int KS, int RWV, int CWV, int NCB, int R, bool HIST>
 __device__ __forceinline__ void conv2_body(const ConvP &p, const HistP &h, char *xs) {
     constexpr int NTH = 64 * RWV * CWV;
@@ -398,10 +406,12 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, const HistP &h, char 
     const int rows = BN + pad, items = rows * 4;
     const _Float16 *tin = nullptr;
     _Float16 *tout = nullptr;
+    [[maybe_unused]] int Tl = p.T;
     if constexpr (HIST) {
         const int ent = h.lanes[chunk];
         tin = h.rd(h.tail[br], ent);
-        if (blockIdx.x == 0 && t0 + BN >= p.T) tout = h.wr(h.tail[br], ent);
+        Tl = h.rows_of(chunk, p.T);
+        if (blockIdx.x == 0 && t0 < Tl && t0 + BN >= Tl) tout = h.wr(h.tail[br], ent);
     }
 
     floatx4 acc[C2_WR][C2_NT];
@@ -448,8 +458,8 @@ __device__ __forceinline__ void conv2_body(const ConvP &p, const HistP &h, char 
             if constexpr (HIST)
                 if (e < items) {
                     if (t < 0) xv[u] = *(const uint4 *)(tin + ((size_t)cb * pad + (t + pad)) * 32 + 8 * (e & 3));
-                    if (tout && t >= p.T - pad && t < p.T)
-                        *(uint4 *)(tout + ((size_t)cb * pad + (t - (p.T - pad))) * 32 + 8 * (e & 3)) = xv[u];
+                    if (tout && t >= Tl - pad && t < Tl)
+                        *(uint4 *)(tout + ((size_t)cb * pad + (t - (Tl - pad))) * 32 + 8 * (e & 3)) = xv[u];
                 }
         }
     };
@@ -1085,7 +1095,7 @@ constexpr int CT_R = 8;
 // blocks are fused compute them from the f32 output instead).
 // HIST (stream lanes): input step -1 of a chunk is the lane's previous chunk's last step,
 // kept HalfSnake'd as this kernel computed it then (`cur` of that step: the bits a one-shot
-// decode keeps in `prev`); the thread of the chunk's last step leaves its own. A lane's
+// decode keeps in `prev`); the thread of the chunk's own last step leaves its own. A lane's
 // first chunk skips the tau - 1 term, as step 0 of a one-shot decode does.
 template <int CINP, int COUTP, int S, bool AVG, int R, bool ACT, class... H>
 __global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p, H... hh) {
@@ -1140,9 +1150,11 @@ __global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p, H... hh)
     float prev[4] = {0.f, 0.f, 0.f, 0.f}, cur[4];
     bool has_prev = false;
     float *hout = nullptr;
+    [[maybe_unused]] int Tl = p.Tin;
     if constexpr (HIST) {
         const int ent = h.lanes[chunk];
         hout = h.wr(h.f32, ent);
+        Tl = h.rows_of(chunk, p.Tin);
         if (tau0 == 0 && (ent & 2)) {
             has_prev = true;
             if (c0 < CINP) {
@@ -1188,7 +1200,7 @@ __global__ __launch_bounds__(256) void conv_transpose2_kernel(ConvTP p, H... hh)
             }
         }
         if constexpr (HIST)
-            if (tau == p.Tin - 1 && c0 < CINP) *(float4 *)(hout + c0) = make_float4(cur[0], cur[1], cur[2], cur[3]);
+            if (tau == Tl - 1 && c0 < CINP) *(float4 *)(hout + c0) = make_float4(cur[0], cur[1], cur[2], cur[3]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) prev[i] = cur[i];
     }
@@ -1210,7 +1222,8 @@ struct PostP {
 // taps x 27 channels against the f16-rounded weights.
 // HIST (stream lanes): the 2-row halo of a chunk's first tile is the lane's previous chunk's
 // last two operand rows (f16-rounded HalfSnake of the mean, as staged then; zeros before the
-// lane's first chunk, the causal padding); the chunk's last tile leaves its own.
+// lane's first chunk, the causal padding); the tile that holds the chunk's own last row
+// leaves its own.
 template <class... H>
 __global__ __launch_bounds__(256) void post_conv_kernel(PostP p, H... hh) {
     constexpr bool HIST = sizeof...(H) != 0;
@@ -1247,9 +1260,12 @@ __global__ __launch_bounds__(256) void post_conv_kernel(PostP p, H... hh) {
     }
     __syncthreads();
     if constexpr (HIST)
-        if (t0 + 256 >= p.T && threadIdx.x < 56) {  // rows T - 2, T - 1 (T >= 1024: this tile holds both)
-            const int ent = h.lanes[chunk];
-            h.wr(h.f32, ent)[threadIdx.x] = hs[p.T - t0 + threadIdx.x / 28][threadIdx.x % 28];
+        if (threadIdx.x < 56) {  // rows Tl - 2, Tl - 1 (Tl a multiple of 1024: the tile of Tl - 1 holds both)
+            const int Tl = h.rows_of(chunk, p.T);
+            if (t0 < Tl && t0 + 256 >= Tl) {
+                const int ent = h.lanes[chunk];
+                h.wr(h.f32, ent)[threadIdx.x] = hs[Tl - t0 + threadIdx.x / 28][threadIdx.x % 28];
+            }
         }
     const int t = t0 + threadIdx.x;
     if (t >= p.T) return;
@@ -1293,7 +1309,8 @@ struct mp_codec {
     unsigned long long *ts_dev = nullptr;
     int ts_stage = -1, ts_block = -1;
     std::string ts_file;
-    int *lane_tab = nullptr;  // stream decodes: the call's lane table (mpc::HistP::lanes), behind its codes
+    int *lane_tab = nullptr;  // stream decodes: the call's lane table (mpc::HistP::lanes) and, behind it, the
+                              // chunks' own frame counts (mpc::HistP::nfr), behind its codes
 };
 
 // Stateful streaming decode: per lane, what the next chunk's first outputs need from the
@@ -1686,14 +1703,17 @@ hipError_t launch_convt_stream(const mpc::ConvTP &p, const mpc::HistP &h, hipStr
     return hipGetLastError();
 }
 
-// One chunk of F frames on each of n lanes (c->lane_tab; c->codes [n][8][6 + F]): codec_run's
-// two-launch residual blocks with every loader reading the lane's state and leaving the next.
+// One chunk on each of n lanes, laid out for F frames each, chunk q's own frames c->lane_tab[n + q]
+// (c->lane_tab; c->codes [n][8][6 + F], -1 behind a chunk's own frames): codec_run's two-launch
+// residual blocks with every loader reading the lane's state and leaving the next.
 int codec_stream_run(mp_codec_stream *st, int n, int F) {
     using namespace mpc;
     mp_codec *c = st->c;
     hipStream_t s = c->stream;
     HistP h{};
     h.lanes = c->lane_tab;
+    h.nfr = c->lane_tab + n;
+    h.maxf = F;
     h.nlanes = st->lanes;
     h.lbytes = st->lbytes;
     {
@@ -1892,11 +1912,14 @@ int mp_hip_codec_stream_create(mp_codec *c, int lanes, mp_codec_stream **out) {
     return MP_OK;
 }
 
-int mp_hip_codec_stream_decode(mp_codec_stream *st, const int32_t *lane_ids, int n, const int32_t *codes, int n_frames,
-                               float *audio_out) {
+int mp_hip_codec_stream_decode_ragged(mp_codec_stream *st, const int32_t *lane_ids, int n, const int32_t *codes,
+                                      const int32_t *n_frames, int max_frames, float *audio_out) {
     if (!st) return MP_ERR_ARG;
     mp_codec *c = st->c;
-    if (!lane_ids || !codes || !audio_out || n < 1 || n_frames < 1) { c->err = "stream decode: invalid arguments"; return MP_ERR_ARG; }
+    if (!lane_ids || !codes || !n_frames || !audio_out || n < 1 || max_frames < 1) {
+        c->err = "stream decode: invalid arguments";
+        return MP_ERR_ARG;
+    }
     if (n > st->lanes) { c->err = "stream decode: more lanes than the stream has"; return MP_ERR_ARG; }
     for (int q = 0; q < n; ++q) {
         if (lane_ids[q] < 0 || lane_ids[q] >= st->lanes) {
@@ -1908,25 +1931,32 @@ int mp_hip_codec_stream_decode(mp_codec_stream *st, const int32_t *lane_ids, int
                 c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " given twice";
                 return MP_ERR_ARG;
             }
+        if (n_frames[q] < 1 || n_frames[q] > max_frames) {
+            c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " has " + std::to_string(n_frames[q]) +
+                     " frames, not 1.." + std::to_string(max_frames);
+            return MP_ERR_ARG;
+        }
     }
-    const int F = n_frames, FH = F + 6;
+    const int F = max_frames, FH = F + 6;
     CHK(hipSetDevice(c->device));
     const size_t ncodes = (size_t)n * 8 * FH, nsamp = (size_t)n * F * mpc::HOP;
-    if (int rc = ensure_buffers(c, n, F, (size_t)n * 8 * 6 + n)) return rc;
+    if (int rc = ensure_buffers(c, n, F, (size_t)n * 8 * 6 + 2 * (size_t)n)) return rc;
     c->lane_tab = c->codes + ncodes;
-    CHK(c->codes_pin.reserve((ncodes + n) * 4));
+    CHK(c->codes_pin.reserve((ncodes + 2 * (size_t)n) * 4));
     CHK(c->audio_pin.reserve(nsamp * 4));
     int32_t *hc = (int32_t *)c->codes_pin.p;
     for (int q = 0; q < n; ++q) {
-        const int ln = lane_ids[q];
-        for (int cb = 0; cb < 8; ++cb) {
+        const int ln = lane_ids[q], nf = n_frames[q];
+        for (int cb = 0; cb < 8; ++cb) {  // [6 of history | the chunk's own frames | -1: a zero operand]
             int32_t *row = hc + ((size_t)q * 8 + cb) * FH;
             memcpy(row, st->hist.data() + (size_t)ln * 48 + cb * 6, 6 * 4);
-            memcpy(row + 6, codes + ((size_t)q * 8 + cb) * F, (size_t)F * 4);
+            memcpy(row + 6, codes + ((size_t)q * 8 + cb) * F, (size_t)nf * 4);
+            std::fill(row + 6 + nf, row + FH, -1);
         }
         hc[ncodes + q] = ln * 4 + 2 * st->started[ln] + st->parity[ln];
+        hc[ncodes + n + q] = nf;
     }
-    CHK(hipMemcpyAsync(c->codes, hc, (ncodes + n) * 4, hipMemcpyHostToDevice, c->stream));
+    CHK(hipMemcpyAsync(c->codes, hc, (ncodes + 2 * (size_t)n) * 4, hipMemcpyHostToDevice, c->stream));
     CHK(c->ev0.create());
     CHK(c->ev1.create());
     CHK(hipEventRecord(c->ev0, c->stream));
@@ -1941,10 +1971,19 @@ int mp_hip_codec_stream_decode(mp_codec_stream *st, const int32_t *lane_ids, int
         const int ln = lane_ids[q];
         st->parity[ln] ^= 1;
         st->started[ln] = 1;
-        for (int cb = 0; cb < 8; ++cb)  // the last 6 of (history ++ chunk)
-            memcpy(st->hist.data() + (size_t)ln * 48 + cb * 6, hc + ((size_t)q * 8 + cb) * FH + F, 6 * 4);
+        for (int cb = 0; cb < 8; ++cb)  // the last 6 of (history ++ the chunk's own frames)
+            memcpy(st->hist.data() + (size_t)ln * 48 + cb * 6, hc + ((size_t)q * 8 + cb) * FH + n_frames[q], 6 * 4);
     }
     return MP_OK;
+}
+
+// the ragged call with every length equal
+int mp_hip_codec_stream_decode(mp_codec_stream *st, const int32_t *lane_ids, int n, const int32_t *codes, int n_frames,
+                               float *audio_out) {
+    if (!st) return MP_ERR_ARG;
+    if (n < 1 || n_frames < 1) { st->c->err = "stream decode: invalid arguments"; return MP_ERR_ARG; }
+    const std::vector<int32_t> nf((size_t)n, n_frames);
+    return mp_hip_codec_stream_decode_ragged(st, lane_ids, n, codes, nf.data(), n_frames, audio_out);
 }
 
 int mp_hip_codec_stream_reset(mp_codec_stream *st, int lane) {

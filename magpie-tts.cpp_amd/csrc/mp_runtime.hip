@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <future>
 #include <string>
 #include <vector>
@@ -129,7 +130,8 @@ struct mp_dev {
     mp_params params{};
     int kv_mode = MP_KV_F32;  // mp_hip_set_kv_mode: applies from the next mp_hip_begin_batch
     int xa_mode = MP_XA_AUTO;  // mp_hip_set_xa_mode: likewise
-    // mp_hip_set_stream_codec_mode: applies from the next mp_hip_decode_stream. CONTINUOUS:
+    // mp_hip_set_stream_codec_mode: applies from the next mp_hip_decode_stream or
+    // mp_hip_decode_queue_stream. CONTINUOUS:
     // slot b is lane b of `cstream`, made on the first use of a codec and kept while the
     // codec and the lane count hold (released by mp_hip_free, which does not touch the codec)
     int stream_codec_mode = MP_STREAM_CODEC_STATELESS;
@@ -1452,6 +1454,8 @@ struct PoolRun {
     int seq = 0;
     bool drained = false;
     std::vector<char> claimed;
+    int cur = 0;          // the staging workspace the next install reads
+    bool staged = false;  // ... holds an utterance: one is always staged ahead while any remain
     mp::Pinned h;  // [ndone 4 | done 16 | nframes 16 | codes max_steps x 8]
     mp::Event e0, e1;
     mp_queue_stats st{};
@@ -1515,9 +1519,29 @@ static int pool_install(mp_dev *dev, PoolRun &r, StageWs &s, int b) {
     return MP_OK;
 }
 
-static int pool_run(mp_dev *dev, PoolRun &r) {
-    // the first `slots` claimed utterances: an ordinary batch at text stride tmax
-    std::vector<int> occ;  // utterance of each slot, -1 once handed out
+// the next claimed utterance's preamble into workspace ws (nothing once the queue is drained)
+static int pool_stage_next(mp_dev *dev, PoolRun &r, int ws) {
+    int u;
+    if (int rc = pool_claim(dev, r, &u)) return rc;
+    if (u < 0) return MP_OK;
+    if (int rc = ensure_stage(dev, r.tmax)) return rc;
+    if (int rc = pool_stage(dev, r, dev->stage[ws], u)) return rc;
+    r.cur = ws;
+    r.staged = true;
+    return MP_OK;
+}
+// slot b takes the staged utterance, and the one after it is staged
+static int pool_refill(mp_dev *dev, PoolRun &r, std::vector<int> &occ, int b) {
+    StageWs &s = dev->stage[r.cur];
+    occ[b] = s.utt;
+    ++r.st.refills;
+    r.staged = false;
+    if (int rc = pool_install(dev, r, s, b)) return rc;
+    return pool_stage_next(dev, r, r.cur ^ 1);
+}
+// The first `slots` claimed utterances: an ordinary batch at text stride tmax, its iteration
+// prepared and the next utterance staged. occ: the utterance of each slot (empty: nothing to run).
+static int pool_start(mp_dev *dev, PoolRun &r, std::vector<int> &occ) {
     for (int b = 0; b < r.slots; ++b) {
         int u;
         if (int rc = pool_claim(dev, r, &u)) return rc;
@@ -1543,23 +1567,17 @@ static int pool_run(mp_dev *dev, PoolRun &r) {
     }
     dev->batch_ready = false;  // the pool owns the batch: mp_hip_decode needs a new mp_hip_begin_batch
     if (int rc = prepare_iteration(dev)) return rc;
+    return pool_stage_next(dev, r, 0);
+}
+
+static int pool_run(mp_dev *dev, PoolRun &r) {
+    std::vector<int> occ;  // utterance of each slot, -1 once handed out
+    if (int rc = pool_start(dev, r, occ)) return rc;
+    const int B = (int)occ.size();
+    if (B == 0) return MP_OK;
     const int NB = dev->NB, S = dev->max_steps;
     HIPCHK(r.h.reserve((size_t)(36 + S * 8) * 4));
     int32_t *h_nd = r.h.as<int32_t>(), *h_done = h_nd + 4, *h_nf = h_nd + 20, *h_codes = h_nd + 36;
-    // one utterance is always staged ahead while any remain
-    int cur = 0;  // the staging workspace the next install reads
-    bool staged = false;
-    auto stage_next = [&](int ws) -> int {
-        int u;
-        if (int rc = pool_claim(dev, r, &u)) return rc;
-        if (u < 0) return MP_OK;
-        if (int rc = ensure_stage(dev, r.tmax)) return rc;
-        if (int rc = pool_stage(dev, r, dev->stage[ws], u)) return rc;
-        cur = ws;
-        staged = true;
-        return MP_OK;
-    };
-    if (int rc = stage_next(0)) return rc;
     HIPCHK(r.e0.create());
     HIPCHK(r.e1.create());
     HIPCHK(hipEventRecord(r.e0, dev->stream));
@@ -1588,14 +1606,9 @@ static int pool_run(mp_dev *dev, PoolRun &r) {
             r.st.useful_slot_iters += nf;
             occ[b] = -1;
             --live;
-            if (!staged) continue;
-            StageWs &s = dev->stage[cur];
-            occ[b] = s.utt;
+            if (!r.staged) continue;
             ++live;
-            ++r.st.refills;
-            staged = false;
-            if (int rc = pool_install(dev, r, s, b)) return rc;
-            if (int rc = stage_next(cur ^ 1)) return rc;
+            if (int rc = pool_refill(dev, r, occ, b)) return rc;
         }
     }
     HIPCHK(hipEventRecord(r.e1, dev->stream));
@@ -1610,12 +1623,11 @@ static int pool_run(mp_dev *dev, PoolRun &r) {
     return MP_OK;
 }
 
-int mp_hip_decode_queue(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int N,
-                        int tmax, int slots, int poll, const mp_params *params, mp_next_cb next, mp_done_cb done,
-                        void *user, mp_queue_stats *stats) {
-    if (!dev) return MP_ERR_ARG;
-    if (stats) *stats = mp_queue_stats{};
-    if (!dev->loaded) return fail(dev, MP_ERR_STATE, "no model loaded");
+// Both pool calls: the arguments checked before anything runs, `run` on a PoolRun, and nothing
+// of the run left in flight whatever its end (a refused call leaves the device usable)
+static int pool_call(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int N, int tmax,
+                     int slots, int poll, const mp_params *params, mp_next_cb next, mp_done_cb done, void *user,
+                     mp_queue_stats *stats, const std::function<int(PoolRun &)> &run) {
     const int bmax = mp_hip_max_batch(dev);
     if (!tokens || !n_tokens || !speaker || N < 1 || tmax < 1 || !params)
         return fail(dev, MP_ERR_ARG, "invalid arguments");
@@ -1626,15 +1638,24 @@ int mp_hip_decode_queue(mp_dev *dev, const int32_t *tokens, const int32_t *n_tok
     if (int rc = check_params(dev, params, &max_steps)) return rc;
     if (int rc = check_utterances(dev, tokens, n_tokens, speaker, N, tmax, &Tmax)) return rc;
     HIPCHK(hipSetDevice(dev->device));
-    PoolRun r{tokens, n_tokens, speaker, N, tmax, slots, poll > 0 ? poll : 8, *params, next, done, user};  // released on return
+    PoolRun r{tokens, n_tokens, speaker, N, tmax, slots, poll, *params, next, done, user};  // released on return
     r.claimed.assign(N, 0);
-    const int rc = pool_run(dev, r);
-    // nothing of this run stays in flight, whatever its end: a refused call leaves the device usable
+    const int rc = run(r);
     hipStreamSynchronize(dev->stream);
     if (dev->side) hipStreamSynchronize(dev->side);
     for (StageWs &s : dev->stage) { s.install_pending = false; s.utt = -1; }
     if (rc == MP_OK && stats) *stats = r.st;
     return rc;
+}
+
+int mp_hip_decode_queue(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int N,
+                        int tmax, int slots, int poll, const mp_params *params, mp_next_cb next, mp_done_cb done,
+                        void *user, mp_queue_stats *stats) {
+    if (!dev) return MP_ERR_ARG;
+    if (stats) *stats = mp_queue_stats{};
+    if (!dev->loaded) return fail(dev, MP_ERR_STATE, "no model loaded");
+    return pool_call(dev, tokens, n_tokens, speaker, N, tmax, slots, poll > 0 ? poll : 8, params, next, done, user, stats,
+                     [&](PoolRun &r) { return pool_run(dev, r); });
 }
 
 // Streaming frame loop (magpie_synthesize_sentence_streaming's loop,
@@ -1860,6 +1881,204 @@ int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_
     if (codes_out) HIPCHK(hipMemcpy(codes_out, dev->codes_out, (size_t)B * S * 8 * 4, hipMemcpyDeviceToHost));
     if (total_samples) *total_samples = samples;
     return MP_OK;
+}
+
+// ---------------------------------------------------------------- streaming slot pool
+// pool_run's loop with a round of fpc = r.poll replays between two looks at the slots, and
+// mp_hip_decode_stream's delivery: at a round end every live slot has produced one more chunk
+// (installs happen at round ends only, so a slot is a whole number of chunks in unless it
+// finished inside the round), the chunks of a round go to the codec together, slot b on lane b
+// of the device's codec stream (continuous mode: one ragged call, whatever their lengths), and
+// reach on_audio in slot order under their utterance's index. The installs and the next
+// round's replays are queued before the round's codec work, so the decode stream runs beside
+// the codec's. The frames reach the host through one of two pinned mirrors of codes_out, each
+// with its snapshot [ndone 4 | step | done | nframes], filled on the decode stream behind the
+// round's replays and ahead of the installs that zero a refilled slot's rows: a finished
+// utterance's codes are on the host before its slot is reinstalled.
+static int pool_stream_run(mp_dev *dev, PoolRun &r, mp_codec *codec, mp_audio_cb on_audio) {
+    const int fpc = r.poll;
+    std::vector<int> occ;  // utterance of each slot, -1 once it has ended
+    if (int rc = pool_start(dev, r, occ)) return rc;
+    const int B = (int)occ.size();
+    if (B == 0) return MP_OK;
+    const bool cont = dev->stream_codec_mode == MP_STREAM_CODEC_CONTINUOUS;
+    if (cont) {
+        if (!dev->cstream || dev->cstream_codec != codec || dev->cstream_lanes < B) {
+            mp_hip_codec_stream_free(dev->cstream);
+            dev->cstream = nullptr;
+            if (int rc = mp_hip_codec_stream_create(codec, B, &dev->cstream))
+                return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
+            dev->cstream_codec = codec;
+            dev->cstream_lanes = B;
+        }
+        if (int rc = mp_hip_codec_stream_reset(dev->cstream, -1))
+            return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
+    }
+    const int NB = dev->NB, S = dev->max_steps;
+    for (mp::Event &e : dev->sev) HIPCHK(e.create(hipEventDisableTiming));
+    const size_t ncodes = (size_t)NB * S * 8, nmir = ncodes + 4 + 3 * (size_t)NB;
+    HIPCHK(dev->h_codes_pin.reserve(2 * nmir * 4));
+    int32_t *const mirror = dev->h_codes_pin.as<int32_t>();
+    HIPCHK(r.e0.create());
+    HIPCHK(r.e1.create());
+    HIPCHK(hipEventRecord(r.e0, dev->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    dev->timing = mp_timing{dev->timing.preamble_ms, 0.0, 0, 0, 0.0};
+    int it = 0, live = B;
+    auto enqueue_round = [&](int k) -> int {
+        for (int i = 0; i < fpc; ++i)
+            if (int rc = launch_iteration(dev)) return rc;
+        it += fpc;
+        int32_t *h = mirror + (size_t)k * nmir;
+        HIPCHK(hipMemcpyAsync(h, dev->codes_out, ncodes * 4, hipMemcpyDeviceToHost, dev->stream));
+        HIPCHK(hipMemcpyAsync(h + ncodes, dev->ndone, 16, hipMemcpyDeviceToHost, dev->stream));
+        HIPCHK(hipMemcpyAsync(h + ncodes + 4, dev->step, NB * 4, hipMemcpyDeviceToHost, dev->stream));
+        HIPCHK(hipMemcpyAsync(h + ncodes + 4 + NB, dev->done, NB * 4, hipMemcpyDeviceToHost, dev->stream));
+        HIPCHK(hipMemcpyAsync(h + ncodes + 4 + 2 * NB, dev->nframes, NB * 4, hipMemcpyDeviceToHost, dev->stream));
+        HIPCHK(hipEventRecord(dev->sev[k], dev->stream));
+        return MP_OK;
+    };
+    // a slot's entry of a round: a chunk of n frames from frame f0 (n = 0: none), then its end
+    struct Job { int b, utt, f0, n; bool fin; size_t at; };
+    std::vector<Job> jobs;
+    std::vector<int> delivered(B, 0), stopped(B, 0);
+    std::vector<int32_t> cbm, ids, lens;
+    std::vector<float> audio;
+    bool first = true;
+    // every utterance leaves its slot within max_steps iterations and two rounds
+    const long long it_max = ((long long)r.N + 1) * ((long long)S + 2 * fpc);
+    int k = 0;
+    if (int rc = enqueue_round(0)) return rc;
+    for (;;) {
+        if (it > it_max) return fail(dev, MP_ERR_STATE, "slot pool: a slot never finished");
+        HIPCHK(hipEventSynchronize(dev->sev[k]));
+        const int32_t *h_codes = mirror + (size_t)k * nmir, *h_nd = h_codes + ncodes, *h_step = h_nd + 4,
+                      *h_done = h_step + NB, *h_nf = h_done + NB;
+        if (int rc = handoff_bits(dev, h_nd[2])) return rc;  // before any frame is delivered
+        jobs.clear();
+        int mx = 0;
+        for (int b = 0; b < B; ++b) {
+            if (occ[b] < 0) continue;
+            const bool fin = h_done[b] != 0 || stopped[b];
+            // a stopped utterance's frames of the round that was already queued are not delivered
+            const int n = stopped[b] ? 0 : (h_done[b] ? h_nf[b] : h_step[b]) - delivered[b];
+            if (n < 0 || n > fpc) return fail(dev, MP_ERR_STATE, "slot pool: a slot is not a whole number of chunks in");
+            if (n > 0 || fin) jobs.push_back({b, occ[b], delivered[b], n, fin, 0});
+            mx = std::max(mx, n);
+        }
+        // finished slots take the staged utterances, then the next round is queued
+        for (const Job &j : jobs) {
+            if (!j.fin) continue;
+            occ[j.b] = -1;
+            delivered[j.b] = stopped[j.b] = 0;
+            --live;
+            if (!r.staged) continue;
+            ++live;
+            if (int rc = pool_refill(dev, r, occ, j.b)) return rc;
+        }
+        const bool more = live > 0;
+        if (more)
+            if (int rc = enqueue_round(k ^ 1)) return rc;
+        // the round's chunks through the codec, beside the decode of the next round
+        auto fill = [&](const Job &j, int32_t *dst, int stride) {  // frame-major -> codebook-major
+            const int32_t *fm = h_codes + ((size_t)j.b * S + j.f0) * 8;
+            for (int t = 0; t < j.n; ++t)
+                for (int c = 0; c < 8; ++c) dst[(size_t)c * stride + t] = fm[(size_t)t * 8 + c];
+        };
+        auto codec_fail = [&](int rc) { return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec)); };
+        if (cont) {
+            // one ragged call: every chunk laid out for the longest of the round
+            ids.clear();
+            lens.clear();
+            for (Job &j : jobs)
+                if (j.n > 0) {
+                    j.at = ids.size() * (size_t)mx * 1024;
+                    ids.push_back(j.b);
+                    lens.push_back(j.n);
+                }
+            if (!ids.empty()) {
+                cbm.assign(ids.size() * 8 * mx, 0);
+                audio.resize(ids.size() * (size_t)mx * 1024);
+                size_t q = 0;
+                for (const Job &j : jobs)
+                    if (j.n > 0) fill(j, cbm.data() + q++ * 8 * mx, mx);
+                if (int rc = mp_hip_codec_stream_decode_ragged(dev->cstream, ids.data(), (int)ids.size(), cbm.data(),
+                                                               lens.data(), mx, audio.data()))
+                    return codec_fail(rc);
+            }
+            for (const Job &j : jobs)  // a finished slot's lane starts over
+                if (j.fin)
+                    if (int rc = mp_hip_codec_stream_reset(dev->cstream, j.b)) return codec_fail(rc);
+        } else {
+            // the reference's per-chunk semantics: full chunks together, a shorter one on its own
+            size_t nfull = 0, nsamp = 0;
+            for (Job &j : jobs)
+                if (j.n == fpc) j.at = nfull++ * (size_t)fpc * 1024;
+            nsamp = nfull * (size_t)fpc * 1024;
+            for (Job &j : jobs)
+                if (j.n > 0 && j.n != fpc) { j.at = nsamp; nsamp += (size_t)j.n * 1024; }
+            audio.resize(nsamp);
+            cbm.assign(std::max<size_t>(nfull, 1) * 8 * fpc, 0);
+            size_t q = 0;
+            for (const Job &j : jobs)
+                if (j.n == fpc) fill(j, cbm.data() + q++ * 8 * fpc, fpc);
+            if (nfull)
+                if (int rc = mp_hip_codec_decode_chunks(codec, cbm.data(), (int)nfull, fpc, audio.data())) return codec_fail(rc);
+            for (const Job &j : jobs)
+                if (j.n > 0 && j.n != fpc) {
+                    fill(j, cbm.data(), j.n);
+                    if (int rc = mp_hip_codec_decode(codec, cbm.data(), j.n, audio.data() + j.at)) return codec_fail(rc);
+                }
+        }
+        // delivery, slot by slot
+        for (const Job &j : jobs) {
+            if (j.n > 0) {
+                if (first) {
+                    dev->timing.first_audio_ms = ms_since(t0);
+                    first = false;
+                }
+                if (!j.fin) delivered[j.b] = j.f0 + j.n;
+                if (!on_audio(j.utt, audio.data() + j.at, j.n * 1024, r.user) && !j.fin) {
+                    // the callback asked to stop: the utterance ends here, its slot is refilled at the next round end
+                    stopped[j.b] = 1;
+                    static const int one = 1;
+                    HIPCHK(hipMemcpyAsync(dev->done + j.b, &one, 4, hipMemcpyHostToDevice, dev->stream));
+                    HIPCHK(hipStreamSynchronize(dev->stream));
+                }
+            }
+            if (j.fin) {
+                on_audio(j.utt, nullptr, 0, r.user);  // end-of-utterance notice
+                if (r.done) r.done(j.utt, h_codes + (size_t)j.b * S * 8, j.f0 + j.n, r.user);
+                r.st.useful_slot_iters += j.f0 + j.n;
+            }
+        }
+        if (!more) break;
+        k ^= 1;
+    }
+    HIPCHK(hipEventRecord(r.e1, dev->stream));
+    HIPCHK(hipEventSynchronize(r.e1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, r.e0, r.e1));
+    r.st.iterations = it;
+    r.st.decode_ms = ms;
+    dev->timing.decode_ms = ms;
+    dev->timing.frames_total = (int)r.st.useful_slot_iters;
+    dev->timing.iterations = it;
+    return MP_OK;
+}
+
+int mp_hip_decode_queue_stream(mp_dev *dev, mp_codec *codec, const int32_t *tokens, const int32_t *n_tokens,
+                               const int32_t *speaker, int N, int tmax, int slots, int frames_per_chunk,
+                               const mp_params *params, mp_next_cb next, mp_audio_cb on_audio, mp_done_cb done,
+                               void *user, mp_queue_stats *stats) {
+    if (!dev) return MP_ERR_ARG;
+    if (stats) *stats = mp_queue_stats{};
+    if (!dev->loaded) return fail(dev, MP_ERR_STATE, "no model loaded");
+    if (!codec) return fail(dev, MP_ERR_ARG, "codec is required");
+    if (!on_audio) return fail(dev, MP_ERR_ARG, "on_audio is required");
+    const int fpc = frames_per_chunk > 0 ? frames_per_chunk : 4;  // default 4 (magpie.h:621)
+    return pool_call(dev, tokens, n_tokens, speaker, N, tmax, slots, fpc, params, next, done, user, stats,
+                     [&](PoolRun &r) { return pool_stream_run(dev, r, codec, on_audio); });
 }
 
 int mp_hip_lt_sample(mp_dev *dev, const float *hidden, float temperature, int top_k, int forbid_eos, uint64_t seed,

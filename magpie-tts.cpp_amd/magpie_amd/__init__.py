@@ -84,6 +84,8 @@ SYMBOLS = [
     ("mp_hip_decode", _I, [_P, _P, _P]),
     ("mp_hip_decode_queue", _I, [_P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(mp_params), NEXT_CB, DONE_CB, _P,
                                  ctypes.POINTER(mp_queue_stats)]),
+    ("mp_hip_decode_queue_stream", _I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(mp_params), NEXT_CB, AUDIO_CB,
+                                        DONE_CB, _P, ctypes.POINTER(mp_queue_stats)]),
     ("mp_hip_get_trace", _I, [_P, _P]),
     ("mp_hip_debug_buffer", ctypes.c_int64, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
     ("mp_hip_encode_text", _I, [_P, _P, _I, _P]),
@@ -110,6 +112,7 @@ SYMBOLS = [
     ("mp_hip_codec_error", ctypes.c_char_p, [_P]),
     ("mp_hip_codec_stream_create", _I, [_P, _I, ctypes.POINTER(_P)]),
     ("mp_hip_codec_stream_decode", _I, [_P, _P, _I, _P, _I, _P]),
+    ("mp_hip_codec_stream_decode_ragged", _I, [_P, _P, _I, _P, _P, _I, _P]),
     ("mp_hip_codec_stream_reset", _I, [_P, _I]),
     ("mp_hip_codec_stream_free", None, [_P]),
     ("mp_hip_set_stream_codec_mode", _I, [_P, _I]),
@@ -117,7 +120,8 @@ SYMBOLS = [
 
 # entry points added after round 4: absent from the A/B baseline libraries
 OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue", "mp_hip_codec_stream_create", "mp_hip_codec_stream_decode",
-            "mp_hip_codec_stream_reset", "mp_hip_codec_stream_free", "mp_hip_set_stream_codec_mode"}
+            "mp_hip_codec_stream_reset", "mp_hip_codec_stream_free", "mp_hip_set_stream_codec_mode",
+            "mp_hip_codec_stream_decode_ragged", "mp_hip_decode_queue_stream"}
 
 _lib = None
 
@@ -215,6 +219,7 @@ class QueueResult:
     refills: int
     useful_slot_iters: int             # frames produced
     decode_ms: float
+    first_audio_ms: Optional[float] = None  # stream_queue: the loop's start to the first on_audio
 
     @property
     def utilisation(self) -> float:
@@ -359,6 +364,74 @@ class Device:
             raise raised[0]
         self._check(rc)
         return QueueResult(codes, nf, st.iterations, st.slots, st.refills, int(st.useful_slot_iters), st.decode_ms)
+
+    def stream_queue(self, codec: "Codec", tokens: Sequence[Sequence[int]], on_audio,
+                     speakers: Optional[Sequence[int]] = None, slots: int = 8, frames_per_chunk: int = 4,
+                     continuous: bool = False, next=None, max_dec_steps: int = 500, temperature: float = 0.0,
+                     top_k: int = 80, ignore_eos: bool = False, seed: int = 0, stream_base: int = 0,
+                     emit_eos_frame: bool = False, trace: bool = False) -> QueueResult:
+        """mp_hip_decode_queue_stream (the streaming slot pool): synthesize_queue's utterances
+        through `slots` refilled slots, each utterance's audio handed out chunk by chunk:
+        on_audio(utt, samples) -> bool per chunk of up to frames_per_chunk frames (False stops
+        that utterance), then on_audio(utt, None) once when the utterance has ended.
+        continuous: an utterance's chunks on a lane of a stateful codec stream, so its
+        concatenated audio is Codec.decode of its frames (default: stateless chunks). Returns
+        synthesize_queue's result plus first_audio_ms."""
+        n = len(tokens)
+        tmax = max((len(t) for t in tokens), default=1)
+        tok = np.zeros((max(n, 1), max(tmax, 1)), np.int32)
+        for b, t in enumerate(tokens):
+            tok[b, :len(t)] = np.asarray(t, np.int32)
+        nt = np.array([len(t) for t in tokens], np.int32)
+        spk = np.zeros(n, np.int32) if speakers is None else np.asarray(speakers, np.int32)
+        if len(spk) != n:
+            raise ValueError("speakers must match tokens")
+        p = mp_params(temperature, top_k, max_dec_steps, int(ignore_eos), seed, int(trace), int(stream_base),
+                      int(emit_eos_frame))
+        codes: List[Optional[np.ndarray]] = [None] * n
+        nf = np.full(n, -1, np.int32)
+        raised = []
+
+        def _next(_user):
+            try:
+                u = next()
+                return -1 if u is None else int(u)
+            except BaseException as e:  # an exception cannot cross the C frames: end the queue, re-raise after
+                raised.append(e)
+                return -1
+
+        def _audio(utt, ptr, ns, _user):
+            if raised:
+                return 0
+            try:
+                if ns == 0:  # end-of-utterance notice
+                    on_audio(utt, None)
+                    return 1
+                return 1 if on_audio(utt, np.ctypeslib.as_array(ptr, shape=(ns,)).copy()) is not False else 0
+            except BaseException as e:  # ... stop every utterance at its next chunk, re-raise after
+                raised.append(e)
+                return 0
+
+        def _done(utt, ptr, n_frames, _user):
+            codes[utt] = (np.ctypeslib.as_array(ptr, shape=(n_frames, 8)).copy() if n_frames > 0
+                          else np.zeros((0, 8), np.int32))
+            nf[utt] = n_frames
+
+        self._check(self.lib.mp_hip_set_stream_codec_mode(self.h, 1 if continuous else 0))
+        ncb = NEXT_CB(_next) if next is not None else ctypes.cast(None, NEXT_CB)
+        acb = AUDIO_CB(_audio) if on_audio is not None else ctypes.cast(None, AUDIO_CB)
+        dcb = DONE_CB(_done)
+        st = mp_queue_stats()
+        rc = self.lib.mp_hip_decode_queue_stream(self.h, codec.h if codec is not None else None, tok.ctypes.data,
+                                                 nt.ctypes.data, spk.ctypes.data, n, tmax, slots, frames_per_chunk,
+                                                 ctypes.byref(p), ncb, acb, dcb, None, ctypes.byref(st))
+        if raised:
+            raise raised[0]
+        self._check(rc)
+        tm = mp_timing()
+        self._check(self.lib.mp_hip_get_timing(self.h, ctypes.byref(tm)))
+        return QueueResult(codes, nf, st.iterations, st.slots, st.refills, int(st.useful_slot_iters), st.decode_ms,
+                           tm.first_audio_ms)
 
     def synthesize_stream(self, codec: "Codec", tokens: Sequence[Sequence[int]], on_audio,
                           speakers: Optional[Sequence[int]] = None, max_dec_steps: int = 500,
@@ -618,6 +691,31 @@ class CodecStream:
         out = np.zeros((n, F * 1024), np.float32)
         self._check(self.lib.mp_hip_codec_stream_decode(self.h, ids.ctypes.data, n, codes.ctypes.data, F, out.ctypes.data))
         return out[0] if single else out
+
+    def decode_ragged(self, codes, n_frames: Sequence[int], lanes: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+        """The next chunk of each given lane, lane q's n_frames[q] frames long, in one launch
+        sequence (mp_hip_codec_stream_decode_ragged). codes: [n][8][max_frames], row q holding
+        n_frames[q] frames (the rest ignored), or a sequence of n arrays [8][>= n_frames[q]]
+        (laid out for the longest). Returns n arrays of n_frames[q] * 1024 samples."""
+        if not hasattr(self.lib, "mp_hip_codec_stream_decode_ragged"):
+            raise MagpieError("this libmagpie_hip.so has no ragged stream decode")
+        if not (isinstance(codes, np.ndarray) and codes.ndim == 3):
+            rows = [np.asarray(c, np.int32) for c in codes]
+            F = max([r.shape[1] for r in rows] + [1])
+            codes = np.zeros((len(rows), 8, F), np.int32)
+            for q, r in enumerate(rows):
+                assert r.ndim == 2 and r.shape[0] == 8
+                codes[q, :, :r.shape[1]] = r
+        codes = np.ascontiguousarray(codes, np.int32)
+        n, eight, F = codes.shape
+        assert eight == 8
+        nf = np.ascontiguousarray(n_frames, np.int32)
+        ids = np.ascontiguousarray(np.arange(n) if lanes is None else lanes, np.int32)
+        assert ids.shape == (n,) and nf.shape == (n,)
+        out = np.zeros((n, F * 1024), np.float32)
+        self._check(self.lib.mp_hip_codec_stream_decode_ragged(self.h, ids.ctypes.data, n, codes.ctypes.data,
+                                                               nf.ctypes.data, F, out.ctypes.data))
+        return [out[q, :int(nf[q]) * 1024].copy() for q in range(n)]
 
     def reset(self, lane: int = -1) -> None:
         """Back to the start of an utterance on `lane` (-1: every lane)."""

@@ -193,6 +193,46 @@ def simulate_pool(frames: Sequence[int], slots: int, poll: int, max_dec_steps: i
     return it, sum(frames)
 
 
+def simulate_pool_stream(frames: Sequence[int], slots: int, fpc: int, max_dec_steps: int, emit_eos: bool = False):
+    """The streaming slot pool's schedule (mp_hip_decode_queue_stream) restated on the host:
+    simulate_pool's loop with a round of `fpc` iterations, plus what each round end delivers.
+    Returns (iterations, rounds): rounds[k] is round k's ordered events, slot by slot,
+    (utt, n) for a chunk of n frames (1..fpc) and (utt, 0) for an utterance's end notice,
+    which follows its last chunk. An utterance installed at a round end starts with the next
+    round, so its chunks are fpc, ..., fpc, remainder; the iteration count is
+    simulate_pool(frames, slots, fpc, max_dec_steps, emit_eos)[0]."""
+    if slots < 1 or fpc < 1 or max_dec_steps < 1:
+        raise ValueError("slots, fpc and max_dec_steps must be >= 1")
+    frames = list(frames)
+    if any(f < 0 or f > max_dec_steps for f in frames):
+        raise ValueError("frame counts must be in 0..max_dec_steps")
+    busy = [f if (emit_eos or f >= max_dec_steps) else f + 1 for f in frames]
+    nxt = min(slots, len(frames))
+    occ: List[Optional[int]] = list(range(nxt))  # utterance of each slot (None: empty)
+    start = [0] * nxt                            # iteration after which it was installed
+    sent = [0] * nxt                             # frames of it delivered
+    it, rounds = 0, []
+    while any(u is not None for u in occ):
+        it += fpc
+        events = []
+        for b, u in enumerate(occ):
+            if u is None:
+                continue
+            n = min(frames[u], it - start[b]) - sent[b]
+            if n > 0:
+                events.append((u, n))
+                sent[b] += n
+            if start[b] + busy[u] > it:
+                continue
+            events.append((u, 0))
+            occ[b] = None
+            if nxt < len(frames):
+                occ[b], start[b], sent[b] = nxt, it, 0
+                nxt += 1
+        rounds.append(events)
+    return it, rounds
+
+
 def gather_results(mine: Dict[int, object], n_total: int) -> List[object]:
     """Every rank's {index: result} merged into one list in utterance order (gloo
     all_gather_object on the host; world size 1: the dict itself)."""
