@@ -151,7 +151,7 @@ struct mp_dev {
     unsigned short *h_b16 = nullptr;  // bf16 mode: GELU(FFN up) as the bf16 FFN-down operand [NB][3072]
     float *gpart = nullptr;            // preamble split-K partial sums (mp::gemm_splits)
     mp::Event sev[2];           // streaming: the two chunk snapshots landed
-    mp::Pinned h_codes_pin;     // streaming: pinned host mirror of codes_out [NB][S][8] + snapshots
+    mp::Pinned h_codes_pin;     // streaming: pinned mirrors of codes_out and the snapshots (StreamRun's layout)
     float *sa_part = nullptr, *xa_part = nullptr;  // split-K attention states [NB][12][4][68], [NB][4][772]
     unsigned long long *sagh = nullptr, *xagh = nullptr;  // 16-slot merges: split-state granules
     unsigned long long *kgh = nullptr;  // split-K FFN-down partial tiles (16-bit modes): [48][KS][256]
@@ -1351,6 +1351,19 @@ static int check_handoff(mp_dev *dev) {
     return handoff_bits(dev, nd[2]);
 }
 
+// The end of an event-timed loop: e1 recorded behind it and waited for, the device time
+// e0 -> e1 and the counts into dev->timing
+static int end_timing(mp_dev *dev, hipEvent_t e0, hipEvent_t e1, int iterations, int frames) {
+    HIPCHK(hipEventRecord(e1, dev->stream));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    dev->timing.decode_ms = ms;
+    dev->timing.frames_total = frames;
+    dev->timing.iterations = iterations;
+    return MP_OK;
+}
+
 int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames) {
     if (!dev) return MP_ERR_ARG;
     if (!dev->batch_ready) return fail(dev, MP_ERR_STATE, "mp_hip_begin_batch must precede mp_hip_decode");
@@ -1374,10 +1387,7 @@ int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames) {
             if (*dev->h_ndone.as<int>() >= NB) break;
         }
     }
-    HIPCHK(hipEventRecord(e1, dev->stream));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    if (int rc = end_timing(dev, e0, e1, it, 0)) return rc;  // (the frames: below, once they are read)
     if (int rc = check_handoff(dev)) return rc;
     std::vector<int> h_nf(NB);
     HIPCHK(hipMemcpy(h_nf.data(), dev->nframes, NB * 4, hipMemcpyDeviceToHost));
@@ -1389,9 +1399,7 @@ int mp_hip_decode(mp_dev *dev, int32_t *codes_out, int32_t *n_frames) {
         total += h_nf[b];
     }
     if (codes_out) memcpy(codes_out, h_codes.data(), (size_t)B * dev->max_steps * 8 * 4);
-    dev->timing.decode_ms = ms;
     dev->timing.frames_total = total;
-    dev->timing.iterations = it;
     return MP_OK;
 }
 
@@ -1611,15 +1619,9 @@ static int pool_run(mp_dev *dev, PoolRun &r) {
             if (int rc = pool_refill(dev, r, occ, b)) return rc;
         }
     }
-    HIPCHK(hipEventRecord(r.e1, dev->stream));
-    HIPCHK(hipEventSynchronize(r.e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, r.e0, r.e1));
+    if (int rc = end_timing(dev, r.e0, r.e1, it, (int)r.st.useful_slot_iters)) return rc;
     r.st.iterations = it;
-    r.st.decode_ms = ms;
-    dev->timing.decode_ms = ms;
-    dev->timing.frames_total = (int)r.st.useful_slot_iters;
-    dev->timing.iterations = it;
+    r.st.decode_ms = dev->timing.decode_ms;
     return MP_OK;
 }
 
@@ -1658,14 +1660,16 @@ int mp_hip_decode_queue(mp_dev *dev, const int32_t *tokens, const int32_t *n_tok
                      [&](PoolRun &r) { return pool_run(dev, r); });
 }
 
-// Streaming frame loop (magpie_synthesize_sentence_streaming's loop,
-// magpie.cpp:4762-4838) for every utterance of the batch: after each
-// frames_per_chunk iterations the new frames of every utterance are decoded by
-// the codec in chunks of frames_per_chunk (the last chunk of an utterance may
-// be shorter: EOS or max_dec_steps) and handed to `on_audio` in order.
-// Every full chunk of a round goes through the codec in one launch sequence
-// (chunks are independent, magpie.cpp:4739-4742: the audio is the same); the
-// frames reach the host through a pinned mirror filled on the decode stream.
+// ---------------------------------------------------------------- streaming
+// Both streaming drivers (mp_hip_decode_stream: one batch; pool_stream_run: the slot pool) run
+// rounds of up to frames_per_chunk graph replays. Behind a round's replays, on the decode
+// stream, the codes it wrote and a snapshot [ndone 4 | step | done | nframes] go to a pinned
+// host mirror and an event is recorded: the host never waits inside a copy. When a round has
+// landed the driver queues the next one and only then sends the landed round's chunks, at
+// most one per slot, through the codec, so the decode runs on its stream while the codec runs
+// on the codec's (bit-exact beside it: tests/test_concurrency_gpu.py). Slot b decodes on lane
+// b of the device's codec stream. A stop requested by a callback takes effect after the round
+// already queued, whose frames of that utterance are then not delivered.
 // MAGPIE_STREAM_ASYNC=0: queue each chunk from the calling thread (default 1: a helper thread)
 static bool stream_async() { return mp::env_int("MAGPIE_STREAM_ASYNC", 1) != 0; }
 // MAGPIE_STREAM_TRACE=1: host-side timeline of the streaming loop on stderr (diagnostics)
@@ -1675,319 +1679,96 @@ static bool stream_trace() { return mp::env_int("MAGPIE_STREAM_TRACE", 0) != 0; 
 // chunks, whose first chunk is the time to first audio) queue it from the calling thread
 constexpr int STREAM_ASYNC_MIN_FRAMES = 256;
 
-int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_audio_cb on_audio, void *user,
-                         int32_t *codes_out, int32_t *n_frames, int64_t *total_samples) {
-    if (!dev) return MP_ERR_ARG;
-    if (!dev->batch_ready) return fail(dev, MP_ERR_STATE, "mp_hip_begin_batch must precede mp_hip_decode_stream");
-    if (!codec) return fail(dev, MP_ERR_ARG, "codec is required");
-    const int fpc = frames_per_chunk > 0 ? frames_per_chunk : 4;  // default 4 (magpie.h:621)
-    HIPCHK(hipSetDevice(dev->device));
-    const int NB = dev->NB, B = dev->B, S = dev->max_steps;
-    // continuous codec: slot b decodes on lane b, every lane at the start of an utterance
-    const bool cont = dev->stream_codec_mode == MP_STREAM_CODEC_CONTINUOUS;
-    if (cont) {
-        if (!dev->cstream || dev->cstream_codec != codec || dev->cstream_lanes < B) {
-            mp_hip_codec_stream_free(dev->cstream);
-            dev->cstream = nullptr;
-            if (int rc = mp_hip_codec_stream_create(codec, B, &dev->cstream))
-                return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-            dev->cstream_codec = codec;
-            dev->cstream_lanes = B;
-        }
-        if (int rc = mp_hip_codec_stream_reset(dev->cstream, -1))
-            return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-    }
-    std::vector<int32_t> wave_ids, wave_codes;  // continuous: one stream decode's lanes and codes
-    std::vector<float> wave_audio;
-    std::vector<int> nth;
-    if (int rc = prepare_iteration(dev)) return rc;
-    for (mp::Event &e : dev->sev) HIPCHK(e.create(hipEventDisableTiming));
-    // pinned: a copy into pageable memory would block the host until the chunk's kernels finish
-    HIPCHK(dev->h_codes_pin.reserve(((size_t)NB * S * 8 + 6 * NB) * 4));
-    int32_t *const h_codes = dev->h_codes_pin.as<int32_t>();
-    int *const snap = h_codes + (size_t)NB * S * 8;  // two snapshots of (step, done, nframes)
-    auto t0 = std::chrono::steady_clock::now();
-    // two snapshots of (step, done, nframes): the host reads one while the next chunk's land in the other
-    std::vector<int> delivered(B, 0), stopped(B, 0), ended(B, 0);
-    std::vector<int32_t> cbm;
+namespace {
+// A slot's entry of a round: a chunk of n frames from frame f0 (n = 0: none) of utterance
+// utt, in slot and on codec lane b; ended: the utterance ends with it. at: where decode()
+// put the chunk's samples in StreamRun::audio.
+struct Job { int b, utt, f0, n; bool ended; size_t at; };
+// a landed round: the codes mirror [NB][S][8] and the snapshot, as enqueue() filled them
+struct Snap { const int32_t *codes, *nd, *step, *done, *nf; };
+
+struct StreamRun {
+    mp_dev *dev;
+    mp_codec *codec;
+    int fpc;
+    mp_audio_cb on_audio;
+    void *user;
+    bool cont = false;  // continuous codec: the lanes carry their state from chunk to chunk
+    // the pinned mirror: [codes NB x S x 8] x mirrors, then two snapshots of 4 + 3 NB
+    int NB = 0, S = 0, mirrors = 1;
+    std::vector<int> delivered, stopped;  // per slot: frames handed out; the callback declined
+    std::vector<int32_t> cbm, ids, lens;  // codec staging: codebook-major codes, lanes, lengths
     std::vector<float> audio;
-    int64_t samples = 0;
-    int it = 0;
-    bool first = true;
-    dev->timing = mp_timing{dev->timing.preamble_ms, 0.0, 0, 0, 0.0};
-    auto enqueue_chunk = [&](int slot) -> int {
+    bool first = true;  // no audio delivered yet
+    std::chrono::steady_clock::time_point t0;
+
+    int codec_fail(int rc) { return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec)); }
+    size_t ncodes() const { return (size_t)NB * S * 8; }
+    int32_t *codes(int k) const { return dev->h_codes_pin.as<int32_t>() + (size_t)(k % mirrors) * ncodes(); }
+    int32_t *snap(int k) const { return dev->h_codes_pin.as<int32_t>() + mirrors * ncodes() + (size_t)k * (4 + 3 * NB); }
+    Snap view(int k) const {
+        const int32_t *s = snap(k);
+        return {codes(k), s, s + 4, s + 4 + NB, s + 4 + 2 * NB};
+    }
+
+    // B slots of the prepared batch: codec lanes at the start of an utterance, the events and
+    // the mirror (one codes mirror, or one per snapshot), the timing reset, the clock started
+    int open(int B, int codes_mirrors) {
+        NB = dev->NB; S = dev->max_steps; mirrors = codes_mirrors;
+        cont = dev->stream_codec_mode == MP_STREAM_CODEC_CONTINUOUS;
+        if (cont) {
+            if (!dev->cstream || dev->cstream_codec != codec || dev->cstream_lanes < B) {
+                mp_hip_codec_stream_free(dev->cstream);
+                dev->cstream = nullptr;
+                if (int rc = mp_hip_codec_stream_create(codec, B, &dev->cstream)) return codec_fail(rc);
+                dev->cstream_codec = codec;
+                dev->cstream_lanes = B;
+            }
+            if (int rc = mp_hip_codec_stream_reset(dev->cstream, -1)) return codec_fail(rc);
+        }
+        for (mp::Event &e : dev->sev) HIPCHK(e.create(hipEventDisableTiming));
+        // pinned: a copy into pageable memory would block the host until the round's kernels finish
+        HIPCHK(dev->h_codes_pin.reserve((mirrors * ncodes() + 2 * (4 + 3 * (size_t)NB)) * 4));
+        delivered.assign(B, 0);
+        stopped.assign(B, 0);
+        dev->timing = mp_timing{dev->timing.preamble_ms, 0.0, 0, 0, 0.0};
+        t0 = std::chrono::steady_clock::now();
+        return MP_OK;
+    }
+
+    // A round on the decode stream: n_it replays, then frames f0 .. f0+nf of every slot (nf = S:
+    // the whole buffer in one piece) and the snapshot into mirror k, then sev[k]. Touches nothing
+    // of this struct: it may run on a helper thread while the caller decodes and delivers.
+    int enqueue(int k, int n_it, int f0, int nf) const {
         const hipStream_t st = dev->stream;
-        const int n_it = std::min(fpc, S - it);
         for (int i = 0; i < n_it; ++i)
             if (int rc = launch_iteration(dev, st)) return rc;
-        // the frames these iterations wrote (columns it..it+n_it of every slot) to the
-        // pinned mirror, on the decode stream: no host copy waits on the GPU later
-        HIPCHK(hipMemcpy2DAsync(h_codes + (size_t)it * 8, (size_t)S * 32, dev->codes_out + (size_t)it * 8,
-                                (size_t)S * 32, (size_t)n_it * 32, NB, hipMemcpyDeviceToHost, st));
-        it += n_it;
-        int *h = snap + (size_t)slot * 3 * NB;
-        HIPCHK(hipMemcpyAsync(h, dev->step, NB * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h + NB, dev->done, NB * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(h + 2 * NB, dev->nframes, NB * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(dev->sev[slot], st));
+        if (nf == S)
+            HIPCHK(hipMemcpyAsync(codes(k), dev->codes_out, ncodes() * 4, hipMemcpyDeviceToHost, st));
+        else
+            HIPCHK(hipMemcpy2DAsync(codes(k) + (size_t)f0 * 8, (size_t)S * 32, dev->codes_out + (size_t)f0 * 8,
+                                    (size_t)S * 32, (size_t)nf * 32, NB, hipMemcpyDeviceToHost, st));
+        int32_t *h = snap(k);
+        HIPCHK(hipMemcpyAsync(h, dev->ndone, 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h + 4, dev->step, NB * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h + 4 + NB, dev->done, NB * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h + 4 + 2 * NB, dev->nframes, NB * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(dev->sev[k], st));
         return MP_OK;
-    };
-    struct Job { int b, f0, n; };
-    std::vector<Job> jobs;
-    int slot = 0;
-    if (int rc = enqueue_chunk(0)) return rc;
-    for (;;) {
-        HIPCHK(hipEventSynchronize(dev->sev[slot]));
-        const int *h_step = snap + (size_t)slot * 3 * NB, *h_done = h_step + NB, *h_nf = h_step + 2 * NB;
-        bool more = false;
-        for (int b = 0; b < B; ++b) more |= !(h_done[b] != 0 || stopped[b]);
-        more &= it < S;
-        // the next chunk's iterations are queued before this round's codec work, so
-        // the decode runs on its stream while the codec runs on the codec's (bit-exact
-        // beside it: tests/test_concurrency_gpu.py); a stop requested by a callback
-        // below takes effect after that chunk, whose frames are then not delivered.
-        // Queuing a chunk's graph replays can block the host (the queue's packet slots fill
-        // up: 32 iterations of 65 launches), which left the codec waiting behind the next
-        // chunk's decode, serialising the two (configs[2]: 27.2k vs 27.5k frames/s serial,
-        // r06d): a round with codec work large enough to matter queues the chunk from a
-        // helper thread while this thread runs the codec (HIP calls are thread-safe; the
-        // helper touches only the decode stream and its pinned snapshot)
-        const double t_wait = ms_since(t0);
-        std::future<int> queued;
-        const bool async_q = more && stream_async() && B * fpc >= STREAM_ASYNC_MIN_FRAMES;  // (a thread per round)
-        if (async_q) {
-            queued = std::async(std::launch::async, [&, sl = slot ^ 1]() -> int {
-                HIPCHK(hipSetDevice(dev->device));  // the current device is per thread
-                return enqueue_chunk(sl);
-            });
-        } else if (more) {
-            if (int rc = enqueue_chunk(slot ^ 1)) return rc;
-        }
-        if (stream_trace()) fprintf(stderr, "[stream] round at %.3f ms: chunk landed, next queued %s at %.3f ms\n", t_wait,
-                                    async_q ? "(async)" : "", ms_since(t0));
-        // this round's chunks, utterance by utterance, in delivery order
-        jobs.clear();
-        for (int b = 0; b < B; ++b) {
-            if (stopped[b]) continue;
-            const bool done = h_done[b] != 0;
-            const int produced = done ? h_nf[b] : h_step[b];
-            for (int d = delivered[b]; produced - d >= (done ? 1 : fpc);) {
-                const int n = std::min(fpc, produced - d);
-                jobs.push_back({b, d, n});
-                d += n;
-            }
-        }
-        // full chunks through the codec together, a shorter final chunk on its own
-        size_t nfull = 0;
-        for (const Job &j : jobs) nfull += j.n == fpc;
-        cbm.assign(jobs.size() * 8 * fpc, 0);
-        audio.resize(jobs.size() * fpc * 1024);
-        std::vector<size_t> at(jobs.size());
-        {
-            size_t kf = 0, ks = nfull;
-            for (size_t q = 0; q < jobs.size(); ++q) at[q] = jobs[q].n == fpc ? kf++ : ks++;
-        }
-        for (size_t q = 0; q < jobs.size(); ++q) {
-            const Job &j = jobs[q];
-            const int32_t *fm = h_codes + ((size_t)j.b * S + j.f0) * 8;
-            int32_t *dst = cbm.data() + at[q] * 8 * fpc;
-            for (int t = 0; t < j.n; ++t)  // frame-major -> codebook-major (decode_frames_to_audio, 4468-4473)
-                for (int c = 0; c < 8; ++c) dst[(size_t)c * j.n + t] = fm[(size_t)t * 8 + c];
-        }
-        if (cont) {
-            // a lane's chunks go in frame order, one per call: call w takes the w-th chunk of
-            // every slot that has one, the full ones together, a shorter final one on its own
-            nth.assign(jobs.size(), 0);
-            int calls = 0;
-            for (size_t q = 0; q < jobs.size(); ++q) {
-                nth[q] = q && jobs[q - 1].b == jobs[q].b ? nth[q - 1] + 1 : 0;
-                calls = std::max(calls, nth[q] + 1);
-            }
-            for (int w = 0; w < calls; ++w) {
-                wave_ids.clear();
-                wave_codes.clear();
-                for (size_t q = 0; q < jobs.size(); ++q)
-                    if (nth[q] == w && jobs[q].n == fpc) {
-                        wave_ids.push_back(jobs[q].b);
-                        wave_codes.insert(wave_codes.end(), cbm.begin() + at[q] * 8 * fpc, cbm.begin() + (at[q] + 1) * 8 * fpc);
-                    }
-                if (!wave_ids.empty()) {
-                    wave_audio.resize(wave_ids.size() * fpc * 1024);
-                    if (int rc = mp_hip_codec_stream_decode(dev->cstream, wave_ids.data(), (int)wave_ids.size(),
-                                                            wave_codes.data(), fpc, wave_audio.data()))
-                        return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-                    size_t k = 0;
-                    for (size_t q = 0; q < jobs.size(); ++q)
-                        if (nth[q] == w && jobs[q].n == fpc)
-                            memcpy(audio.data() + at[q] * fpc * 1024, wave_audio.data() + k++ * fpc * 1024, (size_t)fpc * 4096);
-                }
-                for (size_t q = 0; q < jobs.size(); ++q)
-                    if (nth[q] == w && jobs[q].n != fpc) {
-                        const int32_t lane = jobs[q].b;
-                        if (int rc = mp_hip_codec_stream_decode(dev->cstream, &lane, 1, cbm.data() + at[q] * 8 * fpc, jobs[q].n,
-                                                                audio.data() + at[q] * fpc * 1024))
-                            return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-                    }
-            }
-        } else {
-            if (nfull)
-                if (int rc = mp_hip_codec_decode_chunks(codec, cbm.data(), (int)nfull, fpc, audio.data()))
-                    return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-            for (size_t q = 0; q < jobs.size(); ++q)
-                if (jobs[q].n != fpc)
-                    if (int rc = mp_hip_codec_decode(codec, cbm.data() + at[q] * 8 * fpc, jobs[q].n,
-                                                     audio.data() + at[q] * fpc * 1024))
-                        return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-        }
-        if (stream_trace()) fprintf(stderr, "[stream]   codec of %zu chunks done at %.3f ms\n", jobs.size(), ms_since(t0));
-        if (queued.valid())
-            if (int rc = queued.get()) return rc;
-        for (size_t q = 0, b = 0; b < (size_t)B; ++b) {
-            for (; q < jobs.size() && jobs[q].b == (int)b; ++q) {
-                const Job &j = jobs[q];
-                if (stopped[b]) continue;  // a callback of this round stopped the utterance
-                delivered[b] += j.n;
-                samples += (int64_t)j.n * 1024;
-                if (first) {
-                    dev->timing.first_audio_ms = ms_since(t0);
-                    first = false;
-                }
-                if (on_audio && !on_audio((int)b, audio.data() + at[q] * fpc * 1024, j.n * 1024, user)) {
-                    // the callback asked to stop (4820-4824): the utterance ends here
-                    stopped[b] = 1;
-                    const int one = 1;
-                    HIPCHK(hipMemcpyAsync(dev->done + b, &one, 4, hipMemcpyHostToDevice, dev->stream));
-                    HIPCHK(hipStreamSynchronize(dev->stream));
-                }
-            }
-            if ((h_done[b] != 0 || stopped[b]) && !ended[b]) {  // end-of-utterance notice: (utt, NULL, 0)
-                ended[b] = 1;
-                if (on_audio) on_audio((int)b, nullptr, 0, user);
-            }
-        }
-        if (!more) break;
-        slot ^= 1;
     }
-    HIPCHK(hipStreamSynchronize(dev->stream));
-    if (int rc = check_handoff(dev)) return rc;
-    dev->timing.decode_ms = ms_since(t0);
-    dev->timing.iterations = it;
-    int total = 0;
-    for (int b = 0; b < B; ++b) {
-        if (n_frames) n_frames[b] = delivered[b];
-        total += delivered[b];
-    }
-    dev->timing.frames_total = total;
-    if (codes_out) HIPCHK(hipMemcpy(codes_out, dev->codes_out, (size_t)B * S * 8 * 4, hipMemcpyDeviceToHost));
-    if (total_samples) *total_samples = samples;
-    return MP_OK;
-}
 
-// ---------------------------------------------------------------- streaming slot pool
-// pool_run's loop with a round of fpc = r.poll replays between two looks at the slots, and
-// mp_hip_decode_stream's delivery: at a round end every live slot has produced one more chunk
-// (installs happen at round ends only, so a slot is a whole number of chunks in unless it
-// finished inside the round), the chunks of a round go to the codec together, slot b on lane b
-// of the device's codec stream (continuous mode: one ragged call, whatever their lengths), and
-// reach on_audio in slot order under their utterance's index. The installs and the next
-// round's replays are queued before the round's codec work, so the decode stream runs beside
-// the codec's. The frames reach the host through one of two pinned mirrors of codes_out, each
-// with its snapshot [ndone 4 | step | done | nframes], filled on the decode stream behind the
-// round's replays and ahead of the installs that zero a refilled slot's rows: a finished
-// utterance's codes are on the host before its slot is reinstalled.
-static int pool_stream_run(mp_dev *dev, PoolRun &r, mp_codec *codec, mp_audio_cb on_audio) {
-    const int fpc = r.poll;
-    std::vector<int> occ;  // utterance of each slot, -1 once it has ended
-    if (int rc = pool_start(dev, r, occ)) return rc;
-    const int B = (int)occ.size();
-    if (B == 0) return MP_OK;
-    const bool cont = dev->stream_codec_mode == MP_STREAM_CODEC_CONTINUOUS;
-    if (cont) {
-        if (!dev->cstream || dev->cstream_codec != codec || dev->cstream_lanes < B) {
-            mp_hip_codec_stream_free(dev->cstream);
-            dev->cstream = nullptr;
-            if (int rc = mp_hip_codec_stream_create(codec, B, &dev->cstream))
-                return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-            dev->cstream_codec = codec;
-            dev->cstream_lanes = B;
-        }
-        if (int rc = mp_hip_codec_stream_reset(dev->cstream, -1))
-            return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec));
-    }
-    const int NB = dev->NB, S = dev->max_steps;
-    for (mp::Event &e : dev->sev) HIPCHK(e.create(hipEventDisableTiming));
-    const size_t ncodes = (size_t)NB * S * 8, nmir = ncodes + 4 + 3 * (size_t)NB;
-    HIPCHK(dev->h_codes_pin.reserve(2 * nmir * 4));
-    int32_t *const mirror = dev->h_codes_pin.as<int32_t>();
-    HIPCHK(r.e0.create());
-    HIPCHK(r.e1.create());
-    HIPCHK(hipEventRecord(r.e0, dev->stream));
-    const auto t0 = std::chrono::steady_clock::now();
-    dev->timing = mp_timing{dev->timing.preamble_ms, 0.0, 0, 0, 0.0};
-    int it = 0, live = B;
-    auto enqueue_round = [&](int k) -> int {
-        for (int i = 0; i < fpc; ++i)
-            if (int rc = launch_iteration(dev)) return rc;
-        it += fpc;
-        int32_t *h = mirror + (size_t)k * nmir;
-        HIPCHK(hipMemcpyAsync(h, dev->codes_out, ncodes * 4, hipMemcpyDeviceToHost, dev->stream));
-        HIPCHK(hipMemcpyAsync(h + ncodes, dev->ndone, 16, hipMemcpyDeviceToHost, dev->stream));
-        HIPCHK(hipMemcpyAsync(h + ncodes + 4, dev->step, NB * 4, hipMemcpyDeviceToHost, dev->stream));
-        HIPCHK(hipMemcpyAsync(h + ncodes + 4 + NB, dev->done, NB * 4, hipMemcpyDeviceToHost, dev->stream));
-        HIPCHK(hipMemcpyAsync(h + ncodes + 4 + 2 * NB, dev->nframes, NB * 4, hipMemcpyDeviceToHost, dev->stream));
-        HIPCHK(hipEventRecord(dev->sev[k], dev->stream));
-        return MP_OK;
-    };
-    // a slot's entry of a round: a chunk of n frames from frame f0 (n = 0: none), then its end
-    struct Job { int b, utt, f0, n; bool fin; size_t at; };
-    std::vector<Job> jobs;
-    std::vector<int> delivered(B, 0), stopped(B, 0);
-    std::vector<int32_t> cbm, ids, lens;
-    std::vector<float> audio;
-    bool first = true;
-    // every utterance leaves its slot within max_steps iterations and two rounds
-    const long long it_max = ((long long)r.N + 1) * ((long long)S + 2 * fpc);
-    int k = 0;
-    if (int rc = enqueue_round(0)) return rc;
-    for (;;) {
-        if (it > it_max) return fail(dev, MP_ERR_STATE, "slot pool: a slot never finished");
-        HIPCHK(hipEventSynchronize(dev->sev[k]));
-        const int32_t *h_codes = mirror + (size_t)k * nmir, *h_nd = h_codes + ncodes, *h_step = h_nd + 4,
-                      *h_done = h_step + NB, *h_nf = h_done + NB;
-        if (int rc = handoff_bits(dev, h_nd[2])) return rc;  // before any frame is delivered
-        jobs.clear();
-        int mx = 0;
-        for (int b = 0; b < B; ++b) {
-            if (occ[b] < 0) continue;
-            const bool fin = h_done[b] != 0 || stopped[b];
-            // a stopped utterance's frames of the round that was already queued are not delivered
-            const int n = stopped[b] ? 0 : (h_done[b] ? h_nf[b] : h_step[b]) - delivered[b];
-            if (n < 0 || n > fpc) return fail(dev, MP_ERR_STATE, "slot pool: a slot is not a whole number of chunks in");
-            if (n > 0 || fin) jobs.push_back({b, occ[b], delivered[b], n, fin, 0});
-            mx = std::max(mx, n);
-        }
-        // finished slots take the staged utterances, then the next round is queued
-        for (const Job &j : jobs) {
-            if (!j.fin) continue;
-            occ[j.b] = -1;
-            delivered[j.b] = stopped[j.b] = 0;
-            --live;
-            if (!r.staged) continue;
-            ++live;
-            if (int rc = pool_refill(dev, r, occ, j.b)) return rc;
-        }
-        const bool more = live > 0;
-        if (more)
-            if (int rc = enqueue_round(k ^ 1)) return rc;
-        // the round's chunks through the codec, beside the decode of the next round
-        auto fill = [&](const Job &j, int32_t *dst, int stride) {  // frame-major -> codebook-major
-            const int32_t *fm = h_codes + ((size_t)j.b * S + j.f0) * 8;
+    // The round's chunks (jobs with n > 0, at most one per lane) through the codec; sets their `at`
+    int decode(std::vector<Job> &jobs, const Snap &v) {
+        // frame-major -> codebook-major (decode_frames_to_audio, 4468-4473)
+        auto fill = [&](const Job &j, int32_t *dst, int stride) {
+            const int32_t *fm = v.codes + ((size_t)j.b * S + j.f0) * 8;
             for (int t = 0; t < j.n; ++t)
                 for (int c = 0; c < 8; ++c) dst[(size_t)c * stride + t] = fm[(size_t)t * 8 + c];
         };
-        auto codec_fail = [&](int rc) { return fail(dev, rc, std::string("codec: ") + mp_hip_codec_error(codec)); };
         if (cont) {
             // one ragged call: every chunk laid out for the longest of the round
+            int mx = 0;
+            for (const Job &j : jobs) mx = std::max(mx, j.n);
             ids.clear();
             lens.clear();
             for (Job &j : jobs)
@@ -1996,74 +1777,227 @@ static int pool_stream_run(mp_dev *dev, PoolRun &r, mp_codec *codec, mp_audio_cb
                     ids.push_back(j.b);
                     lens.push_back(j.n);
                 }
-            if (!ids.empty()) {
-                cbm.assign(ids.size() * 8 * mx, 0);
-                audio.resize(ids.size() * (size_t)mx * 1024);
-                size_t q = 0;
-                for (const Job &j : jobs)
-                    if (j.n > 0) fill(j, cbm.data() + q++ * 8 * mx, mx);
-                if (int rc = mp_hip_codec_stream_decode_ragged(dev->cstream, ids.data(), (int)ids.size(), cbm.data(),
-                                                               lens.data(), mx, audio.data()))
-                    return codec_fail(rc);
-            }
-            for (const Job &j : jobs)  // a finished slot's lane starts over
-                if (j.fin)
-                    if (int rc = mp_hip_codec_stream_reset(dev->cstream, j.b)) return codec_fail(rc);
-        } else {
-            // the reference's per-chunk semantics: full chunks together, a shorter one on its own
-            size_t nfull = 0, nsamp = 0;
-            for (Job &j : jobs)
-                if (j.n == fpc) j.at = nfull++ * (size_t)fpc * 1024;
-            nsamp = nfull * (size_t)fpc * 1024;
-            for (Job &j : jobs)
-                if (j.n > 0 && j.n != fpc) { j.at = nsamp; nsamp += (size_t)j.n * 1024; }
-            audio.resize(nsamp);
-            cbm.assign(std::max<size_t>(nfull, 1) * 8 * fpc, 0);
+            if (ids.empty()) return MP_OK;
+            cbm.assign(ids.size() * 8 * mx, 0);
+            audio.resize(ids.size() * (size_t)mx * 1024);
             size_t q = 0;
             for (const Job &j : jobs)
-                if (j.n == fpc) fill(j, cbm.data() + q++ * 8 * fpc, fpc);
-            if (nfull)
-                if (int rc = mp_hip_codec_decode_chunks(codec, cbm.data(), (int)nfull, fpc, audio.data())) return codec_fail(rc);
-            for (const Job &j : jobs)
-                if (j.n > 0 && j.n != fpc) {
-                    fill(j, cbm.data(), j.n);
-                    if (int rc = mp_hip_codec_decode(codec, cbm.data(), j.n, audio.data() + j.at)) return codec_fail(rc);
-                }
+                if (j.n > 0) fill(j, cbm.data() + q++ * 8 * mx, mx);
+            if (int rc = mp_hip_codec_stream_decode_ragged(dev->cstream, ids.data(), (int)ids.size(), cbm.data(), lens.data(),
+                                                           mx, audio.data()))
+                return codec_fail(rc);
+            return MP_OK;
         }
-        // delivery, slot by slot
-        for (const Job &j : jobs) {
-            if (j.n > 0) {
-                if (first) {
-                    dev->timing.first_audio_ms = ms_since(t0);
-                    first = false;
-                }
-                if (!j.fin) delivered[j.b] = j.f0 + j.n;
-                if (!on_audio(j.utt, audio.data() + j.at, j.n * 1024, r.user) && !j.fin) {
-                    // the callback asked to stop: the utterance ends here, its slot is refilled at the next round end
-                    stopped[j.b] = 1;
-                    static const int one = 1;
-                    HIPCHK(hipMemcpyAsync(dev->done + j.b, &one, 4, hipMemcpyHostToDevice, dev->stream));
-                    HIPCHK(hipStreamSynchronize(dev->stream));
-                }
+        // the reference's per-chunk semantics (chunks are independent, magpie.cpp:4739-4742):
+        // full chunks in one launch sequence, a shorter one on its own
+        size_t nfull = 0, nsamp = 0;
+        for (Job &j : jobs)
+            if (j.n == fpc) j.at = nfull++ * (size_t)fpc * 1024;
+        nsamp = nfull * (size_t)fpc * 1024;
+        for (Job &j : jobs)
+            if (j.n > 0 && j.n != fpc) { j.at = nsamp; nsamp += (size_t)j.n * 1024; }
+        audio.resize(nsamp);
+        cbm.assign(std::max<size_t>(nfull, 1) * 8 * fpc, 0);
+        size_t q = 0;
+        for (const Job &j : jobs)
+            if (j.n == fpc) fill(j, cbm.data() + q++ * 8 * fpc, fpc);
+        if (nfull)
+            if (int rc = mp_hip_codec_decode_chunks(codec, cbm.data(), (int)nfull, fpc, audio.data())) return codec_fail(rc);
+        for (const Job &j : jobs)
+            if (j.n > 0 && j.n != fpc) {
+                fill(j, cbm.data(), j.n);
+                if (int rc = mp_hip_codec_decode(codec, cbm.data(), j.n, audio.data() + j.at)) return codec_fail(rc);
             }
-            if (j.fin) {
-                on_audio(j.utt, nullptr, 0, r.user);  // end-of-utterance notice
-                if (r.done) r.done(j.utt, h_codes + (size_t)j.b * S * 8, j.f0 + j.n, r.user);
-                r.st.useful_slot_iters += j.f0 + j.n;
+        return MP_OK;
+    }
+
+    // A decoded chunk to the callback. Declined (4820-4824) on a chunk that does not end its
+    // utterance: the slot is stopped, its done flag set behind the round already queued.
+    int deliver(const Job &j) {
+        if (first) {
+            dev->timing.first_audio_ms = ms_since(t0);
+            first = false;
+        }
+        delivered[j.b] = j.f0 + j.n;
+        if (on_audio && !on_audio(j.utt, audio.data() + j.at, j.n * 1024, user) && !j.ended) {
+            stopped[j.b] = 1;
+            static const int one = 1;
+            HIPCHK(hipMemcpyAsync(dev->done + j.b, &one, 4, hipMemcpyHostToDevice, dev->stream));
+            HIPCHK(hipStreamSynchronize(dev->stream));
+        }
+        return MP_OK;
+    }
+};
+}  // namespace
+
+// Streaming frame loop (magpie_synthesize_sentence_streaming's loop, magpie.cpp:4762-4838)
+// for every utterance of the batch: a round is frames_per_chunk iterations (fewer at
+// max_dec_steps), an utterance's last chunk may be shorter (EOS or max_dec_steps), and the
+// chunks reach `on_audio` in slot order. An utterance that ends, by its EOS or because its
+// callback declined a chunk, gets its end notice in the same round. Only the columns a round
+// wrote go to the single codes mirror.
+int mp_hip_decode_stream(mp_dev *dev, mp_codec *codec, int frames_per_chunk, mp_audio_cb on_audio, void *user,
+                         int32_t *codes_out, int32_t *n_frames, int64_t *total_samples) {
+    if (!dev) return MP_ERR_ARG;
+    if (!dev->batch_ready) return fail(dev, MP_ERR_STATE, "mp_hip_begin_batch must precede mp_hip_decode_stream");
+    if (!codec) return fail(dev, MP_ERR_ARG, "codec is required");
+    const int fpc = frames_per_chunk > 0 ? frames_per_chunk : 4;  // default 4 (magpie.h:621)
+    HIPCHK(hipSetDevice(dev->device));
+    const int B = dev->B, S = dev->max_steps;
+    if (int rc = prepare_iteration(dev)) return rc;
+    StreamRun sr{dev, codec, fpc, on_audio, user};
+    if (int rc = sr.open(B, 1)) return rc;
+    std::vector<int> ended(B, 0);
+    std::vector<Job> jobs;
+    // The next round, to be queued by whoever calls the result. `it` counts the replays queued
+    // and moves here, on the calling thread: a helper thread gets the round's numbers by value
+    // and shares nothing with this loop but the decode stream and the mirror it fills.
+    int it = 0;
+    auto next_round = [&](int k) {
+        const int f0 = it, n_it = std::min(fpc, S - it);
+        it += n_it;
+        return [&sr, k, n_it, f0]() -> int { return sr.enqueue(k, n_it, f0, n_it); };
+    };
+    if (int rc = next_round(0)()) return rc;
+    for (int k = 0;; k ^= 1) {
+        HIPCHK(hipEventSynchronize(dev->sev[k]));
+        const Snap v = sr.view(k);
+        if (int rc = handoff_bits(dev, v.nd[2])) return rc;  // before any frame of the round is delivered
+        const double t_wait = ms_since(sr.t0);
+        // this round's chunks: a live slot delivers whole chunks, an ended one what is left
+        jobs.clear();
+        bool more = false;
+        for (int b = 0; b < B; ++b) {
+            const bool done = v.done[b] != 0;
+            more |= !(done || sr.stopped[b]);
+            if (ended[b]) continue;
+            const int n = (done ? v.nf[b] : v.step[b]) - sr.delivered[b];
+            if (n < 0 || n > fpc) return fail(dev, MP_ERR_STATE, "stream: a slot offers more than one chunk in a round");
+            if (done || n == fpc) jobs.push_back({b, b, sr.delivered[b], n, done, 0});
+        }
+        more &= it < S;
+        // Queuing a round's graph replays can block the host (the queue's packet slots fill
+        // up: 32 iterations of 65 launches), which left the codec waiting behind the next
+        // round's decode, serialising the two (configs[2]: 27.2k vs 27.5k frames/s serial,
+        // r06d): a round with codec work large enough to matter is queued from a helper
+        // thread while this thread runs the codec (HIP calls are thread-safe)
+        std::future<int> queued;
+        const bool async_q = more && stream_async() && B * fpc >= STREAM_ASYNC_MIN_FRAMES;  // (a thread per round)
+        if (more) {
+            auto enqueue = next_round(k ^ 1);
+            if (async_q) {
+                queued = std::async(std::launch::async, [dev, enqueue]() -> int {
+                    HIPCHK(hipSetDevice(dev->device));  // the current device is per thread
+                    return enqueue();
+                });
+            } else if (int rc = enqueue()) {
+                return rc;
+            }
+        }
+        if (stream_trace()) fprintf(stderr, "[stream] round at %.3f ms: chunk landed, next queued %s at %.3f ms\n", t_wait,
+                                    async_q ? "(async)" : "", ms_since(sr.t0));
+        if (int rc = sr.decode(jobs, v)) return rc;
+        if (stream_trace()) fprintf(stderr, "[stream]   codec of %zu chunks done at %.3f ms\n", jobs.size(), ms_since(sr.t0));
+        if (queued.valid())
+            if (int rc = queued.get()) return rc;
+        for (const Job &j : jobs) {
+            if (j.n > 0)
+                if (int rc = sr.deliver(j)) return rc;
+            if (j.ended || sr.stopped[j.b]) {  // end-of-utterance notice: (utt, NULL, 0)
+                ended[j.b] = 1;
+                if (on_audio) on_audio(j.b, nullptr, 0, user);
             }
         }
         if (!more) break;
-        k ^= 1;
     }
-    HIPCHK(hipEventRecord(r.e1, dev->stream));
-    HIPCHK(hipEventSynchronize(r.e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, r.e0, r.e1));
-    r.st.iterations = it;
-    r.st.decode_ms = ms;
-    dev->timing.decode_ms = ms;
-    dev->timing.frames_total = (int)r.st.useful_slot_iters;
+    HIPCHK(hipStreamSynchronize(dev->stream));
+    dev->timing.decode_ms = ms_since(sr.t0);
     dev->timing.iterations = it;
+    int total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n_frames) n_frames[b] = sr.delivered[b];
+        total += sr.delivered[b];
+    }
+    dev->timing.frames_total = total;
+    if (codes_out) HIPCHK(hipMemcpy(codes_out, dev->codes_out, (size_t)B * S * 8 * 4, hipMemcpyDeviceToHost));
+    if (total_samples) *total_samples = (int64_t)total * 1024;
+    return MP_OK;
+}
+
+// ---------------------------------------------------------------- streaming slot pool
+// pool_run's loop with a round of fpc = r.poll replays between two looks at the slots, and the
+// streaming mechanism above. Installs happen at round ends only, so a slot is a whole number
+// of chunks in unless it finished inside the round. An utterance that ended, or whose callback
+// declined a chunk in the round before, leaves its slot at the round end: the slot takes the
+// staged utterance before the next round is queued, its codec lane starts over, and its
+// chunks reach on_audio under the utterance's index (the event order is
+// magpie_amd.dist.simulate_pool_stream). Each snapshot has a codes mirror of its own, copied
+// whole ahead of the installs that zero a refilled slot's rows: a finished utterance's codes
+// are on the host before its slot is reinstalled.
+static int pool_stream_run(mp_dev *dev, PoolRun &r, mp_codec *codec, mp_audio_cb on_audio) {
+    const int fpc = r.poll;
+    std::vector<int> occ;  // utterance of each slot, -1 once it has ended
+    if (int rc = pool_start(dev, r, occ)) return rc;
+    const int B = (int)occ.size();
+    if (B == 0) return MP_OK;
+    const int S = dev->max_steps;
+    StreamRun sr{dev, codec, fpc, on_audio, r.user};
+    if (int rc = sr.open(B, 2)) return rc;
+    HIPCHK(r.e0.create());
+    HIPCHK(r.e1.create());
+    HIPCHK(hipEventRecord(r.e0, dev->stream));
+    std::vector<Job> jobs;
+    int it = 0, live = B;
+    // every utterance leaves its slot within max_steps iterations and two rounds
+    const long long it_max = ((long long)r.N + 1) * ((long long)S + 2 * fpc);
+    if (int rc = sr.enqueue(0, fpc, 0, S)) return rc;
+    it += fpc;
+    for (int k = 0;; k ^= 1) {
+        if (it > it_max) return fail(dev, MP_ERR_STATE, "slot pool: a slot never finished");
+        HIPCHK(hipEventSynchronize(dev->sev[k]));
+        const Snap v = sr.view(k);
+        if (int rc = handoff_bits(dev, v.nd[2])) return rc;  // before any frame is delivered
+        jobs.clear();
+        for (int b = 0; b < B; ++b) {
+            if (occ[b] < 0) continue;
+            const bool ended = v.done[b] != 0 || sr.stopped[b];
+            // a stopped utterance's frames of the round that was already queued are not delivered
+            const int n = sr.stopped[b] ? 0 : (v.done[b] ? v.nf[b] : v.step[b]) - sr.delivered[b];
+            if (n < 0 || n > fpc) return fail(dev, MP_ERR_STATE, "slot pool: a slot is not a whole number of chunks in");
+            if (n > 0 || ended) jobs.push_back({b, occ[b], sr.delivered[b], n, ended, 0});
+        }
+        // finished slots take the staged utterances, then the next round is queued
+        for (const Job &j : jobs) {
+            if (!j.ended) continue;
+            occ[j.b] = -1;
+            --live;
+            if (!r.staged) continue;
+            ++live;
+            if (int rc = pool_refill(dev, r, occ, j.b)) return rc;
+        }
+        const bool more = live > 0;
+        if (more) {
+            if (int rc = sr.enqueue(k ^ 1, fpc, 0, S)) return rc;
+            it += fpc;
+        }
+        if (int rc = sr.decode(jobs, v)) return rc;
+        for (const Job &j : jobs)  // a finished slot's lane starts over
+            if (sr.cont && j.ended)
+                if (int rc = mp_hip_codec_stream_reset(dev->cstream, j.b)) return sr.codec_fail(rc);
+        for (const Job &j : jobs) {
+            if (j.n > 0)
+                if (int rc = sr.deliver(j)) return rc;
+            if (!j.ended) continue;
+            on_audio(j.utt, nullptr, 0, r.user);  // end-of-utterance notice
+            if (r.done) r.done(j.utt, v.codes + (size_t)j.b * S * 8, j.f0 + j.n, r.user);
+            r.st.useful_slot_iters += j.f0 + j.n;
+            sr.delivered[j.b] = sr.stopped[j.b] = 0;  // the slot's next utterance starts from nothing
+        }
+        if (!more) break;
+    }
+    if (int rc = end_timing(dev, r.e0, r.e1, it, (int)r.st.useful_slot_iters)) return rc;
+    r.st.iterations = it;
+    r.st.decode_ms = dev->timing.decode_ms;
     return MP_OK;
 }
 

@@ -205,6 +205,52 @@ def test_callback_stops_one_utterance(dev, codec, toks, singles, one_shots):
         np.testing.assert_array_equal(La.audio(b), Lb.audio(b), err_msg=f"utterance {b}")
 
 
+def _batch_rounds(frames, fpc):
+    """the chunk lengths the streaming batch hands out round by round: round r carries frames
+    r*fpc .. of every utterance that still has some"""
+    return [[min(fpc, f - r * fpc) for f in frames if f > r * fpc] for r in range((max(frames) + fpc - 1) // fpc)]
+
+
+@pytest.mark.parametrize("fpc", [4, 3])
+def test_batch_continuous_round_mixes_full_and_short_chunks(dev, codec, toks, fpc):
+    """mp_hip_decode_stream in continuous mode through rounds whose chunks differ in length (one
+    ragged stream decode per round), and through an utterance that ends on a chunk boundary"""
+    utts = [0, 5, 8, 7, 2]
+    kw = dict(max_dec_steps=STEPS, frames_per_chunk=fpc)
+
+    def stream(us, continuous):
+        L = Listener(len(us))
+        codes, total, _ = dev.synthesize_stream(codec, [toks[u] for u in us], L, speakers=[SPKS[u] for u in us],
+                                                continuous=continuous, **kw)
+        assert total == 1024 * sum(len(c) for c in codes)
+        return L, codes
+
+    L, codes = stream(utts, True)
+    frames = [len(c) for c in codes]
+    print(f"fpc {fpc}: frames {frames}, rounds {_batch_rounds(frames, fpc)}")
+    # the inputs' property, from the frame counts: with 4-frame chunks some round holds a full
+    # chunk beside two short ones of different lengths; at this chunk size some round holds a full
+    # chunk beside a short one, and some utterance ends on a chunk boundary
+    assert any(4 in r and len({n for n in r if n < 4}) >= 2 for r in _batch_rounds(frames, 4)), frames
+    assert any(fpc in r and min(r) < fpc for r in _batch_rounds(frames, fpc)), frames
+    assert any(f % fpc == 0 for f in frames), frames
+    assert not L.late
+    for b, f in enumerate(frames):
+        sizes = [c.size // 1024 for c in L.chunks[b]]
+        assert sizes == [fpc] * (f // fpc) + ([f % fpc] if f % fpc else []), (b, sizes, f)
+    for b, u in enumerate(utts):
+        alone = stream([u], True)[1][0]
+        assert np.array_equal(codes[b], alone), (b, u)
+        np.testing.assert_array_equal(L.audio(b), codec.decode(np.ascontiguousarray(codes[b].T)), err_msg=f"utterance {u}")
+    Ls, codes_s = stream(utts, False)
+    for b, u in enumerate(utts):
+        assert np.array_equal(codes_s[b], codes[b]), (b, u)
+        assert [c.size for c in Ls.chunks[b]] == [c.size for c in L.chunks[b]], (b, u)
+        for k, chunk in enumerate(Ls.chunks[b]):
+            own = codec.decode(np.ascontiguousarray(codes[b][k * fpc:k * fpc + chunk.size // 1024].T))
+            np.testing.assert_array_equal(chunk, own, err_msg=f"utterance {u} chunk {k}")
+
+
 def test_argument_errors_leave_device_usable(ma, dev, codec, toks, singles, one_shots):
     bad = [t.copy() for t in toks]
     bad[-1][0] = 5000  # a token id out of range in the LAST utterance: refused before anything runs
