@@ -1309,8 +1309,6 @@ struct mp_codec {
     unsigned long long *ts_dev = nullptr;
     int ts_stage = -1, ts_block = -1;
     std::string ts_file;
-    int *lane_tab = nullptr;  // stream decodes: the call's lane table (mpc::HistP::lanes) and, behind it, the
-                              // chunks' own frame counts (mpc::HistP::nfr), behind its codes
 };
 
 // Stateful streaming decode: per lane, what the next chunk's first outputs need from the
@@ -1455,18 +1453,22 @@ int ensure_buffers(mp_codec *c, int nchunk, int F, size_t codes_extra = 0) {
     return MP_OK;
 }
 
+// The launchers' h: a stream decode's history, the kernel's trailing HistP (null: stateless
+// chunks, the kernel without it); grid, block and ConvP / ConvTP are the same either way.
 template <int BM, int BN, int MODE>
-hipError_t launch_conv(const mpc::ConvP &p, int nchunk, int nbranch, hipStream_t s) {
+hipError_t launch_conv(const mpc::ConvP &p, int nchunk, int nbranch, hipStream_t s, const mpc::HistP *h = nullptr) {
+    using namespace mpc;
     dim3 grid(p.Coutp / BM, nchunk * p.tiles_per_chunk, nbranch);
     // fewer workgroups than ~4 per CU cannot hide the channel loop's load latency by
     // occupancy: pipeline it instead (streaming chunks, the small early stages)
-    const bool pipe = MODE == mpc::IN_F16 && (size_t)grid.x * grid.y * grid.z < 1024;
-    if (pipe) hipLaunchKernelGGL((mpc::conv_mfma_kernel<BM, BN, mpc::IN_F16, true>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((mpc::conv_mfma_kernel<BM, BN, MODE, false>), grid, dim3(256), 0, s, p);
+    const bool pipe = MODE == IN_F16 && (size_t)grid.x * grid.y * grid.z < 1024;
+    if (pipe && h) hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, IN_F16, true, HistP>), grid, dim3(256), 0, s, p, *h);
+    else if (pipe) hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, IN_F16, true>), grid, dim3(256), 0, s, p);
+    else if (h) hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, MODE, false, HistP>), grid, dim3(256), 0, s, p, *h);
+    else hipLaunchKernelGGL((conv_mfma_kernel<BM, BN, MODE, false>), grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
-// h: a stream decode's history (null: stateless chunks)
 template <int RWV, int CWV, int NCB, bool DEEP>
 hipError_t launch_conv2(mpc::ConvP p, int nchunk, int nbranch, hipStream_t s, const mpc::HistP *h = nullptr) {
     constexpr int BN = CWV * 16 * mpc::C2_NT;
@@ -1545,16 +1547,7 @@ hipError_t run_rl(const mpc::RlP &p, int Cp, int nchunk, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-// conv_mfma_kernel with a stream decode's history
-template <int BM, int BN, int MODE>
-hipError_t launch_conv_stream(const mpc::ConvP &p, const mpc::HistP &h, int nchunk, int nbranch, hipStream_t s) {
-    dim3 grid(p.Coutp / BM, nchunk * p.tiles_per_chunk, nbranch);
-    const bool pipe = MODE == mpc::IN_F16 && (size_t)grid.x * grid.y * grid.z < 1024;  // launch_conv's rule
-    if (pipe) hipLaunchKernelGGL((mpc::conv_mfma_kernel<BM, BN, mpc::IN_F16, true, mpc::HistP>), grid, dim3(256), 0, s, p, h);
-    else hipLaunchKernelGGL((mpc::conv_mfma_kernel<BM, BN, MODE, false, mpc::HistP>), grid, dim3(256), 0, s, p, h);
-    return hipGetLastError();
-}
-// h: a stream decode's history (null: stateless chunks); the same kernel choice either way
+// the same kernel choice with a stream decode's history or without
 hipError_t run_conv(const mpc::ConvP &p, int BM, int mode, int nchunk, int nbranch, hipStream_t s,
                     const mpc::HistP *h = nullptr) {
     using namespace mpc;
@@ -1569,42 +1562,57 @@ hipError_t run_conv(const mpc::ConvP &p, int BM, int mode, int nchunk, int nbran
             case 32: if (p.T >= 128) return launch_conv2<1, 4, 1, false>(p, nchunk, nbranch, s, h); break;
         }
     }
-    if (h) {
-        if (BM == 64) {
-            if (mode == IN_FSQ) return launch_conv_stream<64, 64, IN_FSQ>(p, *h, nchunk, nbranch, s);
-            return launch_conv_stream<64, 64, IN_F16>(p, *h, nchunk, nbranch, s);
-        }
-        return launch_conv_stream<32, 128, IN_F16>(p, *h, nchunk, nbranch, s);
-    }
     if (BM == 64) {
-        if (mode == IN_FSQ) return launch_conv<64, 64, IN_FSQ>(p, nchunk, nbranch, s);
-        return launch_conv<64, 64, IN_F16>(p, nchunk, nbranch, s);
+        if (mode == IN_FSQ) return launch_conv<64, 64, IN_FSQ>(p, nchunk, nbranch, s, h);
+        return launch_conv<64, 64, IN_F16>(p, nchunk, nbranch, s, h);
     }
-    return launch_conv<32, 128, IN_F16>(p, nchunk, nbranch, s);
+    return launch_conv<32, 128, IN_F16>(p, nchunk, nbranch, s, h);
 }
 
 // One stage's ConvTranspose; a stage whose residual blocks run fused takes no f16 operands
+// (a stream decode's never do: it is not built without them)
 template <int CINP, int COUTP, int S, bool AVG, int R>
-hipError_t launch_convt(const mpc::ConvTP &p, bool fused, hipStream_t s) {
+hipError_t launch_convt(const mpc::ConvTP &p, bool fused, hipStream_t s, const mpc::HistP *h = nullptr) {
+    using namespace mpc;
     const dim3 grid((p.nchunk * ((p.Tin + R - 1) / R) * (COUTP / 2) + 255) / 256);
-    auto kernel = mpc::conv_transpose2_kernel<CINP, COUTP, S, AVG, R, true>;
+    if (h) {
+        if (fused) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((conv_transpose2_kernel<CINP, COUTP, S, AVG, R, true, HistP>), grid, dim3(256), 0, s, p, *h);
+        return hipGetLastError();
+    }
+    auto kernel = conv_transpose2_kernel<CINP, COUTP, S, AVG, R, true>;
     if constexpr (rb_fusable(COUTP))  // the 448-channel stage has no fused form: no second instantiation
-        if (fused) kernel = mpc::conv_transpose2_kernel<CINP, COUTP, S, AVG, R, false>;
+        if (fused) kernel = conv_transpose2_kernel<CINP, COUTP, S, AVG, R, false>;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
-// Decode nchunk independent chunks of F frames each (codes [chunk][8][F]).
-int codec_run(mp_codec *c, int nchunk, int F) {
+// A stream decode's side of the launch sequence: the stream whose lanes the call's chunks are,
+// and the call's HistP (lanes, nfr, maxf, nlanes, lbytes set by the caller; the sequence
+// points tail / f32 at each launch's piece of the state).
+struct StreamCtx {
+    mp_codec_stream *st;
+    mpc::HistP h;
+};
+
+// The nano-codec's launch sequence over nchunk chunks of F frames each.
+// sx null: independent chunks (codes [chunk][8][F]), every conv's rows before the chunk zero.
+// sx set: chunk q is one chunk of lane sx->h.lanes[q], laid out for F frames of which
+// sx->h.nfr[q] are its own (codes [chunk][8][6 + F], -1 behind its own frames): every loader
+// reads the lane's state and leaves the next. The same launches either way, but for the fused
+// residual blocks, which carry no state: `fused` below is the one condition.
+int codec_run(mp_codec *c, int nchunk, int F, StreamCtx *sx = nullptr) {
     using namespace mpc;
     hipStream_t s = c->stream;
+    mp_codec_stream *st = sx ? sx->st : nullptr;
+    HistP *h = sx ? &sx->h : nullptr;
     // pre-conv with the FSQ dequant in its loader
     {
         ConvP p{};
         p.W[0] = c->pre.w; p.bias[0] = c->pre.b; p.x[0] = nullptr; p.out[0] = c->x_pre;
         p.resid[0] = nullptr; p.act[0] = nullptr; p.ks[0] = 7; p.codes = c->codes; p.cout_real = 864;
         p.Cinp = 32; p.Coutp = CP_PRE; p.T = F; p.dil = 1; p.tiles_per_chunk = (F + 63) / 64;
-        CHK(run_conv(p, 64, IN_FSQ, nchunk, 1, s));
+        CHK(run_conv(p, 64, IN_FSQ, nchunk, 1, s, h));
     }
     int T = F;
     for (int i = 0; i < NSTAGE; ++i) {
@@ -1618,14 +1626,16 @@ int codec_run(mp_codec *c, int nchunk, int F) {
         tp.w = c->up_w[i]; tp.bias = c->up_b[i]; tp.out = c->x0; tp.cout_real = C; tp.Coutp = Cp;
         for (int j = 0; j < 3; ++j) { tp.act[j] = c->a16[j]; tp.act_alpha[j] = c->rb_alpha[i][j][0][0]; }
         tp.Tin = T; tp.s = RATE[i]; tp.nchunk = nchunk;
+        if (h) h->f32 = st->ct_prev[i];
+        // the fused residual blocks (rl_kernel, rb_kernel) keep no state across chunks
+        const bool fused = !sx && rb_fused(Cp);
         // input steps per thread: 1 and 2 on the short early stages (threads), CT_R later
-        const bool fused = rb_fused(Cp);
         switch (i) {
-            case 0: CHK((launch_convt<896, 448, 8, false, 1>(tp, fused, s))); break;
-            case 1: CHK((launch_convt<448, 224, 8, true, 2>(tp, fused, s))); break;
-            case 2: CHK((launch_convt<224, 128, 4, true, CT_R>(tp, fused, s))); break;
-            case 3: CHK((launch_convt<128, 64, 2, true, CT_R>(tp, fused, s))); break;
-            default: CHK((launch_convt<64, 32, 2, true, CT_R>(tp, fused, s))); break;
+            case 0: CHK((launch_convt<896, 448, 8, false, 1>(tp, fused, s, h))); break;
+            case 1: CHK((launch_convt<448, 224, 8, true, 2>(tp, fused, s, h))); break;
+            case 2: CHK((launch_convt<224, 128, 4, true, CT_R>(tp, fused, s, h))); break;
+            case 3: CHK((launch_convt<128, 64, 2, true, CT_R>(tp, fused, s, h))); break;
+            default: CHK((launch_convt<64, 32, 2, true, CT_R>(tp, fused, s, h))); break;
         }
         T *= RATE[i];
         if (fused && rl_fused(Cp)) {
@@ -1663,85 +1673,7 @@ int codec_run(mp_codec *c, int nchunk, int F) {
             }
             continue;
         }
-        const int BM = BMS[i], BN = BM == 64 ? 64 : 128;
-        for (int k = 0; k < 3; ++k) {
-            // h = conv_{ks_j, d_k}(HS_in(x)) for the 3 branches j; only HS_sk(h) (f16) is kept
-            ConvP p{};
-            for (int j = 0; j < 3; ++j) {
-                const mp_codec::Conv &cv = c->rb[i][j][k][0];
-                p.W[j] = cv.w; p.Wf[j] = cv.wf; p.bias[j] = cv.b; p.x[j] = c->a16[j]; p.out[j] = nullptr; p.resid[j] = nullptr;
-                p.act[j] = c->b16[j]; p.act_alpha[j] = c->rb_alpha[i][j][k][1]; p.ks[j] = KS[j];
-            }
-            p.act_nsnake = C / 2; p.cout_real = C; p.Cinp = Cp; p.Coutp = Cp; p.T = T; p.dil = DIL[k];
-            p.tiles_per_chunk = (T + BN - 1) / BN;
-            CHK(run_conv(p, BM, IN_F16, nchunk, 3, s));
-            // x' = x + conv_{ks_j, 1}(HS_sk(h)); plus the next block's operand HS_in(x')
-            for (int j = 0; j < 3; ++j) {
-                const mp_codec::Conv &cv = c->rb[i][j][k][1];
-                p.W[j] = cv.w; p.Wf[j] = cv.wf; p.bias[j] = cv.b; p.x[j] = c->b16[j];
-                p.out[j] = c->brb[j]; p.resid[j] = k == 0 ? c->x0 : c->brb[j];
-                p.act[j] = k < 2 ? c->a16[j] : nullptr;
-                p.act_alpha[j] = k < 2 ? c->rb_alpha[i][j][k + 1][0] : nullptr;
-            }
-            p.dil = 1;
-            CHK(run_conv(p, BM, IN_F16, nchunk, 3, s));
-        }
-    }
-    PostP pp{c->brb[0], c->brb[1], c->brb[2], c->post_alpha, c->post_w, c->post_b, c->audio, T, nchunk};
-    hipLaunchKernelGGL(post_conv_kernel<>, dim3(nchunk * ((T + 255) / 256)), dim3(256), 0, s, pp);
-    CHK(hipGetLastError());
-    return MP_OK;
-}
-
-// ---- stream lanes: the per-conv launch sequence with history (run_conv's choice between
-// conv_mfma_kernel and conv2_kernel, in their HistP forms; their bits are the fused kernels',
-// tests/test_codec_gpu.py)
-template <int CINP, int COUTP, int S, bool AVG, int R>
-hipError_t launch_convt_stream(const mpc::ConvTP &p, const mpc::HistP &h, hipStream_t s) {
-    const dim3 grid((p.nchunk * ((p.Tin + R - 1) / R) * (COUTP / 2) + 255) / 256);
-    hipLaunchKernelGGL((mpc::conv_transpose2_kernel<CINP, COUTP, S, AVG, R, true, mpc::HistP>), grid, dim3(256), 0, s, p, h);
-    return hipGetLastError();
-}
-
-// One chunk on each of n lanes, laid out for F frames each, chunk q's own frames c->lane_tab[n + q]
-// (c->lane_tab; c->codes [n][8][6 + F], -1 behind a chunk's own frames): codec_run's two-launch
-// residual blocks with every loader reading the lane's state and leaving the next.
-int codec_stream_run(mp_codec_stream *st, int n, int F) {
-    using namespace mpc;
-    mp_codec *c = st->c;
-    hipStream_t s = c->stream;
-    HistP h{};
-    h.lanes = c->lane_tab;
-    h.nfr = c->lane_tab + n;
-    h.maxf = F;
-    h.nlanes = st->lanes;
-    h.lbytes = st->lbytes;
-    {
-        ConvP p{};
-        p.W[0] = c->pre.w; p.bias[0] = c->pre.b; p.x[0] = nullptr; p.out[0] = c->x_pre;
-        p.resid[0] = nullptr; p.act[0] = nullptr; p.ks[0] = 7; p.codes = c->codes; p.cout_real = 864;
-        p.Cinp = 32; p.Coutp = CP_PRE; p.T = F; p.dil = 1; p.tiles_per_chunk = (F + 63) / 64;
-        CHK(run_conv(p, 64, IN_FSQ, n, 1, s, &h));
-    }
-    int T = F;
-    for (int i = 0; i < NSTAGE; ++i) {
-        const int cin = CH[i], C = CH[i + 1], Cin_p = i == 0 ? CP_PRE : CP[i - 1], Cp = CP[i];
-        ConvTP tp{};
-        tp.x = i == 0 ? c->x_pre : c->brb[0];
-        tp.xa = c->brb[1]; tp.xb = c->brb[2];
-        tp.alpha = c->up_alpha[i]; tp.n_snake = cin / 2; tp.cin_real = cin; tp.Cinp = Cin_p;
-        tp.w = c->up_w[i]; tp.bias = c->up_b[i]; tp.out = c->x0; tp.cout_real = C; tp.Coutp = Cp;
-        for (int j = 0; j < 3; ++j) { tp.act[j] = c->a16[j]; tp.act_alpha[j] = c->rb_alpha[i][j][0][0]; }
-        tp.Tin = T; tp.s = RATE[i]; tp.nchunk = n;
-        h.f32 = st->ct_prev[i];
-        switch (i) {  // codec_run's steps per thread
-            case 0: CHK((launch_convt_stream<896, 448, 8, false, 1>(tp, h, s))); break;
-            case 1: CHK((launch_convt_stream<448, 224, 8, true, 2>(tp, h, s))); break;
-            case 2: CHK((launch_convt_stream<224, 128, 4, true, CT_R>(tp, h, s))); break;
-            case 3: CHK((launch_convt_stream<128, 64, 2, true, CT_R>(tp, h, s))); break;
-            default: CHK((launch_convt_stream<64, 32, 2, true, CT_R>(tp, h, s))); break;
-        }
-        T *= RATE[i];
+        // the two-launch residual blocks (their bits are the fused kernels', tests/test_codec_gpu.py)
         const int BM = BMS[i], BN = BM == 64 ? 64 : 128;
         for (int k = 0; k < 3; ++k)
             for (int sk = 0; sk < 2; ++sk) {
@@ -1749,7 +1681,7 @@ int codec_stream_run(mp_codec_stream *st, int n, int F) {
                 for (int j = 0; j < 3; ++j) {
                     const mp_codec::Conv &cv = c->rb[i][j][k][sk];
                     p.W[j] = cv.w; p.Wf[j] = cv.wf; p.bias[j] = cv.b; p.ks[j] = KS[j];
-                    h.tail[j] = st->tail[i][j][k][sk];
+                    if (h) h->tail[j] = st->tail[i][j][k][sk];
                     if (!sk) {  // h = conv_{ks_j, d_k}(HS_in(x)); only HS_sk(h) (f16) is kept
                         p.x[j] = c->a16[j]; p.out[j] = nullptr; p.resid[j] = nullptr;
                         p.act[j] = c->b16[j]; p.act_alpha[j] = c->rb_alpha[i][j][k][1];
@@ -1761,12 +1693,17 @@ int codec_stream_run(mp_codec_stream *st, int n, int F) {
                 }
                 p.act_nsnake = C / 2; p.cout_real = C; p.Cinp = Cp; p.Coutp = Cp; p.T = T; p.dil = sk ? 1 : DIL[k];
                 p.tiles_per_chunk = (T + BN - 1) / BN;
-                CHK(run_conv(p, BM, IN_F16, n, 3, s, &h));
+                CHK(run_conv(p, BM, IN_F16, nchunk, 3, s, h));
             }
     }
-    h.f32 = st->post_hs;
-    PostP pp{c->brb[0], c->brb[1], c->brb[2], c->post_alpha, c->post_w, c->post_b, c->audio, T, n};
-    hipLaunchKernelGGL(post_conv_kernel<HistP>, dim3(n * ((T + 255) / 256)), dim3(256), 0, s, pp, h);
+    const PostP pp{c->brb[0], c->brb[1], c->brb[2], c->post_alpha, c->post_w, c->post_b, c->audio, T, nchunk};
+    const dim3 grid(nchunk * ((T + 255) / 256));
+    if (h) {
+        h->f32 = st->post_hs;
+        hipLaunchKernelGGL(post_conv_kernel<HistP>, grid, dim3(256), 0, s, pp, *h);
+    } else {
+        hipLaunchKernelGGL(post_conv_kernel<>, grid, dim3(256), 0, s, pp);
+    }
     CHK(hipGetLastError());
     return MP_OK;
 }
@@ -1778,6 +1715,63 @@ int stream_reset_lane(mp_codec_stream *st, int lane) {
         CHK(hipMemsetAsync(st->state + ((size_t)par * st->lanes + lane) * st->lbytes, 0, st->lbytes, c->stream));
     st->parity[lane] = st->started[lane] = 0;
     std::fill(st->hist.begin() + (size_t)lane * 48, st->hist.begin() + (size_t)(lane + 1) * 48, -1);
+    return MP_OK;
+}
+
+// What a decode call does around the launch sequence, stateless (sx null) or stream: the
+// buffers, the codes up through pinned memory, the sequence between the two events of
+// last_ms, the audio down and out. stage(host codes) writes the call's nchunk * 8 * F +
+// codes_extra ints; it runs once the device buffers stand, so it may take c->codes' address.
+template <class Stage>
+int decode_call(mp_codec *c, int nchunk, int F, size_t codes_extra, StreamCtx *sx, float *audio_out, Stage stage) {
+    if (int rc = ensure_buffers(c, nchunk, F, codes_extra)) return rc;
+    const size_t ncodes = (size_t)nchunk * 8 * F + codes_extra, nsamp = (size_t)nchunk * F * mpc::HOP;
+    CHK(c->codes_pin.reserve(ncodes * 4));
+    CHK(c->audio_pin.reserve(nsamp * 4));
+    stage((int32_t *)c->codes_pin.p);
+    CHK(hipMemcpyAsync(c->codes, c->codes_pin.p, ncodes * 4, hipMemcpyHostToDevice, c->stream));
+    CHK(c->ev0.create());
+    CHK(c->ev1.create());
+    CHK(hipEventRecord(c->ev0, c->stream));
+    if (int rc = codec_run(c, nchunk, F, sx)) return rc;
+    CHK(hipEventRecord(c->ev1, c->stream));
+    CHK(hipMemcpyAsync(c->audio_pin.p, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
+    CHK(hipStreamSynchronize(c->stream));
+    memcpy(audio_out, c->audio_pin.p, nsamp * 4);
+    CHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+    return MP_OK;
+}
+
+// diagnostics: MAGPIE_CODEC_TS=stage,block,file -> the phase stamps of that stage's
+// rb_kernel launch for residual block `block` (tools_dev/codec_rb_timeline.py)
+constexpr size_t TS_N = (size_t)3 * mpc::RB_TS_GX * mpc::RB_TS_N;
+// before a decode (read per call: parsed into locals and committed only when all 3 fields
+// parse; absent or malformed, the stamps are off again)
+int ts_arm(mp_codec *c) {
+    const char *e = getenv("MAGPIE_CODEC_TS");
+    char file[512] = {0};
+    int st = -1, bl = -1;
+    if (e && sscanf(e, "%d,%d,%511s", &st, &bl, file) == 3) {
+        c->ts_stage = st;
+        c->ts_block = bl;
+        c->ts_file = file;
+        if (!c->ts_dev) CHK(c->ts_mem.bytes(&c->ts_dev, TS_N * 8));
+        CHK(hipMemsetAsync(c->ts_dev, 0, TS_N * 8, c->stream));
+    } else {
+        c->ts_stage = c->ts_block = -1;
+        c->ts_file.clear();
+    }
+    return MP_OK;
+}
+// after it: the stamps to the file
+int ts_dump(mp_codec *c) {
+    if (!c->ts_dev || c->ts_file.empty()) return MP_OK;
+    std::vector<unsigned long long> h(TS_N);
+    CHK(hipMemcpy(h.data(), c->ts_dev, TS_N * 8, hipMemcpyDeviceToHost));
+    if (FILE *f = fopen(c->ts_file.c_str(), "wb")) {
+        fwrite(h.data(), 8, h.size(), f);
+        fclose(f);
+    }
     return MP_OK;
 }
 
@@ -1811,50 +1805,12 @@ int mp_hip_codec_decode_chunks(mp_codec *c, const int32_t *codes, int n_chunks, 
     if (!c) return MP_ERR_ARG;
     if (!codes || !audio_out || n_chunks < 1 || chunk_frames < 1) { c->err = "invalid arguments"; return MP_ERR_ARG; }
     CHK(hipSetDevice(c->device));
-    if (int rc = ensure_buffers(c, n_chunks, chunk_frames)) return rc;
-    const size_t ncodes = (size_t)n_chunks * 8 * chunk_frames, nsamp = (size_t)n_chunks * chunk_frames * mpc::HOP;
-    CHK(c->codes_pin.reserve(ncodes * 4));
-    CHK(c->audio_pin.reserve(nsamp * 4));
-    memcpy(c->codes_pin.p, codes, ncodes * 4);
-    CHK(hipMemcpyAsync(c->codes, c->codes_pin.p, ncodes * 4, hipMemcpyHostToDevice, c->stream));
-    CHK(c->ev0.create());
-    CHK(c->ev1.create());
-    // diagnostics: MAGPIE_CODEC_TS=stage,block,file -> the phase stamps of that stage's
-    // rb_kernel launch for residual block `block` (tools_dev/codec_rb_timeline.py)
-    constexpr size_t TS_N = (size_t)3 * mpc::RB_TS_GX * mpc::RB_TS_N;
-    // (read per call: parsed into locals and committed only when all 3 fields parse;
-    // absent or malformed, the stamps are off again)
-    {
-        const char *e = getenv("MAGPIE_CODEC_TS");
-        char file[512] = {0};
-        int st = -1, bl = -1;
-        if (e && sscanf(e, "%d,%d,%511s", &st, &bl, file) == 3) {
-            c->ts_stage = st;
-            c->ts_block = bl;
-            c->ts_file = file;
-            if (!c->ts_dev) CHK(c->ts_mem.bytes(&c->ts_dev, TS_N * 8));
-            CHK(hipMemsetAsync(c->ts_dev, 0, TS_N * 8, c->stream));
-        } else {
-            c->ts_stage = c->ts_block = -1;
-            c->ts_file.clear();
-        }
-    }
-    CHK(hipEventRecord(c->ev0, c->stream));
-    if (int rc = codec_run(c, n_chunks, chunk_frames)) return rc;
-    CHK(hipEventRecord(c->ev1, c->stream));
-    CHK(hipMemcpyAsync(c->audio_pin.p, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
-    CHK(hipStreamSynchronize(c->stream));
-    memcpy(audio_out, c->audio_pin.p, nsamp * 4);
-    CHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-    if (c->ts_dev && !c->ts_file.empty()) {
-        std::vector<unsigned long long> h(TS_N);
-        CHK(hipMemcpy(h.data(), c->ts_dev, TS_N * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(c->ts_file.c_str(), "wb")) {
-            fwrite(h.data(), 8, h.size(), f);
-            fclose(f);
-        }
-    }
-    return MP_OK;
+    if (int rc = ts_arm(c)) return rc;
+    const size_t ncodes = (size_t)n_chunks * 8 * chunk_frames;
+    if (int rc = decode_call(c, n_chunks, chunk_frames, 0, nullptr, audio_out,
+                             [&](int32_t *hc) { memcpy(hc, codes, ncodes * 4); }))
+        return rc;
+    return ts_dump(c);
 }
 
 int mp_hip_codec_last_ms(mp_codec *c, float *ms) {
@@ -1939,33 +1895,30 @@ int mp_hip_codec_stream_decode_ragged(mp_codec_stream *st, const int32_t *lane_i
     }
     const int F = max_frames, FH = F + 6;
     CHK(hipSetDevice(c->device));
-    const size_t ncodes = (size_t)n * 8 * FH, nsamp = (size_t)n * F * mpc::HOP;
-    if (int rc = ensure_buffers(c, n, F, (size_t)n * 8 * 6 + 2 * (size_t)n)) return rc;
-    c->lane_tab = c->codes + ncodes;
-    CHK(c->codes_pin.reserve((ncodes + 2 * (size_t)n) * 4));
-    CHK(c->audio_pin.reserve(nsamp * 4));
-    int32_t *hc = (int32_t *)c->codes_pin.p;
-    for (int q = 0; q < n; ++q) {
-        const int ln = lane_ids[q], nf = n_frames[q];
-        for (int cb = 0; cb < 8; ++cb) {  // [6 of history | the chunk's own frames | -1: a zero operand]
-            int32_t *row = hc + ((size_t)q * 8 + cb) * FH;
-            memcpy(row, st->hist.data() + (size_t)ln * 48 + cb * 6, 6 * 4);
-            memcpy(row + 6, codes + ((size_t)q * 8 + cb) * F, (size_t)nf * 4);
-            std::fill(row + 6 + nf, row + FH, -1);
+    // behind the codes [n][8][FH]: the lane table [n] and the chunks' own frame counts [n]
+    const size_t ncodes = (size_t)n * 8 * FH;
+    StreamCtx sx{st, {}};
+    sx.h.maxf = F;
+    sx.h.nlanes = st->lanes;
+    sx.h.lbytes = st->lbytes;
+    int32_t *hc = nullptr;
+    const auto stage = [&](int32_t *pin) {
+        hc = pin;
+        for (int q = 0; q < n; ++q) {
+            const int ln = lane_ids[q], nf = n_frames[q];
+            for (int cb = 0; cb < 8; ++cb) {  // [6 of history | the chunk's own frames | -1: a zero operand]
+                int32_t *row = hc + ((size_t)q * 8 + cb) * FH;
+                memcpy(row, st->hist.data() + (size_t)ln * 48 + cb * 6, 6 * 4);
+                memcpy(row + 6, codes + ((size_t)q * 8 + cb) * F, (size_t)nf * 4);
+                std::fill(row + 6 + nf, row + FH, -1);
+            }
+            hc[ncodes + q] = ln * 4 + 2 * st->started[ln] + st->parity[ln];
+            hc[ncodes + n + q] = nf;
         }
-        hc[ncodes + q] = ln * 4 + 2 * st->started[ln] + st->parity[ln];
-        hc[ncodes + n + q] = nf;
-    }
-    CHK(hipMemcpyAsync(c->codes, hc, (ncodes + 2 * (size_t)n) * 4, hipMemcpyHostToDevice, c->stream));
-    CHK(c->ev0.create());
-    CHK(c->ev1.create());
-    CHK(hipEventRecord(c->ev0, c->stream));
-    if (int rc = codec_stream_run(st, n, F)) return rc;
-    CHK(hipEventRecord(c->ev1, c->stream));
-    CHK(hipMemcpyAsync(c->audio_pin.p, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
-    CHK(hipStreamSynchronize(c->stream));
-    memcpy(audio_out, c->audio_pin.p, nsamp * 4);
-    CHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+        sx.h.lanes = c->codes + ncodes;
+        sx.h.nfr = sx.h.lanes + n;
+    };
+    if (int rc = decode_call(c, n, F, (size_t)n * 8 * 6 + 2 * (size_t)n, &sx, audio_out, stage)) return rc;
     // the call succeeded: every lane's state advances (the parity just written becomes the one read)
     for (int q = 0; q < n; ++q) {
         const int ln = lane_ids[q];

@@ -65,6 +65,29 @@ def test_mixed_chunk_sizes_equal_one_shot(gpu_codec):
     np.testing.assert_array_equal(got, gpu_codec.decode(codes))
 
 
+@pytest.mark.parametrize("switches", [{}, {"MAGPIE_CODEC_UNFUSED": "1", "MAGPIE_CODEC_RL": "0"}], ids=["default", "unfused"])
+def test_first_chunk_equals_stateless_decode(gpu_codec, monkeypatch, switches):
+    """The two arms of the codec's one launch sequence against each other: a first chunk on a
+    fresh lane (zero state: the causal padding) is Codec.decode of the same codes, bit for bit,
+    with the stateless arm on its fused residual blocks (the default switches) and on the
+    two-launch blocks the stream arm always runs. F = 1 keeps every stage below the wide-tile
+    thresholds (conv_mfma_kernel everywhere, T shorter than the tails); F = 32 reaches
+    conv2_kernel on every stage. Then one ragged call of 3 lanes after a reset."""
+    for k, v in switches.items():
+        monkeypatch.setenv(k, v)
+    s = gpu_codec.stream(lanes=3)
+    for lane, F in enumerate((1, 4, 32)):  # each on a lane nothing has used
+        codes = _codes(80 + F, F)
+        np.testing.assert_array_equal(s.decode(codes[None], lanes=[lane])[0], gpu_codec.decode(codes), err_msg=f"F = {F}")
+    lens = (4, 1, 3)
+    rows = [_codes(90 + q, n) for q, n in enumerate(lens)]
+    s.reset()
+    got = s.decode_ragged(rows, lens)
+    s.close()
+    for q, row in enumerate(rows):
+        np.testing.assert_array_equal(got[q], gpu_codec.decode(row), err_msg=f"lane {q}: {lens[q]} of 4 frames")
+
+
 def test_lanes_interleaved_reordered_and_reset(gpu_codec):
     sizes = {0: [2, 5, 1, 3], 1: [4, 1, 2], 2: [1, 5, 3, 2]}
     codes = {b: _codes(30 + b, sum(sizes[b])) for b in sizes}
