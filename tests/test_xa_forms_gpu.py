@@ -5,7 +5,8 @@ the O-projection launch) reads 6 KB per text token and layer; the direct form
 (q_net GEMV, attention over K, V, o_net: magpie.cpp:1713-1767, the order the oracle
 restates) reads 1 KB per token + 0.79 MB of q_net / o_net, so AUTO switches to it
 above MP_XA_DIRECT_T = 160 tokens. Both are checked against the oracle at the f32
-bar, and batches against single runs of the same form.
+bar, and batches against single runs of the same form. The text-length edges of both
+forms (T = 1 ... 1024, the AUTO switch at 160 / 161): tests/test_text_edges_gpu.py.
 """
 import numpy as np
 import pytest
