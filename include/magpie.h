@@ -133,9 +133,16 @@ struct magpie_context {
     // stream (MP_STREAM_CODEC_CONTINUOUS), so a sentence's audio is one magpie_codec_decode of
     // its frames; false (default): stateless chunks, as the reference streams
     bool continuous_codec;
+    // added: classifier-free guidance scale (mp_hip_set_cfg; the model's published default is
+    // 2.5); 0 (default) = off, nothing changes. Honoured by magpie_synthesize_codes*,
+    // magpie_synthesize_codes_batch, magpie_synthesize_sentence_streaming and
+    // magpie_synthesize_streaming; every utterance then takes two decode slots, so a batch
+    // and max_parallel_sentences are capped at half of mp_hip_max_batch. f32 and bf16 weights
+    // only; the two *_queue calls return their failure value under guidance.
+    float cfg_scale;
     magpie_context()
         : n_threads(4), temperature(0.7f), top_k(80), speaker_id(0), codec(nullptr), seed(0),
-          max_parallel_sentences(8), continuous_codec(false) {}
+          max_parallel_sentences(8), continuous_codec(false), cfg_scale(0.f) {}
 };
 
 // magpie.h:310-313

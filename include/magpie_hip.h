@@ -117,6 +117,42 @@ int mp_hip_load_model_ex(mp_dev *dev, const char *gguf_path, int weight_mode);
 #define MP_KV_F32 0
 #define MP_KV_BF16 1
 int mp_hip_set_kv_mode(mp_dev *dev, int kv_mode);
+/* Classifier-free guidance, applied from the next mp_hip_begin_batch. scale 0 (the default)
+ * is off; a non-finite scale is MP_ERR_ARG. The model's published inference default is 2.5.
+ *
+ * A guided utterance is two decode slots that share every sampled code:
+ *   - the conditional branch: exactly the plain decode of the utterance;
+ *   - the unconditional branch: the same decoder without the text and without the speaker
+ *     context. Its encoder output is all zeros, so (the cross-attention has no biases) its
+ *     XA K and V are zeros and every layer's cross-attention adds a zero vector, in the
+ *     prefill and in every step; no encoder pass runs for it. Its 110 context rows are the
+ *     decoder positions alone. It has its own self-attention cache, and its input frames
+ *     (BOS, then every emitted frame) are the conditional branch's, code for code.
+ * Every codebook of a frame is picked once, from
+ *     mixed[i] = scale * cond[i] + (1 - scale) * uncond[i],   i = 0..2023,
+ * in f32, by the one device function every pick site uses (cfg_mix, mp_fused.hpp). The mask
+ * (special ids; EOS while step < 4 or ignore_eos), the first-max argmax, the top-k draw
+ * (stream stream_base + b, step, codebook) and the argmax / EOS rule apply to `mixed` as
+ * they apply to the logits of a plain decode. The picked code feeds both branches. Both
+ * advance, stop and freeze together; n_frames, codes, emit_eos_frame and max_dec_steps
+ * behave per utterance as without guidance. At scale 1 `mixed` equals `cond` exactly, and
+ * the codes are the plain decode's, bit for bit.
+ *
+ * Slot layout: mp_hip_begin_batch(B) builds 2B slots, slot b < B the conditional branch of
+ * utterance b and slot B + b its partner, then pads as always (padding slots are unpaired
+ * copies of slot 0). Hence B <= mp_hip_max_batch / 2, else MP_ERR_ARG. The mix happens in
+ * the pick's own logit load: the iteration's launch list is the plain list of 2B slots, and
+ * the scale lives in device memory, so one captured graph serves any scale.
+ * mp_hip_decode / mp_hip_decode_stream report B utterances (codes, n_frames, audio
+ * callbacks, mp_timing.frames_total).
+ *
+ * Refused under guidance, before anything runs and leaving the device usable:
+ *   - MP_ERR_UNSUPPORTED from mp_hip_begin_batch in the F16 and Q8_0 / Q4_0 weight modes
+ *     (f32 as stored and bf16 run, with either SA cache type and either XA form);
+ *   - MP_ERR_UNSUPPORTED from mp_hip_decode_queue and mp_hip_decode_queue_stream: a refill
+ *     would have to install a pair into two slots (a follow-up).
+ * mp_hip_lt_sample is not affected. */
+int mp_hip_set_cfg(mp_dev *dev, float scale);
 /* Cross-attention form of the decode step, applied from the next mp_hip_begin_batch.
  * REASSOC: x += sum_t softmax_t(K'_t . LN(x)) V'_t with K' = W_q^T K, V' = W_o V
  * precomputed per utterance (reads 6 KB per text token and layer; fused into the
@@ -196,6 +232,9 @@ int mp_hip_decode_queue(mp_dev *dev, const int32_t *tokens, const int32_t *n_tok
 /* decoder hidden state after every step (BOS first): [B][max_dec_steps+1][768];
  * requires params.trace_hidden. */
 int mp_hip_get_trace(mp_dev *dev, float *hidden);
+/* the same of the unconditional branches of a guided batch (mp_hip_set_cfg), utterance b's
+ * at [b]; mp_hip_get_trace returns the conditional branches'. MP_ERR_STATE without guidance. */
+int mp_hip_get_trace_uncond(mp_dev *dev, float *hidden);
 /* magpie_encode_text (src/magpie.cpp:2284-2374): the text encoder alone (embedding +
  * positions, the encoder layers, final LN) for one utterance, into a private device
  * workspace; enc_out: host [n_tokens][768]. A batch in progress (mp_hip_begin_batch /

@@ -91,6 +91,13 @@ void magpie_free(magpie_context *ctx) {
 
 const char *magpie_get_backend_name(magpie_context *ctx) { return ctx && ctx->model.dev ? "HIP (gfx950)" : "none"; }
 
+// ctx->cfg_scale to the device, ahead of every begin_batch / queue call (mp_hip_set_cfg)
+static bool apply_cfg(const magpie_context *ctx) {
+    if (mp_hip_set_cfg(ctx->model.dev, ctx->cfg_scale) == MP_OK) return true;
+    fprintf(stderr, "magpie: cfg_scale must be finite\n");
+    return false;
+}
+
 static mp_params params_of(const magpie_context *ctx) {
     mp_params p{};
     p.temperature = ctx->temperature;
@@ -117,6 +124,7 @@ bool magpie_synthesize_codes_batch(magpie_context *ctx, const int32_t *const *to
     }
     const mp_params p = params_of(ctx);
     const int steps = p.max_dec_steps > 0 ? p.max_dec_steps : 500;
+    if (!apply_cfg(ctx)) return false;
     if (mp_hip_begin_batch(ctx->model.dev, tok.data(), nt.data(), spk.data(), B, tmax, &p) != MP_OK) {
         fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));
         return false;
@@ -149,6 +157,7 @@ bool magpie_synthesize_codes_queue(magpie_context *ctx, const int32_t *const *to
     auto on_done = [](int utt, const int32_t *codes, int n_frames, void *user) {
         ((std::vector<int32_t> *)user)[utt].assign(codes, codes + (size_t)n_frames * 8);
     };
+    if (!apply_cfg(ctx)) return false;  // (a guided device refuses the queue: MP_ERR_UNSUPPORTED)
     if (mp_hip_decode_queue(ctx->model.dev, tok.data(), nt.data(), spk.data(), N, tmax, slots, 0, &p, nullptr, on_done,
                             out, nullptr) != MP_OK) {
         fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));
@@ -398,6 +407,7 @@ long long stream_batch(magpie_context *ctx, magpie_codec *codec, const std::vect
     p.seed = ctx->seed;
     p.stream_base = sentence0;  // sentence i draws from stream i, batched or not
     p.emit_eos_frame = 1;       // the streaming loop emits the EOS frame (magpie.cpp:4800-4806)
+    if (!apply_cfg(ctx)) return -1;
     if (mp_hip_begin_batch(ctx->model.dev, tok.data(), nt.data(), spk.data(), B, tmax, &p) != MP_OK) {
         fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));
         return -1;
@@ -455,7 +465,8 @@ int magpie_synthesize_streaming(magpie_context *ctx, magpie_codec *codec, const 
     ctx->top_k = params.top_k;
     ctx->speaker_id = params.speaker_id;
     const int bmax = std::max(1, mp_hip_max_batch(ctx->model.dev));
-    const int P = std::max(1, std::min(ctx->max_parallel_sentences, bmax));
+    // under guidance a sentence takes two slots
+    const int P = std::max(1, std::min(ctx->max_parallel_sentences, ctx->cfg_scale != 0.f ? bmax / 2 : bmax));
     long long total = 0;
     for (size_t s0 = 0; s0 < sents.size(); s0 += P) {
         const size_t s1 = std::min(sents.size(), s0 + P);
@@ -504,6 +515,7 @@ int magpie_synthesize_streaming_queue(magpie_context *ctx, magpie_codec *codec, 
         if (r.codes) r.codes[utt].assign(codes, codes + (size_t)n_frames * 8);
     };
     mp_hip_set_stream_codec_mode(ctx->model.dev, ctx->continuous_codec ? MP_STREAM_CODEC_CONTINUOUS : MP_STREAM_CODEC_STATELESS);
+    if (!apply_cfg(ctx)) return -1;  // (a guided device refuses the queue: MP_ERR_UNSUPPORTED)
     if (mp_hip_decode_queue_stream(ctx->model.dev, codec->dev, tok.data(), nt.data(), spk.data(), N, tmax, slots,
                                    params.frames_per_chunk, &p, nullptr, audio, done, &run, nullptr) != MP_OK) {
         fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));

@@ -220,7 +220,8 @@ constexpr int FIN_THREADS = 256;
 // counter, the done flags and ts, which the entry reads next.
 __global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *logits, int *step, int *iter, int *done_flags,
                                                                   unsigned long long *ts, int smp_on, FinP p) {
-    p.logits = logits; p.step = step; p.iter = iter; p.done = done_flags; p.ts = ts; p.smp.on = smp_on;
+    p.logits = logits; p.step = step; p.iter = iter; p.done = done_flags; p.ts = ts;
+    p.smp.on = smp_on & 1; p.smp.guided = smp_on >> 1;
     const unsigned long long t_start = ts_begin(p.ts);
     const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
     // greedy: codebook 7's pick split over the 4 waves (lt_step_body's split pick: each
@@ -230,12 +231,7 @@ __global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *l
     float lq[QPR];
     int stp_q = 0;
     if (quad) {
-        const float *lg = p.logits + (size_t)b * VCB + ts_dep(t_start);
-#pragma unroll
-        for (int q = 0; q < QPR; ++q) {
-            const int i = (tid & 63) + 64 * (w * QPR + q);
-            lq[q] = i < VCB ? lg[i] : -INFINITY;
-        }
+        cfg_logit_rows<QPR>(p.logits + ts_dep(t_start), p.smp, b, w * QPR, lq);
         stp_q = p.step[b];
     }
     if (p.iter && b == 0 && tid == 0) p.iter[0] += 1;  // the next iteration's hand-off tags
@@ -287,7 +283,7 @@ __global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *l
         if (!quad) {
             __shared__ float scratch[2 * VCB];
             const int stp = p.step[b];
-            i0 = wave_pick(p.logits + (size_t)b * VCB + ts_dep(t_start), p.ignore_eos || stp < 4, p.audio_bos,
+            i0 = wave_pick(p.logits + ts_dep(t_start), p.ignore_eos || stp < 4, p.audio_bos,
                            p.audio_eos, p.smp, b, stp, NCB - 1, scratch, amax);
         }
         if (tid == 0) {
@@ -446,7 +442,7 @@ __global__ __launch_bounds__(64) void lt_pick_kernel(GemvP p) {
             if (j < p.cb) { kr[j] = *(const float4 *)(kb + j * LTD); vr[j] = *(const float4 *)(vb + j * LTD); }
     }
     float lv[PICK_R];
-    load_logits(p.logits + (size_t)b * VCB, lv);
+    load_logits(p.logits, p.smp, b, lv);
     const int stp = p.step[b];
     int amax;
     const int code = wave_pick_v(lv, p.ignore_eos || stp < 4, p.audio_bos, p.audio_eos, p.smp, b, stp, p.cb - 1, wsc,
@@ -718,7 +714,7 @@ __device__ __forceinline__ void lt_y_load(const LtFfn2P &p, int b, LtYPre &r) {
         r.kr[j] = *(const f32x4 *)(p.ltk + row + jj * LTD);
         r.vr[j] = *(const f32x4 *)(p.ltv + row + jj * LTD);
     }
-    load_logits(p.logits + (size_t)b * VCB, r.lv);
+    load_logits(p.logits, p.smp, b, r.lv);
     r.stp = p.step[b];
 }
 // position cb's table rows for `code` (codebook cb-1's pick): q | k, o_net(v), P[code]
@@ -806,12 +802,7 @@ __device__ __forceinline__ void lt_y_load_q(const LtFfn2P &p, int b, int w, LtYP
         r.kr[j] = *(const f32x4 *)(p.ltk + row + jj * LTD);
         r.vr[j] = *(const f32x4 *)(p.ltv + row + jj * LTD);
     }
-    const float *lg = p.logits + (size_t)b * VCB;
-#pragma unroll
-    for (int q = 0; q < QPR; ++q) {
-        const int i = lane + 64 * (w * QPR + q);
-        lq[q] = i < VCB ? lg[i] : -INFINITY;
-    }
+    cfg_logit_rows<QPR>(p.logits, p.smp, b, w * QPR, lq);
     r.stp = p.step[b];
 }
 // every wave: its rows' pick, its candidate's table rows (g, in flight during the exchange),
@@ -925,7 +916,8 @@ template <int NB>
 __global__ __launch_bounds__(MP_BLOCK) void lt_ffn2_kernel(const float *logits, float *ltk, float *ltv, const int *step,
                                                            const float *lnw, unsigned long long *ts, int cb, int smp_on,
                                                            LtFfn2P p) {
-    p.logits = logits; p.ltk = ltk; p.ltv = ltv; p.step = step; p.f.lnw = lnw; p.f.ts = ts; p.cb = cb; p.smp.on = smp_on;
+    p.logits = logits; p.ltk = ltk; p.ltv = ltv; p.step = step; p.f.lnw = lnw; p.f.ts = ts; p.cb = cb;
+    p.smp.on = smp_on & 1; p.smp.guided = smp_on >> 1;
     const unsigned long long t_start = ts_begin(p.f.ts);
     float accs[NB];
     lt_step_body<NB>(p, blockIdx.x, ts_dep(t_start), accs, nullptr);
@@ -939,7 +931,7 @@ hipError_t op_lt_ffn2(const LtFfn2P &p, int NB, hipStream_t s) {
         !p.votab || !p.ptab || !p.lt_pos || !p.logits || !p.codes_cur || !p.step || !p.smp.cfg || !p.smp.argeos ||
         p.cb < 0 || p.cb >= NCB)
         return hipErrorInvalidValue;
-#define LT_FFN2_ARGS p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts, p.cb, p.smp.on, p
+#define LT_FFN2_ARGS p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts, p.cb, smp_flags(p.smp), p
     switch (NB) {
     case 1: mp::launch(lt_ffn2_kernel<1>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
     case 2: mp::launch(lt_ffn2_kernel<2>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
@@ -972,7 +964,8 @@ __device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u 
 __global__ __launch_bounds__(MP_BLOCK) void lt_slot_kernel(const float *logits, float *ltk, float *ltv, const int *step,
                                                            const float *lnw, unsigned long long *ts, int cb, int smp_on,
                                                            LtFfn2P p) {
-    p.logits = logits; p.ltk = ltk; p.ltv = ltv; p.step = step; p.f.lnw = lnw; p.f.ts = ts; p.cb = cb; p.smp.on = smp_on;
+    p.logits = logits; p.ltk = ltk; p.ltv = ltv; p.step = step; p.f.lnw = lnw; p.f.ts = ts; p.cb = cb;
+    p.smp.on = smp_on & 1; p.smp.guided = smp_on >> 1;
     const unsigned long long t_start = ts_begin(p.f.ts);
     static_assert(LTD == MP_BLOCK && LTS_U % 8 == 0 && LTS_U % MP_NWAVES == 0, "unit split");
     __shared__ __attribute__((aligned(16))) float xs[LTD];
@@ -1087,7 +1080,7 @@ hipError_t op_lt_slot(const LtFfn2P &p, int NB, hipStream_t s) {
         !p.smp.argeos || p.cb < 0 || p.cb >= NCB || NB < 1 || NB > 16)
         return hipErrorInvalidValue;
     mp::launch(lt_slot_kernel, dim3(LTS_P, NB), dim3(MP_BLOCK), 0, s, p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts, p.cb,
-               p.smp.on, p);
+               smp_flags(p.smp), p);
     return hipGetLastError();
 }
 
@@ -1318,7 +1311,7 @@ hipError_t op_lt_kvo(const GemvP &p, int NB, hipStream_t s) {
 hipError_t op_finalize(const FinP &p, int B, hipStream_t s) {
     if (!p.smp.cfg || !p.smp.argeos) return hipErrorInvalidValue;
     if (p.x && (!p.emb || !p.pos_emb || p.pos_rows < 1)) return hipErrorInvalidValue;
-    mp::launch(lt_finalize_kernel, dim3(B), dim3(FIN_THREADS), 0, s, p.logits, p.step, p.iter, p.done, p.ts, p.smp.on, p);
+    mp::launch(lt_finalize_kernel, dim3(B), dim3(FIN_THREADS), 0, s, p.logits, p.step, p.iter, p.done, p.ts, smp_flags(p.smp), p);
     return hipGetLastError();
 }
 

@@ -288,7 +288,7 @@ __global__ __launch_bounds__(MP_BLOCK) void lt_slot_q8_kernel(const float *logit
 #pragma clang fp contract(off)
     // leading arguments (mp_decode.hip, gemv_kernel's note): what the pick's first loads read, and ts
     p.g.logits = logits; p.g.ltk = ltk; p.g.ltv = ltv; p.g.step = step; p.g.lt_pos = lt_pos; p.ts = ts;
-    p.g.cb = cb_lead; p.g.smp.on = smp_on;
+    p.g.cb = cb_lead; p.g.smp.on = smp_on & 1; p.g.smp.guided = smp_on >> 1;
     const unsigned long long t_start = ts_begin(p.ts);
     constexpr int PPW = LTQ_P / WP, UW = LTF / WP, UWW = UW / MP_NWAVES, RWG = LTD / WP, RWW = RWG / MP_NWAVES;
     constexpr int NPT = LTQ_P * RWG / MP_BLOCK;  // merge: partial granules per thread
@@ -317,12 +317,7 @@ __global__ __launch_bounds__(MP_BLOCK) void lt_slot_q8_kernel(const float *logit
     int stq = 0;
     const bool quad = cb > 0 && !g.smp.on;
     if (quad) {
-        const float *lg = g.logits + (size_t)b * VCB;
-#pragma unroll
-        for (int r = 0; r < QPR; ++r) {
-            const int i = lane + 64 * (w * QPR + r);
-            lq[r] = i < VCB ? lg[i] : -INFINITY;
-        }
+        cfg_logit_rows<QPR>(g.logits, g.smp, b, w * QPR, lq);
 #pragma unroll
         for (int j = 0; j < NCB - 1; ++j)
             if (j < cb) { kr[j] = *(const float4 *)(g.ltk + rowb + j * LTD); vr[j] = *(const float4 *)(g.ltv + rowb + j * LTD); }
@@ -330,7 +325,7 @@ __global__ __launch_bounds__(MP_BLOCK) void lt_slot_q8_kernel(const float *logit
         stq = g.step[b];
     } else if (w == 0) {
         if (cb > 0) {
-            load_logits(g.logits + (size_t)b * VCB, lv);
+            load_logits(g.logits, g.smp, b, lv);
 #pragma unroll
             for (int j = 0; j < NCB - 1; ++j)
                 if (j < cb) { kr[j] = *(const float4 *)(g.ltk + rowb + j * LTD); vr[j] = *(const float4 *)(g.ltv + rowb + j * LTD); }
@@ -546,7 +541,7 @@ hipError_t op_lt_slot_q8(const LtSlotQ8P &p, int NB, hipStream_t s) {
         (g.cb > 0 && (!g.logits || !g.codes_cur || !g.qkvtab || !g.ptab || !g.lt_pos || !g.step || !g.smp.cfg ||
                       !g.smp.argeos)))
         return hipErrorInvalidValue;
-#define LTQ8_ARGS p.g.logits, p.g.ltk, p.g.ltv, p.g.step, p.g.lt_pos, p.ts, p.g.cb, p.g.smp.on, p
+#define LTQ8_ARGS p.g.logits, p.g.ltk, p.g.ltv, p.g.step, p.g.lt_pos, p.ts, p.g.cb, smp_flags(p.g.smp), p
     if (p.part) mp::launch(lt_slot_q8_kernel<true, true, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
     else if (p.wot) mp::launch(lt_slot_q8_kernel<true, false, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
     else if (NB >= 8) mp::launch(lt_slot_q8_kernel<false, false, 32>, dim3(32, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);

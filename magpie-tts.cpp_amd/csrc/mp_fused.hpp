@@ -27,13 +27,47 @@ namespace mp {
 // orders them, lane 0 runs the two sequential float loops. scratch: 2*VCB floats.
 // `stream` is the batch slot; the draw stream is the slot's entry of cfg->stream.
 constexpr int PICK_R = (VCB + 63) / 64;  // logits per lane
-__device__ __forceinline__ void load_logits(const float *lg, float (&lv)[PICK_R]) {
+// Classifier-free guidance: the one mix of a conditional and an unconditional logit, f32,
+// unfused, so every pick site and batch size computes the same bits. At scale 1 the second
+// product is 0 and the result is `cond` exactly: a guided run at 1 is the plain run.
+__device__ __forceinline__ float cfg_mix(float cond, float uncond, float scale) {
+#pragma clang fp contract(off)
+    return scale * cond + (1.0f - scale) * uncond;
+}
+// Logit rows [r0, r0 + NR) of slot b's pick (lane l holds ids l + 64 r), the padding past VCB
+// at -inf: every pick site's load. An unpaired slot (or a batch without guidance: no look
+// at the pairing) gets its own row as stored. A paired slot loads its partner's row behind
+// its own, both in flight together, and gets cfg_mix of the pair's two rows: the lower slot
+// of a pair is the conditional branch, so both slots compute the same values.
+template <int NR>
+__device__ __forceinline__ void cfg_logit_rows(const float *logits, const Sampling &smp, int b, int r0, float (&lv)[NR]) {
     const int lane = threadIdx.x & 63;
+    const float *lg = logits + (size_t)b * VCB;
 #pragma unroll
-    for (int r = 0; r < PICK_R; ++r) {
-        const int i = lane + 64 * r;
+    for (int r = 0; r < NR; ++r) {
+        const int i = lane + 64 * (r0 + r);
         lv[r] = i < VCB ? lg[i] : -INFINITY;
     }
+    if (!smp.guided) return;
+    const int pb = smp.cfg->partner[b];
+    if (pb < 0) return;  // wave-uniform: b is
+    const float *lp = logits + (size_t)pb * VCB;
+    float pv[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const int i = lane + 64 * (r0 + r);
+        pv[r] = i < VCB ? lp[i] : -INFINITY;
+    }
+    const float s = smp.cfg->cfg_scale;
+    const bool cond = b < pb;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const int i = lane + 64 * (r0 + r);
+        if (i < VCB) lv[r] = cond ? cfg_mix(lv[r], pv[r], s) : cfg_mix(pv[r], lv[r], s);
+    }
+}
+__device__ __forceinline__ void load_logits(const float *logits, const Sampling &smp, int b, float (&lv)[PICK_R]) {
+    cfg_logit_rows<PICK_R>(logits, smp, b, 0, lv);
 }
 // wave_pick on logits already loaded by load_logits (lv is modified)
 __device__ inline int wave_pick_v(float (&lv)[PICK_R], bool forbid_eos, int audio_bos, int audio_eos,
@@ -157,10 +191,11 @@ __device__ inline int wave_pick_v(float (&lv)[PICK_R], bool forbid_eos, int audi
     wave_lds_sync();
     return code;
 }
-__device__ inline int wave_pick(const float *lg, bool forbid_eos, int audio_bos, int audio_eos, const Sampling &smp,
+// (logits: the batch's rows; `stream`, the slot, picks its row -- and its partner's)
+__device__ inline int wave_pick(const float *logits, bool forbid_eos, int audio_bos, int audio_eos, const Sampling &smp,
                                 int stream, int step, int cb, float *scratch, int &amax) {
     float lv[PICK_R];
-    load_logits(lg, lv);
+    load_logits(logits, smp, stream, lv);
     return wave_pick_v(lv, forbid_eos, audio_bos, audio_eos, smp, stream, step, cb, scratch, amax);
 }
 
@@ -885,7 +920,7 @@ __device__ __forceinline__ void prologue(const GemvP &p, float *act, float *red,
         const int lane = tid & 63, w = tid >> 6;
         float *wsc = sc + ltc_off<NB>() + w * 2 * VCB;
         float cur[PICK_R], nxt[PICK_R];
-        if (w < NB) load_logits(p.logits + (size_t)w * VCB, cur);
+        if (w < NB) load_logits(p.logits, p.smp, w, cur);
         float4 kr[NCB], vr[NCB];
         if constexpr (SPW == 1) {
             if (w < NB) {
@@ -904,7 +939,7 @@ __device__ __forceinline__ void prologue(const GemvP &p, float *act, float *red,
             const int b = w + MP_NWAVES * j;
             if (b >= NB) break;  // wave-uniform
             const int bn = b + MP_NWAVES;
-            if (bn < NB) load_logits(p.logits + (size_t)bn * VCB, nxt);
+            if (bn < NB) load_logits(p.logits, p.smp, bn, nxt);
             int amax;
             const int code = wave_pick_v(cur, p.ignore_eos || stp[j] < 4, p.audio_bos, p.audio_eos, p.smp, b,
                                          stp[j], p.cb - 1, wsc, amax);

@@ -99,13 +99,23 @@ struct SmpCfg {                // device-resident, so a captured graph serves an
     int stream[16];            // draw stream of slot b: stream_base + b from mp_hip_begin_batch; a slot
                                // refilled by mp_hip_decode_queue carries its utterance's
                                // (slot_install_kernel), so a draw follows the utterance, not the slot
+    // Classifier-free guidance (mp_hip_set_cfg). A guided utterance is two slots, the
+    // conditional one c and its text-free partner u > c: partner[c] = u, partner[u] = c,
+    // stream[u] = stream[c]. Both pick every code from cfg_mix of their two logit rows
+    // (cfg_logit_rows, mp_fused.hpp), so both arrive at the same code. -1: unpaired.
+    float cfg_scale;
+    int partner[16];
 };
 struct Sampling {
     int on;                    // temperature >= 0.01 (baked into the captured graph)
     const SmpCfg *cfg;
     int *argeos;               // [B] 1 once a codebook's argmax was EOS this frame (4343-4346)
     int *amax;                 // optional [B][8]: every codebook's argmax (magpie_sample_result.argmax_codes)
+    int guided;                // the batch has paired slots (baked into the captured graph like `on`); 0: no
+                               // pick reads cfg->partner, every slot takes the unpaired path
 };
+// `on` and `guided` as the one leading kernel argument of the LT step / finalize kernels
+__host__ __device__ inline int smp_flags(const Sampling &s) { return (s.on ? 1 : 0) | (s.guided ? 2 : 0); }
 
 // LT FFN up + GELU + FFN down in one launch (lt_ffn_kernel): workgroup p owns
 // hidden units [p*16, p*16+16) and writes its share of FFN down, part[b][p][256]

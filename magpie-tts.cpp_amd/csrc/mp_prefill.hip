@@ -513,6 +513,10 @@ __global__ void embed_text_kernel(const int *tok, const int *T, int Tmax, const 
 // x[b][t] = baked_context[spk_b][t] + dec_pos[t] for the 110 context frames (4138-4189).
 __global__ void embed_context_kernel(const int *spk, const float *baked, const float *dec_pos, float *X) {
     const int m = blockIdx.x, b = m / CTX, t = m % CTX;
+    if (spk[b] < 0) {  // no speaker context (the unconditional branch of guidance): the positions alone
+        for (int k = threadIdx.x; k < D; k += blockDim.x) X[(size_t)m * D + k] = dec_pos[(size_t)t * D + k];
+        return;
+    }
     const float *src = baked + (size_t)spk[b] * CTX * D + (size_t)t * D;
     for (int k = threadIdx.x; k < D; k += blockDim.x) X[(size_t)m * D + k] = src[k] + dec_pos[(size_t)t * D + k];
 }

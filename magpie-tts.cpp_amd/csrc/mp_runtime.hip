@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -87,6 +88,7 @@ struct LtIo {
     int *codes_cur, *codes_prev, *codes_out, *step, *pos, *done, *nframes, *ndone, *argeos, *amax;
     SmpCfg *cfg;
     int sampling, ignore_eos, emit_eos, max_steps, lt_only;
+    int guided;  // the slots are paired (Sampling::guided)
 };
 
 }  // namespace mp
@@ -99,6 +101,11 @@ struct PreWs {
     const int32_t *tok, *T, *spk;  // device [NB][Tmax] token ids, [NB] lengths, [NB] speakers
     int NB, Tmax, max_seq, kv16;
     bool xa_direct;                // no K' / V' (kp, vp unused)
+    // classifier-free guidance (0: none): slots [n_text, 2 n_text) are the text-free partners
+    // of slots [0, n_text). The encoder and the XA K/V run for the n_text leading slots only;
+    // the partners' tables are zeros, their context rows the positions alone, and the padding
+    // slots behind them get slot 0's tables
+    int n_text;
     float *pX, *pH, *pQKV, *pATT, *pF, *pXQ, *pXAO, *gpart, *enc_out;  // scratch
     float *xak, *xav, *kp, *vp, *kc, *vc;                              // outputs
     hipStream_t stream;
@@ -127,6 +134,12 @@ struct mp_dev {
     bool loaded = false;
     // batch configuration
     int B = 0, NB = 0, Tmax = 0, max_steps = 0, max_seq = 0, nch = 0;
+    // mp_hip_set_cfg: applies from the next mp_hip_begin_batch. A guided batch (`guided`) of B
+    // utterances has slots = 2 B: slot b < B is utterance b's conditional branch, slot B + b
+    // its unconditional partner; otherwise slots = B
+    float cfg_scale = 0.f;
+    bool guided = false;
+    int slots = 0;
     mp_params params{};
     int kv_mode = MP_KV_F32;  // mp_hip_set_kv_mode: applies from the next mp_hip_begin_batch
     int xa_mode = MP_XA_AUTO;  // mp_hip_set_xa_mode: likewise
@@ -216,7 +229,8 @@ void free_batch(mp_dev *dev) {
     dev->granules.clear();
     dev->ops.clear();
     dev->batch_ready = false;
-    dev->B = dev->NB = dev->Tmax = dev->max_steps = 0;
+    dev->B = dev->NB = dev->Tmax = dev->max_steps = dev->slots = 0;
+    dev->guided = false;
     dev->xa_direct = false;
     dev->kp = dev->vp = nullptr;
     dev->trace = nullptr;  // a batch without a trace must not see (or write) the last one's
@@ -279,11 +293,14 @@ static hipError_t alloc_pre_scratch(mp::DevBlocks &mem, float **const (&p)[8], s
         if (hipError_t e = zero ? mem.get_zeroed(p[i], n[i], *zero) : mem.get(p[i], n[i])) return e;
     return hipSuccess;
 }
-int alloc_batch(mp_dev *dev, int B, int Tmax, int max_steps, bool trace) {
+int alloc_batch(mp_dev *dev, int B, bool guided, int Tmax, int max_steps, bool trace) {
     free_batch(dev);
-    const int NB = B <= 1 ? 1 : B <= 2 ? 2 : B <= 4 ? 4 : B <= 8 ? 8 : 16;
+    const int slots = guided ? 2 * B : B;
+    const int NB = slots <= 1 ? 1 : slots <= 2 ? 2 : slots <= 4 ? 4 : slots <= 8 ? 8 : 16;
     const int L = dev->m.dec_layers;
     dev->B = B;
+    dev->slots = slots;
+    dev->guided = guided;
     dev->NB = NB;
     dev->Tmax = Tmax;
     dev->max_steps = max_steps;
@@ -428,7 +445,7 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
     // the family of a tensor: the Q8_0 one where the file holds it quantised
     auto fam = [&](const mp::QW &q) -> const mp::OpTable & { return q ? tq : tb; };
     const double F = b16 ? 2.0 : 4.0, A = 4.0, act = (double)NB;
-    const mp::Sampling smp{io.sampling, io.cfg, io.argeos, io.amax};
+    const mp::Sampling smp{io.sampling, io.cfg, io.argeos, io.amax, io.guided};
     const Emit e{dev, out, NB, q8dump, mp::LtDumpP{io.logits, io.ltX, io.ltY, io.lty2, io.ltq, io.codes_cur}};
     auto base = [&](int cb) {
         mp::GemvP g = gemv_base(m, NB, io.step, smp, io.ignore_eos);
@@ -655,7 +672,7 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     // algorithmic bytes: weights at their stored width (Q8_0: 34 B per 32), activations f32
     const double F = b16 ? 2.0 : 4.0, A = 4.0, act = (double)NB;
     const bool sampling = dev->params.temperature >= 0.01f;
-    const mp::Sampling smp{sampling, dev->smpcfg, dev->argeos};
+    const mp::Sampling smp{sampling, dev->smpcfg, dev->argeos, nullptr, dev->guided};
     const Emit e{dev, out, NB, true, mp::LtDumpP{}};
     dev->q8dump_n = 0;
     dev->q8dump_index.clear();
@@ -796,7 +813,7 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     io.codes_cur = dev->codes_cur; io.codes_prev = dev->codes_prev; io.codes_out = dev->codes_out; io.step = dev->step;
     io.pos = dev->pos; io.done = dev->done; io.nframes = dev->nframes; io.ndone = dev->ndone; io.argeos = dev->argeos;
     io.amax = dev->amax; io.cfg = dev->smpcfg;
-    io.sampling = sampling; io.ignore_eos = dev->params.ignore_eos;
+    io.sampling = sampling; io.ignore_eos = dev->params.ignore_eos; io.guided = dev->guided;
     io.emit_eos = dev->params.emit_eos_frame; io.max_steps = dev->max_steps; io.lt_only = false;
     return build_lt(dev, io, NB, out, true);
 }
@@ -914,6 +931,7 @@ static int run_encoder(mp_dev *dev, const EncWs &w, hipStream_t s) {
 
 static PreWs batch_ws(const mp_dev *dev) {
     return PreWs{dev->tok, dev->T, dev->spk, dev->NB, dev->Tmax, dev->max_seq, dev->kv16, dev->xa_direct,
+                 dev->guided ? dev->B : 0,
                  dev->pX, dev->pH, dev->pQKV, dev->pATT, dev->pF, dev->pXQ, dev->pXAO, dev->gpart, dev->enc_out,
                  dev->xak, dev->xav, dev->kp, dev->vp, dev->kc, dev->vc, dev->stream};
 }
@@ -923,10 +941,12 @@ int run_preamble(mp_dev *dev, const PreWs &w) {
     const Model &m = dev->m;
     const int NB = w.NB, Tmax = w.Tmax, L = m.dec_layers;
     hipStream_t s = w.stream;
-    const int Me = NB * Tmax;
+    // the slots with a text: all of them, or under guidance the conditional ones
+    const int NE = w.n_text > 0 ? w.n_text : NB;
+    const int Me = NE * Tmax;
     auto pre_gemm = [&](GemmP gp, int epi, hipStream_t st) { return preamble_gemm(m, w.gpart, gp, epi, st); };
     {
-        const EncWs e{w.tok, w.T, NB, Tmax, w.pX, w.pH, w.pQKV, w.pATT, w.pF, w.gpart, w.enc_out};
+        const EncWs e{w.tok, w.T, NE, Tmax, w.pX, w.pH, w.pQKV, w.pATT, w.pF, w.gpart, w.enc_out};
         if (int rc = run_encoder(dev, e, s)) return rc;
     }
     // --- cross-attention K/V per layer (1663-1711): LN(encoder output) with each layer's
@@ -972,12 +992,12 @@ int run_preamble(mp_dev *dev, const PreWs &w) {
         gp.A = w.xak; gp.lda = 128; gp.W = m.xq_t[0]; gp.C = w.kp; gp.ldc = 768;
         gp.M = Tmax; gp.N = 768; gp.K = 128; gp.rows_per_utt = Tmax;
         gp.xround = -1;
-        gp.nbatch = NB * L; gp.wmod = L; gp.sA = (long long)Tmax * 128; gp.sW = 768 * 128; gp.sC = (long long)Tmax * 768;
+        gp.nbatch = NE * L; gp.wmod = L; gp.sA = (long long)Tmax * 128; gp.sW = 768 * 128; gp.sC = (long long)Tmax * 768;
         HIPCHK(pre_gemm(gp, GE_STORE, s));
         gp.A = w.xav; gp.W = m.dec[0].xo; gp.C = w.vp; gp.sW = s_xo;
         HIPCHK(pre_gemm(gp, GE_STORE, s));
     } else {
-        for (int b = 0; b < NB; ++b)
+        for (int b = 0; b < NE; ++b)
             for (int l = 0; l < L; ++l) {
                 if (m.dec[l].xq8 || w.xa_direct) continue;
                 const size_t xo = ((size_t)(b * L + l) * Tmax) * 128, po = ((size_t)(b * L + l) * Tmax) * 768;
@@ -990,7 +1010,29 @@ int run_preamble(mp_dev *dev, const PreWs &w) {
                 HIPCHK(pre_gemm(gp, GE_STORE, s));
             }
     }
-    // --- baked context + 110-frame causal prefill (3991-4060, 4167-4238)
+    // --- guidance: the unconditional partners' tables are zeros (an all-zero encoder output
+    //     through the bias-free kv_net: K = V = 0, hence K' = V' = 0), over every row of the
+    //     slot; the padding slots behind the pairs are copies of slot 0
+    if (w.n_text > 0) {
+        const size_t xs = (size_t)L * Tmax * 128, ps = (size_t)L * Tmax * 768;  // a slot's tables
+        const bool kp = !w.xa_direct && w.kp;
+        HIPCHK(hipMemsetAsync(w.xak + NE * xs, 0, NE * xs * 4, s));
+        HIPCHK(hipMemsetAsync(w.xav + NE * xs, 0, NE * xs * 4, s));
+        if (kp) {
+            HIPCHK(hipMemsetAsync(w.kp + NE * ps, 0, NE * ps * 4, s));
+            HIPCHK(hipMemsetAsync(w.vp + NE * ps, 0, NE * ps * 4, s));
+        }
+        for (int b = 2 * NE; b < NB; ++b) {
+            HIPCHK(hipMemcpyAsync(w.xak + b * xs, w.xak, xs * 4, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(w.xav + b * xs, w.xav, xs * 4, hipMemcpyDeviceToDevice, s));
+            if (kp) {
+                HIPCHK(hipMemcpyAsync(w.kp + b * ps, w.kp, ps * 4, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(w.vp + b * ps, w.vp, ps * 4, hipMemcpyDeviceToDevice, s));
+            }
+        }
+    }
+    // --- baked context + 110-frame causal prefill (3991-4060, 4167-4238); a speaker of -1
+    //     (a guidance partner) has no context: its rows are the positions alone
     const int Mc = NB * CTX;
     HIPCHK(pre_embed_context(w.spk, NB, m.baked, m.dec_pos, w.pX, s));
     HIPCHK(pre_ln_rows(w.pX, 768, m.dec[0].norm_self, w.pH, 768, Mc, m.eps, s));
@@ -1126,6 +1168,12 @@ int mp_hip_set_stream_codec_mode(mp_dev *dev, int mode) {
     return MP_OK;
 }
 
+int mp_hip_set_cfg(mp_dev *dev, float scale) {
+    if (!dev || !std::isfinite(scale)) return MP_ERR_ARG;
+    dev->cfg_scale = scale;
+    return MP_OK;
+}
+
 int mp_hip_set_kv_mode(mp_dev *dev, int kv_mode) {
     if (!dev || (kv_mode != MP_KV_F32 && kv_mode != MP_KV_BF16)) return MP_ERR_ARG;
     dev->kv_mode = kv_mode;
@@ -1183,22 +1231,32 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
     const int bmax = mp_hip_max_batch(dev);
     if (!tokens || !n_tokens || !speaker || B < 1 || B > bmax || tmax < 1 || !params)
         return fail(dev, MP_ERR_ARG, "invalid arguments (B must be 1..mp_hip_max_batch: 8 with f32 weights, 16 in the bf16 / F16 / Q8_0 / Q4_0 modes)");
+    // classifier-free guidance (mp_hip_set_cfg): two slots per utterance
+    const bool guided = dev->cfg_scale != 0.f;
+    if (guided) {
+        const int wm = dev->m.weight_mode;
+        if (wm != MP_WEIGHTS_AS_STORED && wm != MP_WEIGHTS_BF16)
+            return fail(dev, MP_ERR_UNSUPPORTED, "guidance (mp_hip_set_cfg) runs with f32 (as stored) and bf16 weights only, not in the F16 or Q8_0 / Q4_0 modes");
+        if (2 * B > bmax)
+            return fail(dev, MP_ERR_ARG, "under guidance an utterance takes two slots: B must be 1.." + std::to_string(bmax / 2) +
+                                             " (half of mp_hip_max_batch = " + std::to_string(bmax) + ")");
+    }
     int Tmax = 0, max_steps = 0;
     if (int rc = check_params(dev, params, &max_steps)) return rc;
     if (int rc = check_utterances(dev, tokens, n_tokens, speaker, B, tmax, &Tmax)) return rc;
     if (pin_tmax > 0) Tmax = std::max(Tmax, pin_tmax);
     HIPCHK(hipSetDevice(dev->device));
     const bool trace = params->trace_hidden != 0;
-    const bool same = dev->NB > 0 && dev->B == B && dev->Tmax == Tmax && dev->max_steps == max_steps &&
+    const bool same = dev->NB > 0 && dev->B == B && dev->guided == guided && dev->Tmax == Tmax && dev->max_steps == max_steps &&
                       (dev->trace != nullptr) == trace && dev->params.ignore_eos == params->ignore_eos &&
                       (dev->params.temperature >= 0.01f) == (params->temperature >= 0.01f) &&
                       dev->params.emit_eos_frame == params->emit_eos_frame &&
                       dev->kv16 == (dev->kv_mode == MP_KV_BF16) && dev->xa_direct == want_xa_direct(dev, Tmax);
     dev->params = *params;
     if (!same) {
-        if (int rc = alloc_batch(dev, B, Tmax, max_steps, trace)) return rc;
+        if (int rc = alloc_batch(dev, B, guided, Tmax, max_steps, trace)) return rc;
     }
-    const int NB = dev->NB;
+    const int NB = dev->NB, slots = dev->slots;
     auto t0 = std::chrono::steady_clock::now();
     std::vector<int> h_tok((size_t)NB * Tmax, 0), h_T(NB, 1), h_spk(NB, 0);
     for (int b = 0; b < B; ++b) {
@@ -1206,13 +1264,18 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
         h_spk[b] = speaker[b];
         for (int t = 0; t < n_tokens[b]; ++t) h_tok[(size_t)b * Tmax + t] = tokens[(size_t)b * tmax + t];
     }
-    for (int b = B; b < NB; ++b) { h_T[b] = h_T[0]; h_spk[b] = h_spk[0]; }
+    // a text-free partner: its utterance's length (zero XA rows), no speaker context (-1)
+    for (int b = B; b < slots; ++b) { h_T[b] = h_T[b - B]; h_spk[b] = -1; }
+    for (int b = slots; b < NB; ++b) { h_T[b] = h_T[0]; h_spk[b] = h_spk[0]; }
     HIPCHK(hipMemcpyAsync(dev->tok, h_tok.data(), h_tok.size() * 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(dev->T, h_T.data(), NB * 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(dev->spk, h_spk.data(), NB * 4, hipMemcpyHostToDevice, dev->stream));
     {   // sampling settings live on the device: the captured graph serves any of them
-        mp::SmpCfg cfg{params->temperature, params->top_k, (unsigned long long)params->seed, params->stream_base, {}};
-        for (int b = 0; b < 16; ++b) cfg.stream[b] = params->stream_base + b;
+        mp::SmpCfg cfg{params->temperature, params->top_k, (unsigned long long)params->seed, params->stream_base, {},
+                       dev->cfg_scale, {}};
+        for (int b = 0; b < 16; ++b) { cfg.stream[b] = params->stream_base + b; cfg.partner[b] = -1; }
+        if (guided)  // the pair draws from the utterance's stream
+            for (int b = 0; b < B; ++b) { cfg.partner[b] = B + b; cfg.partner[B + b] = b; cfg.stream[B + b] = cfg.stream[b]; }
         HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
         HIPCHK(hipMemsetAsync(dev->argeos, 0, NB * 4, dev->stream));
     }
@@ -1275,7 +1338,7 @@ int mp_hip_encode_text(mp_dev *dev, const int32_t *tokens, int n_tokens, float *
 
 // Per-decode device state: BOS frame at position 110 (magpie.cpp:4243-4318).
 int reset_decode_state(mp_dev *dev) {
-    const int NB = dev->NB, B = dev->B;
+    const int NB = dev->NB, B = dev->slots;  // a guided pair's two slots are both live
     std::vector<int> h_pos(NB, mp::CTX), h_zero(NB, 0), h_done(NB, 0), h_prev((size_t)NB * 8, dev->m.audio_bos);
     for (int b = B; b < NB; ++b) h_done[b] = 1;
     int h_nd[4] = {NB - B, 0, 0, 0};
@@ -1568,8 +1631,8 @@ static int pool_start(mp_dev *dev, PoolRun &r, std::vector<int> &occ) {
         }
         if (int rc = begin_batch(dev, tok.data(), nt.data(), spk.data(), B, r.tmax, &r.params, r.tmax)) return rc;
         // the draw streams follow the utterances, not the slots
-        mp::SmpCfg cfg{r.params.temperature, r.params.top_k, (unsigned long long)r.params.seed, r.params.stream_base, {}};
-        for (int b = 0; b < 16; ++b) cfg.stream[b] = r.params.stream_base + (b < B ? occ[b] : b);
+        mp::SmpCfg cfg{r.params.temperature, r.params.top_k, (unsigned long long)r.params.seed, r.params.stream_base, {}, 0.f, {}};
+        for (int b = 0; b < 16; ++b) { cfg.stream[b] = r.params.stream_base + (b < B ? occ[b] : b); cfg.partner[b] = -1; }
         HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
         HIPCHK(hipStreamSynchronize(dev->stream));
     }
@@ -1630,6 +1693,8 @@ static int pool_run(mp_dev *dev, PoolRun &r) {
 static int pool_call(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int N, int tmax,
                      int slots, int poll, const mp_params *params, mp_next_cb next, mp_done_cb done, void *user,
                      mp_queue_stats *stats, const std::function<int(PoolRun &)> &run) {
+    if (dev->cfg_scale != 0.f)
+        return fail(dev, MP_ERR_UNSUPPORTED, "the slot pool does not run under guidance (mp_hip_set_cfg): a refill would have to install a pair");
     const int bmax = mp_hip_max_batch(dev);
     if (!tokens || !n_tokens || !speaker || N < 1 || tmax < 1 || !params)
         return fail(dev, MP_ERR_ARG, "invalid arguments");
@@ -1823,6 +1888,8 @@ struct StreamRun {
             stopped[j.b] = 1;
             static const int one = 1;
             HIPCHK(hipMemcpyAsync(dev->done + j.b, &one, 4, hipMemcpyHostToDevice, dev->stream));
+            if (dev->guided)  // the pair stops together
+                HIPCHK(hipMemcpyAsync(dev->done + dev->B + j.b, &one, 4, hipMemcpyHostToDevice, dev->stream));
             HIPCHK(hipStreamSynchronize(dev->stream));
         }
         return MP_OK;
@@ -2032,7 +2099,7 @@ int mp_hip_lt_sample(mp_dev *dev, const float *hidden, float temperature, int to
         al(&io.ltk, 8 * 256); al(&io.ltv, 8 * 256); al(&io.ltf, 1024);
         al(&io.ltp, std::max({mp::LT_FFN_P, mp::LTS_P, mp::LTQ_P}) * 256);
         al(&io.logits, 2024); al(&io.codes_cur, 8); al(&io.step, 1); al(&io.done, 1); al(&io.argeos, 1); al(&io.amax, 8);
-        al(&io.cfg, 8);
+        al(&io.cfg, (sizeof(mp::SmpCfg) + 3) / 4);
         if (!ok) {
             dev->ltio_mem.clear();
             return fail(dev, MP_ERR_HIP, "LT sample scratch allocation failed");
@@ -2044,7 +2111,8 @@ int mp_hip_lt_sample(mp_dev *dev, const float *hidden, float temperature, int to
     io.ignore_eos = forbid_eos != 0;
     // step: a call counter >= 4 (so only forbid_eos masks EOS), also the draw's step index
     const int step = 4 + dev->lt_calls++;
-    mp::SmpCfg cfg{temperature, top_k, (unsigned long long)seed, -1, {-1}};
+    mp::SmpCfg cfg{temperature, top_k, (unsigned long long)seed, -1, {-1}, 0.f, {}};
+    for (int &pb : cfg.partner) pb = -1;
     HIPCHK(hipMemcpyAsync(io.hidden, hidden, 768 * 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(io.step, &step, 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(io.cfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
@@ -2062,6 +2130,15 @@ int mp_hip_get_trace(mp_dev *dev, float *hidden) {
     if (!dev || !hidden) return MP_ERR_ARG;
     if (!dev->trace) return fail(dev, MP_ERR_STATE, "trace_hidden was not enabled");
     HIPCHK(hipMemcpy(hidden, dev->trace, (size_t)dev->B * (dev->max_steps + 1) * 768 * 4, hipMemcpyDeviceToHost));
+    return MP_OK;
+}
+
+int mp_hip_get_trace_uncond(mp_dev *dev, float *hidden) {
+    if (!dev || !hidden) return MP_ERR_ARG;
+    if (!dev->trace) return fail(dev, MP_ERR_STATE, "trace_hidden was not enabled");
+    if (!dev->guided) return fail(dev, MP_ERR_STATE, "the batch was not begun under guidance (mp_hip_set_cfg)");
+    const size_t n = (size_t)dev->B * (dev->max_steps + 1) * 768;  // slots B .. 2B-1 follow the conditional ones
+    HIPCHK(hipMemcpy(hidden, dev->trace + n, n * 4, hipMemcpyDeviceToHost));
     return MP_OK;
 }
 

@@ -116,12 +116,15 @@ SYMBOLS = [
     ("mp_hip_codec_stream_reset", _I, [_P, _I]),
     ("mp_hip_codec_stream_free", None, [_P]),
     ("mp_hip_set_stream_codec_mode", _I, [_P, _I]),
+    ("mp_hip_set_cfg", _I, [_P, ctypes.c_float]),
+    ("mp_hip_get_trace_uncond", _I, [_P, _P]),
 ]
 
 # entry points added after round 4: absent from the A/B baseline libraries
 OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue", "mp_hip_codec_stream_create", "mp_hip_codec_stream_decode",
             "mp_hip_codec_stream_reset", "mp_hip_codec_stream_free", "mp_hip_set_stream_codec_mode",
-            "mp_hip_codec_stream_decode_ragged", "mp_hip_decode_queue_stream"}
+            "mp_hip_codec_stream_decode_ragged", "mp_hip_decode_queue_stream", "mp_hip_set_cfg",
+            "mp_hip_get_trace_uncond"}
 
 _lib = None
 
@@ -208,6 +211,8 @@ class SynthResult:
     decode_ms: float
     iterations: int
     hidden: Optional[np.ndarray] = None  # [B][max_steps+1][768] when traced
+    # the same of the unconditional branches, when traced under guidance (Device.set_cfg)
+    hidden_uncond: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -267,6 +272,17 @@ class Device:
         self._check(self.lib.mp_hip_set_kv_mode(self.h, self.KV_MODES[kv]))
         self.xa = xa
         self._check(self.lib.mp_hip_set_xa_mode(self.h, self.XA_MODES[xa]))
+        self.cfg_scale = 0.0
+
+    def set_cfg(self, scale: float) -> None:
+        """mp_hip_set_cfg: classifier-free guidance from the next begin(); 0 is off. Every
+        utterance then decodes as a pair of slots (conditional, text-free) whose logits are
+        mixed in every code pick, scale * cond + (1 - scale) * uncond, so a batch holds at
+        most max_batch() // 2 utterances. f32 and bf16 weights; the queue calls refuse."""
+        if not hasattr(self.lib, "mp_hip_set_cfg"):
+            raise MagpieError("this libmagpie_hip.so has no classifier-free guidance")
+        self._check(self.lib.mp_hip_set_cfg(self.h, float(scale)))
+        self.cfg_scale = float(scale)
 
     def _check(self, rc: int) -> None:
         if rc != MP_OK:
@@ -486,8 +502,12 @@ class Device:
         if trace:
             hidden = np.zeros((B, max_dec_steps + 1, 768), np.float32)
             self._check(self.lib.mp_hip_get_trace(self.h, hidden.ctypes.data))
+        hidden_u = None
+        if trace and self.cfg_scale != 0.0:
+            hidden_u = np.zeros((B, max_dec_steps + 1, 768), np.float32)
+            self._check(self.lib.mp_hip_get_trace_uncond(self.h, hidden_u.ctypes.data))
         return SynthResult([codes[b, :nf[b]].copy() for b in range(B)], nf, tm.preamble_ms, tm.decode_ms,
-                           tm.iterations, hidden)
+                           tm.iterations, hidden, hidden_u)
 
     def encode_text(self, tokens) -> np.ndarray:
         """mp_hip_encode_text (magpie_encode_text, magpie.cpp:2284-2374): the text encoder

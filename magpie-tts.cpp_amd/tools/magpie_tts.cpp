@@ -27,6 +27,8 @@ void usage(const char *prog) {
             "  --temp FLOAT         sampling temperature (default: 0.7, 0 = greedy)\n"
             "  --top-k INT          top-k sampling (default: 80)\n"
             "  --seed N             sampling stream seed (default: 0)\n"
+            "  --cfg-scale S        classifier-free guidance scale (default: 0 = off; the model's\n"
+            "                       published setting is 2.5; f32 and bf16 weights)\n"
             "  --stream             sentence-chunked streaming synthesis (4-frame codec chunks)\n"
             "  --continuous-codec   codec chunks carry their conv state: seamless across chunks\n"
             "  --bf16               bf16 decode projections (MFMA)\n"
@@ -77,7 +79,7 @@ int main(int argc, char **argv) {
     const char *model = "weights/magpie-357m-f32.gguf", *codec_path = "weights/nano-codec-f32.gguf";
     const char *text = nullptr, *out = "output.wav";
     int speaker = 0, top_k = 80;
-    float temp = 0.7f;
+    float temp = 0.7f, cfg_scale = 0.f;
     unsigned long long seed = 0;
     bool quiet = false, stream = false, bf16 = false, continuous = false;
     for (int i = 1; i < argc; ++i) {
@@ -98,6 +100,7 @@ int main(int argc, char **argv) {
         else if (a == "--temp") temp = (float)atof(val("--temp"));
         else if (a == "--top-k") top_k = atoi(val("--top-k"));
         else if (a == "--seed") seed = strtoull(val("--seed"), nullptr, 10);
+        else if (a == "--cfg-scale") cfg_scale = (float)atof(val("--cfg-scale"));
         else if (a == "--stream") stream = true;
         else if (a == "--continuous-codec") continuous = true;
         else if (a == "--bf16") bf16 = true;
@@ -124,6 +127,7 @@ int main(int argc, char **argv) {
     ctx->speaker_id = speaker;
     ctx->seed = seed;
     ctx->continuous_codec = continuous;
+    ctx->cfg_scale = cfg_scale;
     magpie_codec *codec = magpie_codec_init(codec_path);
     if (!codec) {
         fprintf(stderr, "Error: Failed to load codec from %s\n", codec_path);
