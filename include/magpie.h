@@ -140,10 +140,23 @@ struct magpie_context {
     // and max_parallel_sentences are capped at half of mp_hip_max_batch. f32 and bf16 weights
     // only; the two *_queue calls return their failure value under guidance.
     float cfg_scale;
+    // added: the attention prior (mp_hip_set_attn_prior, magpie_hip.h). attn_prior_eps 0
+    // (default) = off, nothing changes; else in (0, 1]: the weight of a text position outside
+    // the window [a - 1, a + attn_prior_lookahead] around the attended position a, from frame
+    // attn_prior_start on, in the decoder layers of attn_prior_layers (bit l; 0 = all). Honoured
+    // by the calls that honour cfg_scale; f32 and bf16 weights only, the two *_queue calls return
+    // their failure value. magpie_get_alignment reads the attended positions back.
+    float attn_prior_eps;
+    int attn_prior_lookahead, attn_prior_start;
+    uint32_t attn_prior_layers;
     magpie_context()
         : n_threads(4), temperature(0.7f), top_k(80), speaker_id(0), codec(nullptr), seed(0),
-          max_parallel_sentences(8), continuous_codec(false), cfg_scale(0.f) {}
+          max_parallel_sentences(8), continuous_codec(false), cfg_scale(0.f),
+          attn_prior_eps(0.f), attn_prior_lookahead(5), attn_prior_start(0), attn_prior_layers(0) {}
 };
+// added: the attended text position of every frame of the last batch decoded with the attention
+// prior, utterance b's row at att[b * rows] (valid for f < its frame count); false without one
+bool magpie_get_alignment(magpie_context *ctx, std::vector<int32_t> &att, int *rows);
 
 // magpie.h:310-313
 struct magpie_sample_result {

@@ -153,6 +153,60 @@ int mp_hip_set_kv_mode(mp_dev *dev, int kv_mode);
  *     would have to install a pair into two slots (a follow-up).
  * mp_hip_lt_sample is not affected. */
 int mp_hip_set_cfg(mp_dev *dev, float scale);
+/* Attention prior: monotonic cross-attention (XA) guidance, with the alignment out. It
+ * follows the shape of the model's published attention prior but is this library's own
+ * definition (that source is not available here). NULL is off (the default); applied from
+ * the next mp_hip_begin_batch.
+ *
+ * Each utterance starts with the attended position a = 0 and a log-prior row lp[t] = 0,
+ * t < T. For decode frame f = 0, 1, ... (row f of mp_hip_get_trace; the 110-frame prefill
+ * never takes a prior):
+ *  1. in every layer l of `layers` the XA softmax runs over
+ *       score_l[t] = (q . K_t) / sqrt(128) + lp[t]
+ *     (reassociated form: (K'_t . LN(x)) * scale, then + lp[t]); the add is a separate f32
+ *     add. Layers outside the mask compute what they compute without a prior;
+ *  2. p_l = softmax_t(score_l) of the masked layers, avg[t] = sum_l p_l[t], l ascending;
+ *  3. a' = the first index of the maximum of avg over a <= t <= min(a + W, T - 1): the
+ *     position never moves back and never jumps more than W;
+ *  4. att[f] = a' for every frame a live slot computes, its stopping frame included, so
+ *     rows f < n_frames of mp_hip_get_alignment are valid. Only if the slot advances in the
+ *     iteration (it was not done and its finalize does not stop it): a = a', and the next
+ *     frame's row is lp[t] = 0 for max(a' - 1, 0) <= t <= min(a' + W, T - 1) and L elsewhere,
+ *     L = (float)log((double)epsilon), computed once on the host; all zeros while
+ *     f + 1 < start_step. A slot that stops or is frozen keeps a and lp: its recomputed last
+ *     frame reproduces the same bits (and rewrites the same att entry);
+ *  5. epsilon = 1 (L = 0) and T <= W + 2 (every position inside the window) leave lp = 0:
+ *     codes and hidden states are the plain run's bit for bit, the alignment is still
+ *     reported;
+ *  6. under guidance (mp_hip_set_cfg) the prior and the vote belong to the conditional
+ *     slot; the text-free partner's lp stays zero and it casts no vote (its XA adds a zero
+ *     vector whatever its weights). Padding slots never update.
+ * The settings live in device memory (one captured graph serves any of them); whether a
+ * batch runs with a prior at all is part of its launch list: the O-projection + XA launch
+ * takes its PRIOR form and xa_align_kernel follows the finalize. Without a prior no launch,
+ * kernel or list changes.
+ *
+ * Runs with f32 (as stored) and bf16 weights, either XA form, either SA cache type, every
+ * batch size of those modes, mp_hip_decode and mp_hip_decode_stream. Refused, before
+ * anything runs and leaving the device usable:
+ *   - MP_ERR_UNSUPPORTED from mp_hip_begin_batch in the F16 and Q8_0 / Q4_0 weight modes,
+ *     and when `layers` selects more than 12 layers;
+ *   - MP_ERR_UNSUPPORTED from mp_hip_decode_queue and mp_hip_decode_queue_stream: a refill
+ *     would have to reset a and lp in the slot install (a follow-up, with the pair install);
+ *   - MP_ERR_ARG for an epsilon outside (0, 1] or not finite, a negative lookahead or a
+ *     negative start_step. */
+typedef struct mp_attn_prior {
+    float epsilon;     /* weight of a text position outside the window, 0 < epsilon <= 1 */
+    int lookahead;     /* W >= 0: the window reaches W tokens past the attended position */
+    int start_step;    /* first frame (mp_hip_get_trace row, BOS frame = 0) whose XA takes a prior; >= 0 */
+    uint32_t layers;   /* bit l: decoder layer l takes the prior and votes on the alignment; 0 = all */
+} mp_attn_prior;
+int mp_hip_set_attn_prior(mp_dev *dev, const mp_attn_prior *prior);
+/* att [B][max_dec_steps + 1] of the last decoded batch begun with a prior: the attended text
+ * position of every frame, rows valid for f < n_frames. MP_ERR_STATE without a prior. */
+int mp_hip_get_alignment(mp_dev *dev, int32_t *att);
+/* the shape of that array: B utterances, rows = max_dec_steps + 1. MP_ERR_STATE without a prior. */
+int mp_hip_alignment_shape(mp_dev *dev, int *B, int *rows);
 /* Cross-attention form of the decode step, applied from the next mp_hip_begin_batch.
  * REASSOC: x += sum_t softmax_t(K'_t . LN(x)) V'_t with K' = W_q^T K, V' = W_o V
  * precomputed per utterance (reads 6 KB per text token and layer; fused into the

@@ -92,10 +92,24 @@ void magpie_free(magpie_context *ctx) {
 const char *magpie_get_backend_name(magpie_context *ctx) { return ctx && ctx->model.dev ? "HIP (gfx950)" : "none"; }
 
 // ctx->cfg_scale to the device, ahead of every begin_batch / queue call (mp_hip_set_cfg)
+// and the attention prior's fields (mp_hip_set_attn_prior; attn_prior_eps 0: off)
 static bool apply_cfg(const magpie_context *ctx) {
-    if (mp_hip_set_cfg(ctx->model.dev, ctx->cfg_scale) == MP_OK) return true;
-    fprintf(stderr, "magpie: cfg_scale must be finite\n");
+    if (mp_hip_set_cfg(ctx->model.dev, ctx->cfg_scale) != MP_OK) {
+        fprintf(stderr, "magpie: cfg_scale must be finite\n");
+        return false;
+    }
+    const mp_attn_prior pr{ctx->attn_prior_eps, ctx->attn_prior_lookahead, ctx->attn_prior_start, ctx->attn_prior_layers};
+    if (mp_hip_set_attn_prior(ctx->model.dev, ctx->attn_prior_eps == 0.f ? nullptr : &pr) == MP_OK) return true;
+    fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));
     return false;
+}
+
+bool magpie_get_alignment(magpie_context *ctx, std::vector<int32_t> &att, int *rows) {
+    int B = 0, R = 0;
+    if (!ctx || !ctx->model.dev || mp_hip_alignment_shape(ctx->model.dev, &B, &R) != MP_OK) return false;
+    att.assign((size_t)B * R, 0);
+    if (rows) *rows = R;
+    return mp_hip_get_alignment(ctx->model.dev, att.data()) == MP_OK;
 }
 
 static mp_params params_of(const magpie_context *ctx) {

@@ -49,10 +49,10 @@ __global__ __launch_bounds__(MP_BLOCK) void gemv_kernel(const float *W, const fl
     p.W = W; p.src = src; p.lnw = lnw; p.part = part; p.addsrc = addsrc; p.ts = ts; p.src_ld = src_ld;
     p.N = (int)(nn & 0xffffu); p.nrow_blocks = (int)(nn >> 16);
     const unsigned long long t_start = ts_begin(p.ts);
-    if constexpr (EPI == EPI_RESID_XA) {
+    if constexpr (epi_xa(EPI)) {
         // the launch's last XA_SPLITS x NB workgroups: cross-attention on this launch's x1
         if (__builtin_expect((int)blockIdx.x >= p.nrow_blocks, 0)) {  // laid out behind the rows' path
-            xa_tail(p, t_start);
+            xa_tail<EPI == EPI_RESID_XAP>(p, t_start);
             return;
         }
     }
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(MP_BLOCK) void gemv_kernel(const float *W, const fl
         if (lane < RW * NB && nq < p.N) eop = epi_operand<EPI>(p, nq, lane % NB);
     }
     if constexpr (PRE || epi_has_operand<EPI>()) __builtin_amdgcn_sched_barrier(0);
-    if constexpr (EPI != EPI_RESID_XA && EPI != EPI_QKV_SA) ts_phase<1>(p.ts, 0);  // profiling: weights issued
+    if constexpr (!epi_xa(EPI) && EPI != EPI_QKV_SA) ts_phase<1>(p.ts, 0);  // profiling: weights issued
     float acc[RW][NB];
 #pragma unroll
     for (int hh = 0; hh < NB / NBS; ++hh) {
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(MP_BLOCK) void gemv_kernel(const float *W, const fl
             ph.src = p.src + (size_t)hh * NBS * p.src_ld;
             prologue<NBS, K, PRO>(ph, act, red, sc);
         }
-        if constexpr (EPI != EPI_RESID_XA && EPI != EPI_QKV_SA) ts_phase<2>(p.ts, 0);  // profiling: prologue done
+        if constexpr (!epi_xa(EPI) && EPI != EPI_QKV_SA) ts_phase<2>(p.ts, 0);  // profiling: prologue done
         // every (row, slot) partial first, then their wave sums advanced together
         // (wave_sum_n: each total is wave_sum's, same tree and order)
         float sv[RW * NBS];
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(MP_BLOCK) void gemv_kernel(const float *W, const fl
     // acc[][] is wave-uniform: lane r*NB + b owns output (row0 + r, slot b), so the
     // epilogue (GELU, KV append, residual) runs on RW*NB lanes in parallel.
     static_assert(RW * NB <= 64, "one lane per output");
-    if constexpr (EPI != EPI_RESID_XA && EPI != EPI_QKV_SA) ts_phase<3>(p.ts, 0);  // profiling: dot products
+    if constexpr (!epi_xa(EPI) && EPI != EPI_QKV_SA) ts_phase<3>(p.ts, 0);  // profiling: dot products
     float v = 0.f;
 #pragma unroll
     for (int r = 0; r < RW; ++r)
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(MP_BLOCK) void gemv_kernel(const float *W, const fl
     if (lane >= RW * NB) return;
     const int b = lane % NB, n = row0 + lane / NB;
     if (n >= p.N) return;
-    if constexpr (EPI == EPI_RESID_XA) {
+    if constexpr (epi_xa(EPI)) {
         publish_x1_op(p, v, n, b, eop);
     } else if constexpr (EPI == EPI_QKV_SA) {
         publish_qkv(p, v, n, b);
@@ -200,6 +200,98 @@ __global__ __launch_bounds__(XA_THREADS) void xa_part_kernel(XaP p) {
 hipError_t op_xa(const XaP &p, int B, hipStream_t s) {
     if (!p.x || !p.part || !p.lnw || !p.kp || !p.vp || !p.T || p.Tmax < 1 || p.Tmax > TMAX_LIMIT) return hipErrorInvalidValue;
     mp::launch(xa_part_kernel, dim3(XA_SPLITS, B), dim3(XA_THREADS), 0, s, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- attention prior: alignment
+// The last launch of an iteration built with the attention prior (magpie_hip.h), behind
+// lt_finalize_kernel: one workgroup of 4 waves per slot. The masked layers' score rows of the
+// frame (xa_part<.., PRIOR> / xa_text_attention_q<PRIOR>) go to LDS, wave w reducing rows
+// w, w + 4, ... to their maximum and softmax denominator (the DPP wave reductions); one
+// thread per window position then sums p_l[t] over the layers in ascending order, the
+// first maximum over the window a <= t <= min(a + W, T - 1) is a'. att_out[f] = a' for the
+// frame f the slot computed (a stopped slot recomputes its last frame with the same row, so
+// it rewrites the same value); a and the next frame's row move only when the finalize let
+// the slot advance (done still 0). Only the slot's own T, step and window decide the work.
+constexpr int ALIGN_THREADS = 256;
+__global__ __launch_bounds__(ALIGN_THREADS) void xa_align_kernel(AlignP p) {
+    __shared__ float rows[PRIOR_MAX_LAYERS][TMAX_LIMIT];
+    __shared__ float lm[PRIOR_MAX_LAYERS], ld[PRIOR_MAX_LAYERS];
+    __shared__ float bv[ALIGN_THREADS / 64];
+    __shared__ int bi[ALIGN_THREADS / 64];
+    const unsigned long long t_start = ts_begin(p.ts);
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int pb = b < p.nlive ? p.smp->partner[b] : -1;
+    const bool done = p.done[b] != 0;
+    const int st = p.step[b];
+    const int f = min(done ? st : st - 1, p.max_steps - 1);  // the frame this iteration computed
+    // padding; a text-free partner (no vote, its row stays zero); nothing computed yet
+    if (b >= p.nlive || (pb >= 0 && pb < b) || f < 0) {
+        ts_end(p.ts, t_start);  // profiling: these workgroups stamp their end too
+        return;
+    }
+    const PriorCfg c = *p.pr.cfg;
+    const int T = min(p.T[b], p.Tmax), a = min(max(p.att_pos[b], 0), T - 1);
+    const int hi = min(a + min(c.W, TMAX_LIMIT), T - 1);
+    int nm = 0;
+    for (int l = 0; l < p.nlayers && nm < PRIOR_MAX_LAYERS; ++l) {
+        if (!((c.layers >> l) & 1u)) continue;
+        if ((nm & 3) == w) {
+            const float *s = p.pr.scores + ((size_t)b * p.nlayers + l) * p.Tmax;
+            float mx = -INFINITY;
+            for (int t = lane; t < T; t += 64) {
+                const float v = s[t];
+                rows[nm][t] = v;
+                mx = fmaxf(mx, v);
+            }
+            mx = wave_max(mx);
+            float sum = 0.f;
+            for (int t = lane; t < T; t += 64) sum += expf(rows[nm][t] - mx);  // this lane's own stores
+            sum = wave_sum(sum);
+            if (lane == 0) { lm[nm] = mx; ld[nm] = sum; }
+        }
+        ++nm;
+    }
+    lds_sync();
+    // avg[t] over the window, layers ascending; this thread's first maximum
+    float best = -INFINITY;
+    int bt = a;
+    for (int t = a + tid; t <= hi; t += ALIGN_THREADS) {
+        float avg = 0.f;
+        for (int j = 0; j < nm; ++j) avg += expf(rows[j][t] - lm[j]) / ld[j];
+        if (avg > best) { best = avg; bt = t; }
+    }
+    // the workgroup's first maximum: greater value, or the same value at a lower position
+    const float wbest = wave_max(best);
+    // (a lane's own first maximum is its lowest position; among the lanes holding the wave's
+    // maximum the lowest position wins)
+    int cand = best == wbest ? bt : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) cand = min(cand, __shfl_xor(cand, o));
+    if (lane == 0) { bv[w] = wbest; bi[w] = cand; }
+    lds_sync();
+    float gb = bv[0];
+    int ap = bi[0];
+#pragma unroll
+    for (int q = 1; q < ALIGN_THREADS / 64; ++q)
+        if (bv[q] > gb || (bv[q] == gb && bi[q] < ap)) { gb = bv[q]; ap = bi[q]; }
+    if (tid == 0) p.att_out[(size_t)b * (p.max_steps + 1) + f] = ap;
+    if (!done) {  // the slot advanced: a and the next frame's row
+        if (tid == 0) p.att_pos[b] = ap;
+        const bool primed = f + 1 >= c.start_step;
+        const int lo = max(ap - 1, 0), up = min(ap + min(c.W, TMAX_LIMIT), T - 1);
+        float *lp = p.pr.lp + (size_t)b * p.Tmax;
+        for (int t = tid; t < T; t += ALIGN_THREADS) lp[t] = (!primed || (t >= lo && t <= up)) ? 0.f : c.L;
+    }
+    ts_end(p.ts, t_start);
+}
+// (the masked layers are counted where the mask is set, mp_hip_begin_batch: at most
+// PRIOR_MAX_LAYERS; the kernel stages no row beyond that many whatever the mask holds)
+hipError_t op_xa_align(const AlignP &p, int B, hipStream_t s) {
+    if (!p.pr.cfg || !p.pr.lp || !p.pr.scores || !p.T || !p.step || !p.done || !p.smp || !p.att_pos || !p.att_out ||
+        p.Tmax < 1 || p.Tmax > TMAX_LIMIT || p.nlayers < 1 || p.nlayers > 32 || p.max_steps < 1 || p.nlive < 1 || p.nlive > B)
+        return hipErrorInvalidValue;
+    mp::launch(xa_align_kernel, dim3(B), dim3(ALIGN_THREADS), 0, s, p);
     return hipGetLastError();
 }
 
@@ -353,7 +445,7 @@ static hipError_t launch_gemv(const GemvP &p, hipStream_t s) {
     GemvP q = p;
     q.nrow_blocks = (p.N + rows_per_block - 1) / rows_per_block;
     if (p.N > 0xffff || q.nrow_blocks > 0xffff) return hipErrorInvalidValue;  // nn's two 16-bit halves
-    const int grid = q.nrow_blocks + (EPI == EPI_RESID_XA ? XA_SPLITS * NB : EPI == EPI_QKV_SA ? NH * SA_SPLITS * NB : 0);
+    const int grid = q.nrow_blocks + (epi_xa(EPI) ? XA_SPLITS * NB : EPI == EPI_QKV_SA ? NH * SA_SPLITS * NB : 0);
     mp::launch((gemv_kernel<NB, RW, K, PRO, EPI>), dim3(grid), dim3(MP_BLOCK), 0, s, q.W, q.src, q.lnw, q.part, q.addsrc,
                q.ts, q.src_ld, (unsigned)q.N | (unsigned)q.nrow_blocks << 16, q);
     return hipGetLastError();
@@ -383,6 +475,7 @@ static OpTable make_f32_ops() {
         t.qkv_sa = &launch_gemv<NB, RW_QKV, D, PRO_LN, EPI_QKV_SA>;
         t.oproj = &launch_gemv<NB, 1, D, PRO_SA_MERGE, EPI_RESID>;
         t.oproj_xa = &launch_gemv<NB, 1, D, PRO_SA_MERGE, EPI_RESID_XA>;
+        t.oproj_xap = &launch_gemv<NB, 1, D, PRO_SA_MERGE, EPI_RESID_XAP>;
         t.ff1x = &launch_gemv<NB, RW_FF1, D, PRO_XA_LN, EPI_GELU>;
         // the generic LT steps: a Q8_0 file's F32 LT projections (build_lt's last branch)
         t.lt_a = &launch_gemv<NB, 1, LTD, PRO_LTX_LN, EPI_LTQKV>;

@@ -97,10 +97,10 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_b16_kernel(const unsigned short
     __shared__ __attribute__((aligned(16))) floatx4 part[MP_NWAVES][64];
     __shared__ float red[8];
     __shared__ float sc[SC];
-    if constexpr (EPI == EPI_RESID_XA) {
+    if constexpr (epi_xa(EPI)) {
         // the launch's last XA_SPLITS x NB workgroups: cross-attention on this launch's x1 (mp_xa.hpp)
         if (__builtin_expect((int)blockIdx.x >= p.nrow_blocks, 0)) {  // laid out behind the rows' path
-            xa_tail(p, t_start);
+            xa_tail<EPI == EPI_RESID_XAP>(p, t_start);
             return;
         }
     }
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(MP_BLOCK) void gemm_b16_kernel(const unsigned short
     if (col >= NB) return;
     const int n = rt * 16 + row;
     if (n >= p.N) return;
-    if constexpr (EPI == EPI_RESID_XA) publish_x1_op(p, v, n, col, eop);
+    if constexpr (epi_xa(EPI)) publish_x1_op(p, v, n, col, eop);
     else if constexpr (EPI == EPI_QKV_SA) publish_qkv(p, v, n, col);
     else if constexpr (EPI == EPI_BIAS || EPI == EPI_RESID || EPI == EPI_ADD_STORE) epi_store_op<EPI>(p, v, n, col, eop);
     else epi_store<EPI>(p, v, n, col, EPI == EPI_LTX_ADD ? sc[col * LTD + n] : 0.f);
@@ -386,7 +386,7 @@ static hipError_t launch_b16(const GemvP &p, hipStream_t s) {
     if (KS > 1 && (!p.kgh || !p.iter || !p.hx_err)) return hipErrorInvalidValue;
     GemvP q = p;
     q.nrow_blocks = (p.N + 15) / 16 * KS;  // row workgroups (KS per 16-row tile)
-    const int grid = q.nrow_blocks + (EPI == EPI_RESID_XA ? XA_SPLITS * NB : EPI == EPI_QKV_SA ? NH * SA_SPLITS * NB : 0);
+    const int grid = q.nrow_blocks + (epi_xa(EPI) ? XA_SPLITS * NB : EPI == EPI_QKV_SA ? NH * SA_SPLITS * NB : 0);
     mp::launch((gemm_b16_kernel<NB, K, PRO, EPI, F16, KS>), dim3(grid), dim3(MP_BLOCK), 0, s, q.Wb,
                PRO == PRO_PLAIN_B16 ? (const void *)q.src_b16 : (const void *)q.src, q.lnw, q.part, q.addsrc, q.ts, q.src_ld,
                q.nrow_blocks, q);
@@ -428,6 +428,9 @@ static OpTable make_b16_ops() {
         // 8 and 16 slots: the O-projection + XA launch reads the SA output its split
         // workgroups merged (plain rows), and its XA workgroups merge x2
         if constexpr (NB >= 8) t.oproj_xa_pm = &launch_b16<NB, D, PRO_PLAIN, EPI_RESID_XA, false, OPROJ_KS>;
+        // the attention prior's forms (refused in the F16 mode, whose table leaves them null)
+        t.oproj_xap = &launch_b16<NB, D, PRO_SA_MERGE, EPI_RESID_XAP, false, OPROJ_KS>;
+        if constexpr (NB >= 8) t.oproj_xap_pm = &launch_b16<NB, D, PRO_PLAIN, EPI_RESID_XAP, false, OPROJ_KS>;
         // batch 1: lt_slot_kernel's partial sums merged by the head's prologue
         if constexpr (NB == 1) t.lt_em = &launch_b16<1, LTD, PRO_LTS_MERGE, EPI_BIAS>;
     } else {

@@ -990,7 +990,9 @@ __device__ __forceinline__ void xq8qa_tail(const GemvP &p, float *act, signed ch
 }
 
 // f32 o_net: lane l holds elements 4l..4l+3 of half a row, a wave covers 2 rows
-// per instruction; 64 rows = 4 waves x 8 pairs
+// per instruction; 64 rows = 4 waves x 8 pairs. PRIOR (the attention prior): a masked
+// layer's scores take the slot's lp row, and the slot's first workgroup copies them out
+template <bool PRIOR>
 __global__ __launch_bounds__(MP_BLOCK) void xa_f32_kernel(XaQ8P p) {
     constexpr int RP = XQ8_ROWS / MP_NWAVES / 2;  // row pairs per wave
     __shared__ float pr[TMAX_LIMIT];
@@ -1001,7 +1003,15 @@ __global__ __launch_bounds__(MP_BLOCK) void xa_f32_kernel(XaQ8P p) {
 #pragma unroll
     for (int i = 0; i < RP; ++i) wo[i] = *(const float4 *)(p.wof + (size_t)(r0 + 2 * i + hr) * DXA + d4);
     const size_t kv = ((size_t)(b * p.nlayers + p.layer) * p.Tmax) * DXA;
-    xa_text_attention(p.q + (size_t)b * DXA, p.xak + kv, p.xav + kv, p.T[b], pr, a_s);
+    if constexpr (PRIOR) {
+        const bool on = ((p.prior.cfg->layers >> p.layer) & 1u) != 0;
+        const float *q = p.q + (size_t)b * DXA;
+        xa_text_attention_q<true>([&]() { return q; }, p.xak + kv, p.xav + kv, p.T[b], pr, a_s,
+                                  on ? p.prior.lp + (size_t)b * p.Tmax : nullptr,
+                                  on && blockIdx.x == 0 ? p.prior.scores + ((size_t)b * p.nlayers + p.layer) * p.Tmax : nullptr);
+    } else {
+        xa_text_attention(p.q + (size_t)b * DXA, p.xak + kv, p.xav + kv, p.T[b], pr, a_s);
+    }
     const float4 a4 = *(const float4 *)&a_s[d4];
     float v = 0.f;
 #pragma unroll
@@ -1017,7 +1027,10 @@ __global__ __launch_bounds__(MP_BLOCK) void xa_f32_kernel(XaQ8P p) {
 
 hipError_t op_xa_q8(const XaQ8P &p, int B, hipStream_t s) {
     if (!p.x || !p.x2 || !p.q || !p.xak || !p.xav || !p.T || p.Tmax < 1 || p.Tmax > TMAX_LIMIT) return hipErrorInvalidValue;
-    if (p.wof) mp::launch(xa_f32_kernel, dim3(D / XQ8_ROWS, B), dim3(MP_BLOCK), 0, s, p);
+    if (p.wof && p.prior.cfg) {
+        if (!p.prior.lp || !p.prior.scores) return hipErrorInvalidValue;
+        mp::launch(xa_f32_kernel<true>, dim3(D / XQ8_ROWS, B), dim3(MP_BLOCK), 0, s, p);
+    } else if (p.wof) mp::launch(xa_f32_kernel<false>, dim3(D / XQ8_ROWS, B), dim3(MP_BLOCK), 0, s, p);
     else if (p.wo && p.wod) mp::launch(xa_q8_kernel, dim3(D / XQ8_ROWS, B), dim3(MP_BLOCK), 0, s, p);
     else return hipErrorInvalidValue;
     return hipGetLastError();

@@ -999,12 +999,12 @@ __device__ __forceinline__ void prologue(const GemvP &p, float *act, float *red,
 // the value the epilogue read; epi_store_op / publish_x1_op compute the same expressions.
 template <int EPI>
 constexpr bool epi_has_operand() {
-    return EPI == EPI_BIAS || EPI == EPI_RESID || EPI == EPI_ADD_STORE || EPI == EPI_RESID_XA;
+    return EPI == EPI_BIAS || EPI == EPI_RESID || EPI == EPI_ADD_STORE || epi_xa(EPI);
 }
 template <int EPI>
 __device__ __forceinline__ float epi_operand(const GemvP &p, int n, int b) {
     if constexpr (EPI == EPI_BIAS) return p.bias[n];
-    else if constexpr (EPI == EPI_RESID || EPI == EPI_RESID_XA) return p.resid[(size_t)b * D + n];
+    else if constexpr (EPI == EPI_RESID || epi_xa(EPI)) return p.resid[(size_t)b * D + n];
     else if constexpr (EPI == EPI_ADD_STORE) return p.addsrc[(size_t)b * p.out_ld + n];
     else return 0.f;
 }

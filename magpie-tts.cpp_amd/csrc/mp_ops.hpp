@@ -21,6 +21,8 @@ struct OpTable {
     GemvFn oproj;        // SA split states merged + O-projection + residual
     GemvFn oproj_xa;     // the same + the fused XA in the launch (EPI_RESID_XA)
     GemvFn oproj_xa_pm;  // oproj_xa on an SA output its split workgroups merged (plain rows; bf16, 8 and 16 slots)
+    GemvFn oproj_xap;    // oproj_xa with the attention prior in its XA workgroups (EPI_RESID_XAP; f32 and bf16 modes)
+    GemvFn oproj_xap_pm; // oproj_xa_pm likewise
     GemvFn oproj_xq;     // Q8_0: O-projection + the whole direct Q8_0 XA in the launch (EPI_RESID_XQ8)
     GemvFn xq;           // the direct XA's q_net
     GemvFn ff1;          // LN + FFN up + GELU from a materialised x2 (direct XA, merged XA tail)
@@ -50,6 +52,7 @@ const OpTable &q8_ops(int NB);             // mp_decode_q8.hip
 hipError_t op_sa_attn(const AttnP &, int, hipStream_t);
 hipError_t op_xa(const XaP &, int, hipStream_t);
 hipError_t op_xa_q8(const XaQ8P &, int, hipStream_t);
+hipError_t op_xa_align(const AlignP &, int, hipStream_t);  // the last record of an iteration built with the attention prior
 hipError_t op_finalize(const FinP &, int, hipStream_t);
 hipError_t op_embed(const EmbP &, int, hipStream_t);
 hipError_t op_slot_install(const InstallP &, hipStream_t);  // between two replays, never in the iteration's list

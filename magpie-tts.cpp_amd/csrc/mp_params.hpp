@@ -85,6 +85,37 @@ enum Epi {
                         // workgroups compute the cross-attention's q = Q8(q_net) LN(x1) and hand it on
                         // as granules, and XQ8A x NB workgroups the attention + o_net: x2 (direct
                         // Q8_0 XA, xa_q8_kernel's arithmetic)
+    EPI_RESID_XAP = 14, // EPI_RESID_XA whose XA workgroups add the attention prior's row to the scores
+                        // and store them (xa_part<.., PRIOR>); the O-projection's own path is the same
+};
+constexpr bool epi_xa(int epi) { return epi == EPI_RESID_XA || epi == EPI_RESID_XAP; }
+
+// Attention prior (mp_hip_set_attn_prior, include/magpie_hip.h): the settings, device-resident
+// like SmpCfg, so a captured graph serves any of them; whether a batch runs with a prior at
+// all is baked into its launch list.
+constexpr int PRIOR_MAX_LAYERS = 12;  // masked layers whose score rows xa_align_kernel stages in LDS
+struct PriorCfg {
+    float L;             // (float)log((double)epsilon): the log-prior outside the window
+    int W;               // lookahead
+    int start_step;      // first frame that takes a prior
+    unsigned layers;     // bit l: decoder layer l takes the prior and votes (never 0 here)
+};
+// Per-batch attention-prior state of the XA kernels (all null: no prior)
+struct PriorP {
+    const PriorCfg *cfg;
+    float *lp;           // [NB][Tmax] the frame's log-prior row of every slot (xa_align_kernel writes the next)
+    float *scores;       // [NB][L][Tmax] every masked layer's final scores (xa_align_kernel's input)
+};
+// xa_align_kernel: the alignment vote, the attended position and the next frame's row
+struct SmpCfg;
+struct AlignP {
+    PriorP pr;           // scores read, lp written
+    const int *T, *step, *done;
+    const SmpCfg *smp;   // partner[]: an unconditional slot (partner below it) casts no vote
+    int *att_pos;        // [NB] attended position a
+    int *att_out;        // [NB][max_steps + 1] a' of every frame
+    int Tmax, nlayers, max_steps, nlive;  // nlive: slots behind it are padding
+    unsigned long long *ts;
 };
 
 // Temperature / top-k sampling (sample_top_k, magpie.cpp:1072-1109). Off when
@@ -251,6 +282,7 @@ struct XaP {
     // plain rows)
     float *x2;
     unsigned long long *gh;
+    PriorP prior;          // xa_part<.., PRIOR> only
 };
 
 // Cross-attention with Q8_0 q_net / o_net (weight mode MP_WEIGHTS_Q8) after the
@@ -275,6 +307,7 @@ struct XaQ8P {
     float eps;
     unsigned long long *qg;         // [B][128] {tag, value} granules of q
     int qin;                        // 1: q computed in the attention workgroups (no q granules)
+    PriorP prior;                   // xa_f32_kernel<PRIOR> only (the Q8_0 callers pass nothing)
 };
 
 struct AttnP {  // decode self-attention (one query per utterance)

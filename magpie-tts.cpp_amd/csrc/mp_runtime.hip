@@ -47,7 +47,7 @@ static OpTable table_for(int NB, int weight_mode) {
 }
 
 enum OpKind { K_GEMV = 0, K_ATTN = 1, K_FIN = 2, K_XA = 3, K_XAQ8 = 5, K_LTFFN = 6, K_LTMERGE = 7, K_LTPICK = 8,
-              K_LTFFN2 = 10, K_LTKVO = 11, K_LTSLOT = 12, K_LTFRONT = 13, K_LTSLOTQ8 = 14 };
+              K_LTFFN2 = 10, K_LTKVO = 11, K_LTSLOT = 12, K_LTFRONT = 13, K_LTSLOTQ8 = 14, K_ALIGN = 15 };
 // the f32 batch-1 LT front's granules (one zeroed buffer, LtFrontP::gh): in_proj output, vo_0
 constexpr size_t LTFG_TOTAL = 2 * 256;
 // MAGPIE_DUMP_LT: the LT buffers of slot 0 a state record is read from after a launch
@@ -69,6 +69,7 @@ struct OpRec {
     LtFfn2P l2;
     LtFrontP lf3;
     LtSlotQ8P lq8;
+    AlignP al;
     int B;
     double bytes;
     bool add_sa = false;  // the launch also runs the SA (EPI_QKV_SA): its live-cache bytes are added
@@ -140,6 +141,13 @@ struct mp_dev {
     float cfg_scale = 0.f;
     bool guided = false;
     int slots = 0;
+    // mp_hip_set_attn_prior: applies from the next mp_hip_begin_batch. `prior`: the current
+    // batch's launch list carries the PRIOR forms and xa_align_kernel
+    mp_attn_prior prior_set{};
+    bool prior_wanted = false, prior = false;
+    float *lp = nullptr, *xa_scores = nullptr;  // [NB][Tmax], [NB][L][Tmax]
+    int *att_pos = nullptr, *att_out = nullptr;  // [NB], [NB][max_steps + 1]
+    mp::PriorCfg *priorcfg = nullptr;
     mp_params params{};
     int kv_mode = MP_KV_F32;  // mp_hip_set_kv_mode: applies from the next mp_hip_begin_batch
     int xa_mode = MP_XA_AUTO;  // mp_hip_set_xa_mode: likewise
@@ -231,6 +239,10 @@ void free_batch(mp_dev *dev) {
     dev->batch_ready = false;
     dev->B = dev->NB = dev->Tmax = dev->max_steps = dev->slots = 0;
     dev->guided = false;
+    dev->prior = false;
+    dev->lp = dev->xa_scores = nullptr;
+    dev->att_pos = dev->att_out = nullptr;
+    dev->priorcfg = nullptr;
     dev->xa_direct = false;
     dev->kp = dev->vp = nullptr;
     dev->trace = nullptr;  // a batch without a trace must not see (or write) the last one's
@@ -293,7 +305,7 @@ static hipError_t alloc_pre_scratch(mp::DevBlocks &mem, float **const (&p)[8], s
         if (hipError_t e = zero ? mem.get_zeroed(p[i], n[i], *zero) : mem.get(p[i], n[i])) return e;
     return hipSuccess;
 }
-int alloc_batch(mp_dev *dev, int B, bool guided, int Tmax, int max_steps, bool trace) {
+int alloc_batch(mp_dev *dev, int B, bool guided, bool prior, int Tmax, int max_steps, bool trace) {
     free_batch(dev);
     const int slots = guided ? 2 * B : B;
     const int NB = slots <= 1 ? 1 : slots <= 2 ? 2 : slots <= 4 ? 4 : slots <= 8 ? 8 : 16;
@@ -301,6 +313,7 @@ int alloc_batch(mp_dev *dev, int B, bool guided, int Tmax, int max_steps, bool t
     dev->B = B;
     dev->slots = slots;
     dev->guided = guided;
+    dev->prior = prior;
     dev->NB = NB;
     dev->Tmax = Tmax;
     dev->max_steps = max_steps;
@@ -331,6 +344,10 @@ int alloc_batch(mp_dev *dev, int B, bool guided, int Tmax, int max_steps, bool t
     A(ltk, NB * 8 * 256); A(ltv, NB * 8 * 256); A(ltf, NB * 1024); A(logits, NB * 2024);
     A(ltp, (size_t)NB * std::max({mp::LT_FFN_P, mp::LTS_P, mp::LTQ_P}) * 256); G(ltgh, (size_t)NB * std::max(mp::LTS_P, mp::LTQ_P) * 256); G(ltfg, mp::LTFG_TOTAL); G(ltyg, (size_t)NB * 256);
     if (trace) A(trace, (size_t)NB * (max_steps + 1) * D);
+    if (prior) {
+        A(lp, (size_t)NB * Tmax); A(xa_scores, (size_t)NB * L * Tmax); A(att_pos, NB);
+        A(att_out, (size_t)NB * (max_steps + 1)); A(priorcfg, 1);
+    }
     A(T, NB); A(spk, NB); A(pos, NB); A(step, NB); A(done, NB); A(nframes, NB); A(ndone, 4);  // ndone: [done count, iteration, hand-off timeout, -]
     A(argeos, NB); A(amax, NB * 8); A(smpcfg, 1);
     A(codes_cur, NB * 8); A(codes_prev, NB * 8); A(codes_out, (size_t)NB * max_steps * 8); A(tok, (size_t)NB * Tmax);
@@ -674,6 +691,9 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     const bool sampling = dev->params.temperature >= 0.01f;
     const mp::Sampling smp{sampling, dev->smpcfg, dev->argeos, nullptr, dev->guided};
     const Emit e{dev, out, NB, true, mp::LtDumpP{}};
+    // attention prior: the O-projection + XA launch's PRIOR form, the direct XA's, and
+    // xa_align_kernel behind the finalize (begin_batch refused every other mode)
+    const mp::PriorP prior{dev->priorcfg, dev->lp, dev->xa_scores};
     dev->q8dump_n = 0;
     dev->q8dump_index.clear();
     auto base = [&](int l) {
@@ -726,6 +746,7 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
         if (b16 && mp::b16_oproj_ks() > 1) { g.kgh = dev->kgh; set_handoff(g, dev->ndone); }
         mp::XaP xp{dev->x, dev->xa_part, W.norm_xq, m.eps, dev->kp, dev->vp, dev->T, dev->Tmax, l, L};
         xp.q_f16 = m.weight_mode == MP_WEIGHTS_F16;
+        if (dev->prior) xp.prior = prior;
         const double xa_bytes = A * act * (768.0 + 2.0 * 768 * dev->Tmax + mp::XA_SPLITS * mp::XA_PART);
         // direct XA (Q8_0 q_net / o_net, or long texts: mp_hip_set_xa_mode): x2 materialised
         const bool xa_dir = W.xq8 || dev->xa_direct;
@@ -750,10 +771,10 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
                 return rc;
         } else if (xa_in_oproj) {
             // f32: the fused XA rides in the O-projection's launch on a hand-off of x1
-            mp::GemvFn fn = tb.oproj_xa;
+            mp::GemvFn fn = dev->prior ? tb.oproj_xap : tb.oproj_xa;
             if (merge_sa) {  // the SA output merged by its split workgroups: plain rows
                 g.part = nullptr; g.src = dev->sa_out; g.src_ld = 768;
-                fn = tb.oproj_xa_pm;
+                fn = dev->prior ? tb.oproj_xap_pm : tb.oproj_xa_pm;
             }
             if (merge_xa) { xp.x2 = dev->x2; xp.gh = dev->xagh; }  // x2 merged by the XA workgroups
             g.xa = xp; g.xh = dev->xh; set_handoff(g, dev->ndone);
@@ -776,9 +797,11 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
             xq.Tmax = dev->Tmax; xq.layer = l; xq.nlayers = L;
             if (W.xq8) { xq.wo = W.xo8.q; xq.wod = W.xo8.d; }
             else xq.wof = W.xo;
+            if (dev->prior) xq.prior = prior;
             e.add(W.xq8 ? "xa_q8" : "xa_dir", mp::K_XAQ8, &mp::OpRec::xq, xq,
                   Fx * (768.0 * 128) + A * act * (128.0 + 768 * 2 + 2.0 * 128 * dev->Tmax));
         } else if (!xa_in_oproj && !xq8_in_oproj) {
+            // (never with a prior: begin_batch holds that these modes' tables carry oproj_xap)
             // cross-attention, fused (1713-1767, 3513-3519): x2 = x + o_net(attn(q_net(LN(x))))
             e.add("xa", mp::K_XA, &mp::OpRec::x, xp, xa_bytes);
         }
@@ -815,7 +838,13 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     io.amax = dev->amax; io.cfg = dev->smpcfg;
     io.sampling = sampling; io.ignore_eos = dev->params.ignore_eos; io.guided = dev->guided;
     io.emit_eos = dev->params.emit_eos_frame; io.max_steps = dev->max_steps; io.lt_only = false;
-    return build_lt(dev, io, NB, out, true);
+    if (int rc = build_lt(dev, io, NB, out, true)) return rc;
+    if (dev->prior) {
+        mp::AlignP al{prior, dev->T, dev->step, dev->done, dev->smpcfg, dev->att_pos, dev->att_out,
+                      dev->Tmax, L, dev->max_steps, dev->slots, nullptr};
+        e.add("xa_align", mp::K_ALIGN, &mp::OpRec::al, al, A * act * (2.0 * L * dev->Tmax + dev->Tmax)).dump = {};
+    }
+    return MP_OK;
 }
 
 // one record, launched on s
@@ -834,6 +863,7 @@ hipError_t launch_rec(const mp::OpRec &r, hipStream_t s) {
     case mp::K_LTSLOTQ8: return mp::op_lt_slot_q8(r.lq8, r.B, s);
     case mp::K_LTKVO: return mp::op_lt_kvo(r.g, r.B, s);
     case mp::K_FIN: return mp::op_finalize(r.f, r.B, s);
+    case mp::K_ALIGN: return mp::op_xa_align(r.al, r.B, s);
     }
     return hipErrorInvalidValue;
 }
@@ -1174,6 +1204,34 @@ int mp_hip_set_cfg(mp_dev *dev, float scale) {
     return MP_OK;
 }
 
+int mp_hip_set_attn_prior(mp_dev *dev, const mp_attn_prior *prior) {
+    if (!dev) return MP_ERR_ARG;
+    if (!prior) { dev->prior_wanted = false; return MP_OK; }
+    if (!std::isfinite(prior->epsilon) || !(prior->epsilon > 0.f) || prior->epsilon > 1.f || prior->lookahead < 0 ||
+        prior->start_step < 0)
+        return fail(dev, MP_ERR_ARG, "attention prior: epsilon must be in (0, 1], lookahead and start_step >= 0");
+    dev->prior_set = *prior;
+    dev->prior_wanted = true;
+    return MP_OK;
+}
+
+int mp_hip_get_alignment(mp_dev *dev, int32_t *att) {
+    if (!dev || !att) return MP_ERR_ARG;
+    if (!dev->prior || !dev->att_out) return fail(dev, MP_ERR_STATE, "the batch was not begun with an attention prior (mp_hip_set_attn_prior)");
+    HIPCHK(hipSetDevice(dev->device));
+    HIPCHK(hipStreamSynchronize(dev->stream));
+    HIPCHK(hipMemcpy(att, dev->att_out, (size_t)dev->B * (dev->max_steps + 1) * 4, hipMemcpyDeviceToHost));
+    return MP_OK;
+}
+
+int mp_hip_alignment_shape(mp_dev *dev, int *B, int *rows) {
+    if (!dev || !B || !rows) return MP_ERR_ARG;
+    if (!dev->prior || !dev->att_out) return fail(dev, MP_ERR_STATE, "the batch was not begun with an attention prior (mp_hip_set_attn_prior)");
+    *B = dev->B;
+    *rows = dev->max_steps + 1;
+    return MP_OK;
+}
+
 int mp_hip_set_kv_mode(mp_dev *dev, int kv_mode) {
     if (!dev || (kv_mode != MP_KV_F32 && kv_mode != MP_KV_BF16)) return MP_ERR_ARG;
     dev->kv_mode = kv_mode;
@@ -1241,20 +1299,39 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
             return fail(dev, MP_ERR_ARG, "under guidance an utterance takes two slots: B must be 1.." + std::to_string(bmax / 2) +
                                              " (half of mp_hip_max_batch = " + std::to_string(bmax) + ")");
     }
+    // attention prior (mp_hip_set_attn_prior)
+    const bool prior = dev->prior_wanted;
+    unsigned prior_layers = 0;
+    if (prior) {
+        const int wm = dev->m.weight_mode, L = dev->m.dec_layers;
+        if (wm != MP_WEIGHTS_AS_STORED && wm != MP_WEIGHTS_BF16)
+            return fail(dev, MP_ERR_UNSUPPORTED, "the attention prior (mp_hip_set_attn_prior) runs with f32 (as stored) and bf16 weights only, not in the F16 or Q8_0 / Q4_0 modes");
+        const unsigned all = L >= 32 ? 0xffffffffu : (1u << L) - 1u;
+        prior_layers = dev->prior_set.layers ? dev->prior_set.layers & all : all;
+        if (!prior_layers) return fail(dev, MP_ERR_ARG, "attention prior: `layers` selects no decoder layer of this model");
+        if (__builtin_popcount(prior_layers) > mp::PRIOR_MAX_LAYERS)
+            return fail(dev, MP_ERR_UNSUPPORTED, "attention prior: at most 12 layers may take the prior");
+        // every list of these two modes runs the XA in the O-projection's launch or in its
+        // direct form, both of which have a PRIOR kernel; the f32 family stops at 8 slots
+        // (mp_hip_max_batch), so no list falls back to the standalone xa_part_kernel
+        const int slots = guided ? 2 * B : B;
+        if (!mp::table_for(slots <= 1 ? 1 : slots <= 2 ? 2 : slots <= 4 ? 4 : slots <= 8 ? 8 : 16, wm).oproj_xap)
+            return fail(dev, MP_ERR_UNSUPPORTED, "attention prior: no O-projection + XA kernel with a prior at this batch size");
+    }
     int Tmax = 0, max_steps = 0;
     if (int rc = check_params(dev, params, &max_steps)) return rc;
     if (int rc = check_utterances(dev, tokens, n_tokens, speaker, B, tmax, &Tmax)) return rc;
     if (pin_tmax > 0) Tmax = std::max(Tmax, pin_tmax);
     HIPCHK(hipSetDevice(dev->device));
     const bool trace = params->trace_hidden != 0;
-    const bool same = dev->NB > 0 && dev->B == B && dev->guided == guided && dev->Tmax == Tmax && dev->max_steps == max_steps &&
+    const bool same = dev->NB > 0 && dev->B == B && dev->guided == guided && dev->prior == prior && dev->Tmax == Tmax && dev->max_steps == max_steps &&
                       (dev->trace != nullptr) == trace && dev->params.ignore_eos == params->ignore_eos &&
                       (dev->params.temperature >= 0.01f) == (params->temperature >= 0.01f) &&
                       dev->params.emit_eos_frame == params->emit_eos_frame &&
                       dev->kv16 == (dev->kv_mode == MP_KV_BF16) && dev->xa_direct == want_xa_direct(dev, Tmax);
     dev->params = *params;
     if (!same) {
-        if (int rc = alloc_batch(dev, B, guided, Tmax, max_steps, trace)) return rc;
+        if (int rc = alloc_batch(dev, B, guided, prior, Tmax, max_steps, trace)) return rc;
     }
     const int NB = dev->NB, slots = dev->slots;
     auto t0 = std::chrono::steady_clock::now();
@@ -1278,6 +1355,11 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
             for (int b = 0; b < B; ++b) { cfg.partner[b] = B + b; cfg.partner[B + b] = b; cfg.stream[B + b] = cfg.stream[b]; }
         HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
         HIPCHK(hipMemsetAsync(dev->argeos, 0, NB * 4, dev->stream));
+        if (prior) {  // the prior's settings likewise
+            const mp::PriorCfg pc{(float)std::log((double)dev->prior_set.epsilon), std::min(dev->prior_set.lookahead, (int)mp::TMAX_LIMIT),
+                                  dev->prior_set.start_step, prior_layers};
+            HIPCHK(hipMemcpyAsync(dev->priorcfg, &pc, sizeof pc, hipMemcpyHostToDevice, dev->stream));
+        }
     }
     if (int rc = run_preamble(dev, batch_ws(dev))) return rc;
     HIPCHK(hipStreamSynchronize(dev->stream));
@@ -1350,6 +1432,11 @@ int reset_decode_state(mp_dev *dev) {
     HIPCHK(hipMemcpyAsync(dev->codes_prev, h_prev.data(), h_prev.size() * 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemsetAsync(dev->codes_out, 0, (size_t)NB * dev->max_steps * 8 * 4, dev->stream));
     HIPCHK(hipMemsetAsync(dev->argeos, 0, NB * 4, dev->stream));
+    if (dev->prior) {  // every utterance starts at a = 0 with a zero row
+        HIPCHK(hipMemsetAsync(dev->lp, 0, (size_t)NB * dev->Tmax * 4, dev->stream));
+        HIPCHK(hipMemsetAsync(dev->att_pos, 0, NB * 4, dev->stream));
+        HIPCHK(hipMemsetAsync(dev->att_out, 0, (size_t)NB * (dev->max_steps + 1) * 4, dev->stream));
+    }
     // hand-off tags restart with the iteration counter (ndone[1]): no stale tag may match
     for (const auto &g : dev->granules) HIPCHK(hipMemsetAsync(g.first, 0, g.second * 8, dev->stream));
     // the first frame's decoder input (the BOS codes); later frames' by lt_finalize_kernel
@@ -1695,6 +1782,8 @@ static int pool_call(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens
                      mp_queue_stats *stats, const std::function<int(PoolRun &)> &run) {
     if (dev->cfg_scale != 0.f)
         return fail(dev, MP_ERR_UNSUPPORTED, "the slot pool does not run under guidance (mp_hip_set_cfg): a refill would have to install a pair");
+    if (dev->prior_wanted)
+        return fail(dev, MP_ERR_UNSUPPORTED, "the slot pool does not run with an attention prior (mp_hip_set_attn_prior): a refill would have to reset the slot's attended position and prior row");
     const int bmax = mp_hip_max_batch(dev);
     if (!tokens || !n_tokens || !speaker || N < 1 || tmax < 1 || !params)
         return fail(dev, MP_ERR_ARG, "invalid arguments");
@@ -2255,7 +2344,7 @@ int mp_hip_profile_ops_ts(mp_dev *dev, int iters, float *avg_us) {
         for (int i = 0; i < n; ++i) {
             mp::OpRec r = dev->ops[i];
             unsigned long long *t = ts + (size_t)i * per;
-            r.g.ts = t; r.a.ts = t; r.x.ts = t; r.f.ts = t; r.lf.ts = t; r.l2.f.ts = t; r.lf3.l.f.ts = t; r.lq8.ts = t;
+            r.g.ts = t; r.a.ts = t; r.x.ts = t; r.f.ts = t; r.lf.ts = t; r.l2.f.ts = t; r.lf3.l.f.ts = t; r.lq8.ts = t; r.al.ts = t;
             const hipError_t e = launch_rec(r, dev->stream);
             if (e != hipSuccess) { rc = fail(dev, MP_ERR_HIP, std::string("profile launch: ") + hipGetErrorString(e)); break; }
         }

@@ -266,9 +266,10 @@ inline bool gemv_args_ok(const GemvP &p) {
     if constexpr (EPI == EPI_QKV_SA) ok &= qkv_sa_args_ok(p);
     if constexpr (EPI == EPI_LTQKV) ok &= p.lq && p.lk && p.lv;
     if constexpr (EPI == EPI_LTKVO) ok &= p.lk && p.lv && p.N == 2 * LTD;
-    if constexpr (EPI == EPI_RESID_XA)
+    if constexpr (epi_xa(EPI))
         ok &= p.resid && p.xh && p.iter && p.hx_err && p.N == D && p.xa.part && p.xa.lnw && p.xa.kp && p.xa.vp &&
               p.xa.T && p.xa.Tmax >= 1 && p.xa.Tmax <= TMAX_LIMIT;
+    if constexpr (EPI == EPI_RESID_XAP) ok &= p.xa.prior.cfg && p.xa.prior.lp && p.xa.prior.scores;
     if constexpr (EPI == EPI_RESID_XQ8) {
         const XaQ8P &x = p.xq8;
         ok &= p.resid && p.xh && p.iter && p.hx_err && p.N == D && x.qg && x.wq && x.wqd && x.lnw && x.x2 && x.wo &&

@@ -71,9 +71,13 @@ __device__ __forceinline__ void gh_wait_n(const unsigned long long *g, unsigned 
 // score_u = wave_sum(fmaf chain of k . h over the lane's elements) * scale; one
 // rescale c = exp(m - mn) for the round, then the keys' e_u = exp(score_u - mn) added
 // in key order: l = l c + Σ e_u, o = o c + Σ e_u v_u (each term an explicit fmaf).
+// PRIOR (the attention prior, magpie_hip.h): in a masked layer (`on`, wave-uniform)
+// score_u = score_u + lp[u], a separate f32 add, and lane u stores live key u's final score
+// to srow[key] (xa_align_kernel's input); everything behind the scores is the same code.
+template <bool PRIOR>
 __device__ __forceinline__ void xa_round(const float4 (&k)[XA_KPW][XA_V], const float4 (&vv)[XA_KPW][XA_V],
                                          const float4 (&h)[XA_V], float scale, int tb, int t1, float &m, float &l,
-                                         float4 (&o)[XA_V]) {
+                                         float4 (&o)[XA_V], const float (&lp)[XA_KPW], bool on, float *srow) {
 #pragma clang fp contract(off)
     float sv[XA_KPW], mn = m;
 #pragma unroll
@@ -93,7 +97,15 @@ __device__ __forceinline__ void xa_round(const float4 (&k)[XA_KPW][XA_V], const 
     wave_sum_n<XA_KPW>(sv);
 #pragma unroll
     for (int u = 0; u < XA_KPW; ++u) {
-        sv[u] = tb + XA_WAVES * u < t1 ? sv[u] * scale : -INFINITY;
+        if constexpr (PRIOR) {
+            float sc = sv[u] * scale;
+            if (on) sc = sc + lp[u];
+            const bool live = tb + XA_WAVES * u < t1;
+            if (on && live && (int)(threadIdx.x & 63) == u) srow[tb + XA_WAVES * u] = sc;
+            sv[u] = live ? sc : -INFINITY;
+        } else {
+            sv[u] = tb + XA_WAVES * u < t1 ? sv[u] * scale : -INFINITY;
+        }
         mn = fmaxf(mn, sv[u]);
     }
     const float c = expf(m - mn);
@@ -117,7 +129,9 @@ __device__ __forceinline__ void xa_round(const float4 (&k)[XA_KPW][XA_V], const 
 // as {tag, value} granules xh[b][768] (EPI_RESID_XA): every wave sweeps all 768
 // with relaxed agent-scope loads (write-through producer stores, so no fence is
 // needed) until every tag matches, after its K'/V' rows are already in flight.
-template <bool HANDOFF>
+// PRIOR: the wave's lp values of its keys and the layer's mask bit are issued with its first
+// K'/V' rows, ahead of the hand-off poll: no memory round trip is added behind it.
+template <bool HANDOFF, bool PRIOR = false>
 __device__ __forceinline__ void xa_part(const XaP &p, int sp, int b, unsigned long long *xh, unsigned tag, int *err,
                                         int dep, unsigned long long *ts = nullptr, unsigned long long t_start = 0) {
     __shared__ float wm[XA_WAVES], wl[XA_WAVES];
@@ -130,6 +144,14 @@ __device__ __forceinline__ void xa_part(const XaP &p, int sp, int b, unsigned lo
     const size_t base = ((size_t)(b * p.nlayers + p.layer) * p.Tmax) * D;
     const float *Kp = p.kp + base + 4 * lane + dep, *Vp = p.vp + base + 4 * lane;
     float4 k[XA_KPW][XA_V], vv[XA_KPW][XA_V];
+    float lpv[XA_KPW] = {};
+    unsigned pmask = 0;
+    const float *lprow = nullptr;
+    float *srow = nullptr;
+    if constexpr (PRIOR) {
+        lprow = p.prior.lp + (size_t)b * p.Tmax;
+        srow = p.prior.scores + ((size_t)b * p.nlayers + p.layer) * p.Tmax;
+    }
 #pragma unroll
     for (int u = 0; u < XA_KPW; ++u) {
         const int t = t0 + w + XA_WAVES * u;
@@ -139,7 +161,9 @@ __device__ __forceinline__ void xa_part(const XaP &p, int sp, int b, unsigned lo
             k[u][i] = *(const float4 *)(Kp + r + 256 * i);
             vv[u][i] = *(const float4 *)(Vp + r + 256 * i);
         }
+        if constexpr (PRIOR) lpv[u] = lprow[t < t1 ? t : 0];
     }
+    if constexpr (PRIOR) pmask = p.prior.cfg->layers;
     float4 h[XA_V];
     {   // LN(x) (magpie.cpp:3513), every wave for itself (DPP statistics, no barrier)
         float4 x4[XA_V], g4[XA_V];
@@ -204,13 +228,14 @@ __device__ __forceinline__ void xa_part(const XaP &p, int sp, int b, unsigned lo
     float4 o[XA_V];
 #pragma unroll
     for (int i = 0; i < XA_V; ++i) o[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool prior_on = PRIOR && ((pmask >> p.layer) & 1u) != 0;
     for (int tb = t0 + w; tb < t1; tb += XA_WAVES * XA_KPW) {
         // A round's XA_KPW scores first (independent wave reductions the scheduler
         // interleaves), then one online-softmax update for the set (keys past t1 weigh
         // 0). Every rounding is spelled out (contraction off, explicit fmaf in a fixed
         // order), so each instantiation of this body (batch 1 / batched, handed-off /
         // standalone, f32 / 16-bit families) computes the same bits.
-        xa_round(k, vv, h, scale, tb, t1, m, l, o);
+        xa_round<PRIOR>(k, vv, h, scale, tb, t1, m, l, o, lpv, prior_on, srow);
         const int tn = tb + XA_WAVES * XA_KPW;
         if (tn >= t1) break;
 #pragma unroll
@@ -222,6 +247,7 @@ __device__ __forceinline__ void xa_part(const XaP &p, int sp, int b, unsigned lo
                 k[u][i] = *(const float4 *)(Kp + r + 256 * i);
                 vv[u][i] = *(const float4 *)(Vp + r + 256 * i);
             }
+            if constexpr (PRIOR) lpv[u] = lprow[t < t1 ? t : 0];
         }
     }
     ts_phase<2>(ts, t_start);  // profiling: this (first) wave's keys done
@@ -332,9 +358,10 @@ __device__ __forceinline__ void publish_x1_op(const GemvP &p, float v, int n, in
 }
 
 // the launch's XA workgroups (blockIdx.x >= nrow_blocks): split k % XA_SPLITS of slot k / XA_SPLITS
+template <bool PRIOR = false>
 __device__ __forceinline__ void xa_tail(const GemvP &p, unsigned long long t_start) {
     const int k = blockIdx.x - p.nrow_blocks;
-    xa_part<true>(p.xa, k % XA_SPLITS, k / XA_SPLITS, p.xh, (unsigned)p.iter[0] * 64u + p.layer + 1u, p.hx_err,
+    xa_part<true, PRIOR>(p.xa, k % XA_SPLITS, k / XA_SPLITS, p.xh, (unsigned)p.iter[0] * 64u + p.layer + 1u, p.hx_err,
                   ts_dep(t_start), p.ts, t_start);
     if (p.xa.x2) xa_merge_split(p.xa, k % XA_SPLITS, k / XA_SPLITS, p.xh, (unsigned)p.iter[0] * 64u + p.layer + 1u, p.hx_err);
     ts_end(p.ts, t_start);
@@ -354,10 +381,13 @@ __device__ __forceinline__ void xa_tail(const GemvP &p, unsigned long long t_sta
 //     (lane owns dims lane, 64 + lane), the 4 waves' partials summed in order.
 // Branch-free per key (clamped loads, selects), so the DPP and LDS traffic of a round
 // issues back to back.
+// PRIOR (the attention prior): lp non-null (a masked layer) adds lp[t] to key t's score, a
+// separate f32 add, before it is written to pr; srow non-null (the slot's first workgroup)
+// copies the score row out before pass 2 overwrites it (xa_align_kernel's input).
 constexpr int XA_PF_V = 4;  // rounds of 16 value rows issued at entry
-template <typename QF>
+template <bool PRIOR = false, typename QF>
 __device__ __forceinline__ void xa_text_attention_q(QF getq, const float *Kb, const float *Vb, int Tb, float *pr,
-                                                    float *a_s) {
+                                                    float *a_s, const float *lp = nullptr, float *srow = nullptr) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(16))) float pv[MP_NWAVES][DXA];
     __shared__ float wred[2 * MP_NWAVES];
@@ -375,13 +405,17 @@ __device__ __forceinline__ void xa_text_attention_q(QF getq, const float *Kb, co
             v0pf[r][u] = Vb[(size_t)t * DXA + lane];
             v1pf[r][u] = Vb[(size_t)t * DXA + 64 + lane];
         }
+    // the first round's lp value of this lane's key, issued with its K row
+    float lp0 = 0.f;
+    if constexpr (PRIOR)
+        if (lp) lp0 = lp[min(kq, Tb - 1)];
     const float *qp = getq();
     f32x4 q4[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) q4[i] = *(const f32x4 *)(qp + dq + 4 * i);
     const float scale = 1.0f / sqrtf((float)DXA);
     float mx = -INFINITY;
-    auto score = [&](int t, const f32x4 (&k4)[8]) {
+    auto score = [&](int t, const f32x4 (&k4)[8], float lpt) {
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -392,20 +426,28 @@ __device__ __forceinline__ void xa_text_attention_q(QF getq, const float *Kb, co
         }
         s += dpp_mov<0xB1>(s);  // (s0 + s1) + (s2 + s3) in every lane of the quad
         s += dpp_mov<0x4E>(s);
-        const float sv = s * scale;
+        float sv = s * scale;
+        if constexpr (PRIOR)
+            if (lp) sv = sv + lpt;
         if ((lane & 3) == 0 && t < Tb) pr[t] = sv;
         mx = fmaxf(mx, t < Tb ? sv : -INFINITY);
     };
-    score(kq, kpf);
+    score(kq, kpf, lp0);
     for (int t0 = 64; t0 < Tb; t0 += 64) {
         f32x4 k4[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) k4[i] = *(const f32x4 *)(Kb + (size_t)min(t0 + kq, Tb - 1) * DXA + dq + 4 * i);
-        score(t0 + kq, k4);
+        float lpt = 0.f;
+        if constexpr (PRIOR)
+            if (lp) lpt = lp[min(t0 + kq, Tb - 1)];
+        score(t0 + kq, k4, lpt);
     }
     mx = wave_max(mx);
     if (lane == 0) wred[w] = mx;
     lds_sync();
+    if constexpr (PRIOR)
+        if (srow)
+            for (int t = tid; t < Tb; t += MP_BLOCK) srow[t] = pr[t];
     const float M = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
     float l = 0.f;
     for (int t = tid; t < Tb; t += MP_BLOCK) {

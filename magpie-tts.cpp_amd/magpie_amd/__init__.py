@@ -64,6 +64,11 @@ class mp_queue_stats(ctypes.Structure):
 NEXT_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
 DONE_CB = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int, ctypes.c_void_p)
 
+class mp_attn_prior(ctypes.Structure):
+    _fields_ = [("epsilon", ctypes.c_float), ("lookahead", ctypes.c_int), ("start_step", ctypes.c_int),
+                ("layers", ctypes.c_uint32)]
+
+
 # (name, restype, argtypes) of every symbol include/magpie_hip.h declares
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -118,13 +123,17 @@ SYMBOLS = [
     ("mp_hip_set_stream_codec_mode", _I, [_P, _I]),
     ("mp_hip_set_cfg", _I, [_P, ctypes.c_float]),
     ("mp_hip_get_trace_uncond", _I, [_P, _P]),
+    ("mp_hip_set_attn_prior", _I, [_P, ctypes.POINTER(mp_attn_prior)]),
+    ("mp_hip_get_alignment", _I, [_P, _P]),
+    ("mp_hip_alignment_shape", _I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
 ]
 
 # entry points added after round 4: absent from the A/B baseline libraries
 OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue", "mp_hip_codec_stream_create", "mp_hip_codec_stream_decode",
             "mp_hip_codec_stream_reset", "mp_hip_codec_stream_free", "mp_hip_set_stream_codec_mode",
             "mp_hip_codec_stream_decode_ragged", "mp_hip_decode_queue_stream", "mp_hip_set_cfg",
-            "mp_hip_get_trace_uncond"}
+            "mp_hip_get_trace_uncond", "mp_hip_set_attn_prior", "mp_hip_get_alignment",
+            "mp_hip_alignment_shape"}
 
 _lib = None
 
@@ -283,6 +292,31 @@ class Device:
             raise MagpieError("this libmagpie_hip.so has no classifier-free guidance")
         self._check(self.lib.mp_hip_set_cfg(self.h, float(scale)))
         self.cfg_scale = float(scale)
+
+    def set_attn_prior(self, epsilon: Optional[float] = None, lookahead: int = 5, start_step: int = 0,
+                       layers: int = 0) -> None:
+        """mp_hip_set_attn_prior: monotonic cross-attention guidance from the next begin();
+        epsilon None is off. Every masked layer's XA scores take a log-prior row that is 0 in
+        the window [a - 1, a + lookahead] around the attended text position a and
+        log(epsilon) outside it; a follows the layers' averaged attention, never moves back
+        and never jumps more than `lookahead`. layers: bit l = decoder layer l, 0 = all.
+        f32 and bf16 weights; the queue calls refuse. alignment() returns a per frame."""
+        if not hasattr(self.lib, "mp_hip_set_attn_prior"):
+            raise MagpieError("this libmagpie_hip.so has no attention prior")
+        if epsilon is None:
+            self._check(self.lib.mp_hip_set_attn_prior(self.h, None))
+            return
+        p = mp_attn_prior(float(epsilon), int(lookahead), int(start_step), int(layers))
+        self._check(self.lib.mp_hip_set_attn_prior(self.h, ctypes.byref(p)))
+
+    def alignment(self) -> np.ndarray:
+        """mp_hip_get_alignment: att [B][max_dec_steps + 1], the attended text position of
+        every frame of the last decode (rows valid for f < n_frames)."""
+        B, rows = ctypes.c_int(), ctypes.c_int()
+        self._check(self.lib.mp_hip_alignment_shape(self.h, ctypes.byref(B), ctypes.byref(rows)))
+        att = np.zeros((B.value, rows.value), np.int32)
+        self._check(self.lib.mp_hip_get_alignment(self.h, att.ctypes.data))
+        return att
 
     def _check(self, rc: int) -> None:
         if rc != MP_OK:

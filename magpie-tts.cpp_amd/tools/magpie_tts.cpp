@@ -29,6 +29,11 @@ void usage(const char *prog) {
             "  --seed N             sampling stream seed (default: 0)\n"
             "  --cfg-scale S        classifier-free guidance scale (default: 0 = off; the model's\n"
             "                       published setting is 2.5; f32 and bf16 weights)\n"
+            "  --attn-prior-eps E   attention prior: weight of a text position outside the window\n"
+            "                       around the attended one, in (0, 1] (default: 0 = off; f32 and\n"
+            "                       bf16 weights)\n"
+            "  --attn-prior-lookahead W  the window reaches W tokens ahead (default: 5)\n"
+            "  --attn-prior-start N first frame that takes the prior (default: 0)\n"
             "  --stream             sentence-chunked streaming synthesis (4-frame codec chunks)\n"
             "  --continuous-codec   codec chunks carry their conv state: seamless across chunks\n"
             "  --bf16               bf16 decode projections (MFMA)\n"
@@ -79,7 +84,8 @@ int main(int argc, char **argv) {
     const char *model = "weights/magpie-357m-f32.gguf", *codec_path = "weights/nano-codec-f32.gguf";
     const char *text = nullptr, *out = "output.wav";
     int speaker = 0, top_k = 80;
-    float temp = 0.7f, cfg_scale = 0.f;
+    float temp = 0.7f, cfg_scale = 0.f, prior_eps = 0.f;
+    int prior_w = 5, prior_start = 0;
     unsigned long long seed = 0;
     bool quiet = false, stream = false, bf16 = false, continuous = false;
     for (int i = 1; i < argc; ++i) {
@@ -101,6 +107,9 @@ int main(int argc, char **argv) {
         else if (a == "--top-k") top_k = atoi(val("--top-k"));
         else if (a == "--seed") seed = strtoull(val("--seed"), nullptr, 10);
         else if (a == "--cfg-scale") cfg_scale = (float)atof(val("--cfg-scale"));
+        else if (a == "--attn-prior-eps") prior_eps = (float)atof(val("--attn-prior-eps"));
+        else if (a == "--attn-prior-lookahead") prior_w = atoi(val("--attn-prior-lookahead"));
+        else if (a == "--attn-prior-start") prior_start = atoi(val("--attn-prior-start"));
         else if (a == "--stream") stream = true;
         else if (a == "--continuous-codec") continuous = true;
         else if (a == "--bf16") bf16 = true;
@@ -128,6 +137,9 @@ int main(int argc, char **argv) {
     ctx->seed = seed;
     ctx->continuous_codec = continuous;
     ctx->cfg_scale = cfg_scale;
+    ctx->attn_prior_eps = prior_eps;
+    ctx->attn_prior_lookahead = prior_w;
+    ctx->attn_prior_start = prior_start;
     magpie_codec *codec = magpie_codec_init(codec_path);
     if (!codec) {
         fprintf(stderr, "Error: Failed to load codec from %s\n", codec_path);

@@ -3,7 +3,10 @@
 // (wall-clock fps of magpie_synthesize_codes_graph_reuse).
 //
 // usage: mp_bench MODEL.gguf [frames=256] [batch=1] [reps=3] [tokens=64] [weights=f32|bf16] [cfg_scale=0]
+//                 [prior_eps=0] [prior_lookahead=5] [prior_start=0]
 // cfg_scale != 0: classifier-free guidance (mp_hip_set_cfg): `batch` utterances on 2 x batch slots
+// prior_eps != 0: the attention prior (mp_hip_set_attn_prior) on every layer; the per-iteration
+// event-pair times of the O-projection + XA launches, the finalize and xa_align are printed too
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -14,7 +17,7 @@
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s MODEL.gguf [frames] [batch] [reps] [tokens] [f32|bf16] [cfg_scale]\n", argv[0]);
+        fprintf(stderr, "usage: %s MODEL.gguf [frames] [batch] [reps] [tokens] [f32|bf16] [cfg_scale] [prior_eps] [prior_lookahead] [prior_start]\n", argv[0]);
         return 2;
     }
     const int frames = argc > 2 ? atoi(argv[2]) : 256;
@@ -23,10 +26,13 @@ int main(int argc, char **argv) {
     const int T = argc > 5 ? atoi(argv[5]) : 64;
     const int wm = argc > 6 && !strcmp(argv[6], "bf16") ? MP_WEIGHTS_BF16 : MP_WEIGHTS_AS_STORED;
     const float cfg_scale = argc > 7 ? (float)atof(argv[7]) : 0.f;
+    const mp_attn_prior prior{argc > 8 ? (float)atof(argv[8]) : 0.f, argc > 9 ? atoi(argv[9]) : 5,
+                              argc > 10 ? atoi(argv[10]) : 0, 0};
     mp_dev *dev = nullptr;
     if (mp_hip_init(0, &dev) != MP_OK) { fprintf(stderr, "no HIP device\n"); return 1; }
     if (mp_hip_load_model_ex(dev, argv[1], wm) != MP_OK) { fprintf(stderr, "%s\n", mp_hip_error(dev)); return 1; }
     if (mp_hip_set_cfg(dev, cfg_scale) != MP_OK) { fprintf(stderr, "cfg_scale must be finite\n"); return 1; }
+    if (mp_hip_set_attn_prior(dev, prior.epsilon != 0.f ? &prior : nullptr) != MP_OK) { fprintf(stderr, "%s\n", mp_hip_error(dev)); return 1; }
     std::vector<int32_t> tok((size_t)B * T), nt(B, T), spk(B);
     uint64_t s = 1000;
     for (int b = 0; b < B; ++b) {
@@ -55,6 +61,18 @@ int main(int argc, char **argv) {
         printf("rep %d: %d frames, %d iterations, decode %.3f ms (%.1f fps, %.1f iterations/s), wall %.3f ms, preamble %.2f ms\n",
                r, t.frames_total, t.iterations, t.decode_ms, t.frames_total / (t.decode_ms / 1e3),
                t.iterations / (t.decode_ms / 1e3), s_wall * 1e3, t.preamble_ms);
+    }
+    {   // the launches the prior touches, summed over an iteration (mp_hip_profile_ops event pairs)
+        const int n = mp_hip_num_ops(dev);
+        std::vector<float> us(n > 0 ? n : 1);
+        if (mp_hip_profile_ops(dev, 32, us.data()) != MP_OK) { fprintf(stderr, "%s\n", mp_hip_error(dev)); return 1; }
+        for (const char *name : {"oproj_xa", "oproj", "xa_dir", "finalize", "xa_align"}) {
+            double sum = 0.0;
+            int cnt = 0;
+            for (int i = 0; i < n; ++i)
+                if (!strcmp(mp_hip_op_name(dev, i), name)) { sum += us[i]; ++cnt; }
+            if (cnt) printf("op %s: %d launches, %.2f us per iteration\n", name, cnt, sum);
+        }
     }
     mp_hip_free(dev);
     return 0;
