@@ -1,22 +1,18 @@
 """The attention prior on the device (mp_hip_set_attn_prior) against the numpy f64 restatement
-below, built from tests/golden/make_indep.py's Magpie with the semantics of include/magpie_hip.h.
+of tests/attn_prior_cases.py, built from tests/golden/make_indep.py's Magpie with the semantics
+of include/magpie_hip.h.
 The token seeds were chosen on the CPU: the reference's own decisions are no near-ties (asserted
 per case) and the prior changes codes and alignment entries against the plain run."""
 import contextlib
-import os
-import sys
 
 import numpy as np
 import pytest
 
+from attn_prior_cases import EPS, MIN_ALIGN_MARGIN, MIN_MARGIN, mi, restate
+
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import make_indep as mi  # noqa: E402
-
-STEPS, EPS = 12, 0.1
-MIN_MARGIN, MIN_ALIGN_MARGIN = 1e-3, 1e-4  # make_cfg.py's MIN_MARGIN; the alignment's top-1 / top-2 gap
+STEPS = 12
 # (T, XA form, W, start_step, layers) -> token seed
 CASES = [(5, "reassoc", 1, 0, 0, 124), (70, "reassoc", 5, 0, 0, 1), (70, "direct", 5, 2, 0, 2), (70, "reassoc", 5, 0, 2, 20)]
 
@@ -32,56 +28,6 @@ def ma():
 @pytest.fixture(scope="module")
 def model64(small_model):
     return mi.Magpie(small_model)
-
-
-def restate(M, tokens, speaker, max_steps, eps=None, W=0, start=0, layers=0):
-    """Magpie.synthesize with the attention prior (eps None: plain; the alignment is still voted)."""
-    T = len(tokens)
-    mask = layers or (1 << M.n_dec) - 1
-    enc = M.encode(tokens)
-    kvs = [mi.layer_norm(enc, L["lnm"]) @ L["xkv"].T for L in M.dec]
-    xk, xv = [kv[:, :mi.XA_D] for kv in kvs], [kv[:, mi.XA_D:] for kv in kvs]
-    cache = [(np.zeros((mi.CTX_FRAMES + max_steps + 16, mi.D)), np.zeros((mi.CTX_FRAMES + max_steps + 16, mi.D)))
-             for _ in range(M.n_dec)]
-    x = M.baked[speaker].reshape(mi.CTX_FRAMES, mi.D) + M.dec_pos[:mi.CTX_FRAMES]
-    for l in range(M.n_dec):
-        x = M.dec_layer(l, x, 0, cache, xk, xv)
-    Lp = float(np.float32(np.log(float(np.float32(eps))))) if eps is not None else 0.0
-    a, lp, pos, prev = 0, np.zeros(T), mi.CTX_FRAMES, [mi.AUDIO_BOS] * 8
-    frames, hidden, att, margins, amargins = [], [], [], [], []
-    for f in range(max_steps):
-        x = (M.frame_embedding(prev) + M.dec_pos[pos])[None, :]
-        avg = np.zeros(T)
-        for l, L in enumerate(M.dec):  # dec_layer, + lp inside the masked layers' softmax
-            q, k, v = mi.qkv_split(mi.layer_norm(x, L["ln1"]), L["qkv"])
-            cache[l][0][pos], cache[l][1][pos] = k[0], v[0]
-            x = mi.attend(q, cache[l][0][:pos + 1], cache[l][1][:pos + 1], mi.H, pos) @ L["o"].T + x
-            sc = (mi.layer_norm(x, L["lnq"]) @ L["xq"].T) @ xk[l].T / np.sqrt(mi.XA_D)
-            if mask >> l & 1:
-                sc = sc + lp
-                avg = avg + mi.softmax(sc)[0]
-            x = (mi.softmax(sc) @ xv[l]) @ L["xo"].T + x
-            x = mi.conv_ffn(mi.layer_norm(x, L["ln2"]), L["f1"], L["f2"], 1) + x
-        hidden.append(mi.layer_norm(x[0], M.dec_norm))
-        win = avg[a:min(a + W, T - 1) + 1]
-        a2 = a + int(np.argmax(win))
-        att.append(a2)
-        if len(win) >= 2:
-            top = np.sort(win)
-            amargins.append(top[-1] - top[-2])
-        codes, mg, _ = M.lt_sample_all(hidden[-1], forbid_eos=f < 4)
-        margins.append(mg)
-        if any(c == mi.AUDIO_EOS for c in codes):
-            break
-        frames.append(codes)
-        if f + 1 >= max_steps:
-            break
-        prev, pos, a = codes, pos + 1, a2  # the slot advances
-        t = np.arange(T)
-        inside = (t >= max(a - 1, 0)) & (t <= min(a + W, T - 1))
-        lp = np.where(inside | (f + 1 < start), 0.0, Lp)
-    return {"codes": np.array(frames, np.int32).reshape(-1, 8), "hidden": np.array(hidden), "att": np.array(att, np.int32),
-            "margins": np.array(margins), "amargins": np.array(amargins)}
 
 
 @contextlib.contextmanager
