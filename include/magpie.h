@@ -137,7 +137,8 @@ struct magpie_context {
     // 2.5); 0 (default) = off, nothing changes. Honoured by magpie_synthesize_codes*,
     // magpie_synthesize_codes_batch, magpie_synthesize_sentence_streaming and
     // magpie_synthesize_streaming; every utterance then takes two decode slots, so a batch
-    // and max_parallel_sentences are capped at half of mp_hip_max_batch. f32 and bf16 weights
+    // and max_parallel_sentences are capped at half of mp_hip_max_batch (16 of the bf16 mode's
+    // 32 slots, 4 of the f32 mode's 8). f32 and bf16 weights
     // only; the two *_queue calls return their failure value under guidance.
     float cfg_scale;
     // added: the attention prior (mp_hip_set_attn_prior, magpie_hip.h). attn_prior_eps 0

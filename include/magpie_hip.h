@@ -78,8 +78,9 @@ int mp_hip_load_model(mp_dev *dev, const char *gguf_path);
  * as f32 (F16/BF16/Q8_0 tensors are widened at load). BF16 additionally repacks
  * the decode-step projections (decoder qkv/o/ff1/ff2, LT FFN, LT heads) into
  * bf16 (MFMA fragments for the decoder and heads): half the bytes per frame,
- * activations rounded to bf16 like ggml's BF16 mul_mat; batches up to 16
- * (BASELINE configs 3-4). The preamble, cross-attention, LT in_proj and the LT
+ * activations rounded to bf16 like ggml's BF16 mul_mat; batches up to 32
+ * (BASELINE configs 3-4; above 16 slots every weight fragment feeds two 16-column MFMA
+ * tiles, mp_decode_b16.hip), 16 utterances under guidance. The preamble, cross-attention, LT in_proj and the LT
  * layer's attention (through load-time f32 tables, as AS_STORED computes it)
  * stay f32. No reference counterpart (the
  * reference converter writes F32/F16/Q8_0/Q4_0, convert_magpie_to_gguf.py:197-206). */
@@ -231,9 +232,10 @@ int mp_hip_set_xa_mode(mp_dev *dev, int xa_mode);
 #define MP_STREAM_CODEC_CONTINUOUS 1
 int mp_hip_set_stream_codec_mode(mp_dev *dev, int mode);
 int mp_hip_weight_mode(mp_dev *dev);
-/* the largest batch mp_hip_begin_batch accepts for the loaded model: 16 in the
- * bf16 / F16 modes and for a Q8_0 / Q4_0 file whose decode projections are all
- * quantised, else 8 (negative MP_ERR_* without a model) */
+/* the largest batch mp_hip_begin_batch accepts for the loaded model: 32 in the bf16
+ * mode, 16 in the F16 mode and for a Q8_0 / Q4_0 file whose decode projections are
+ * all quantised, else 8 (negative MP_ERR_* without a model). Under guidance
+ * (mp_hip_set_cfg) an utterance takes two slots: half of it, 16 with bf16 weights. */
 int mp_hip_max_batch(mp_dev *dev);
 int mp_hip_model_info(mp_dev *dev, int *dec_layers, int *enc_layers, size_t *weight_bytes);
 /* replaces magpie_free (magpie.cpp:882-910) */
@@ -242,7 +244,7 @@ const char *mp_hip_error(mp_dev *dev);
 
 /* --- synthesis ------------------------------------------------------------ */
 /* Per-utterance preamble for B independent utterances (1 <= B <= mp_hip_max_batch:
- * 16 in the bf16 / F16 modes and for a fully quantised Q8_0 / Q4_0 file, else 8): text encoder
+ * 32 in the bf16 mode, 16 in the F16 mode and for a fully quantised Q8_0 / Q4_0 file, else 8): text encoder
  * (magpie_encode_text, magpie.cpp:2284-2374), cross-attention K/V
  * (magpie.cpp:4098-4136), baked speaker context + 110-frame prefill
  * (magpie.cpp:4138-4238). tokens: [B][tmax] row-major (padding ignored),

@@ -1,5 +1,6 @@
 // Per-frame decode kernels for gfx950 (f32 path, batch NB <= 8 utterances;
-// the F32 FFN convs of a Q8_0 / Q4_0 file also at 16).
+// the F32 FFN convs of a Q8_0 / Q4_0 file also at 16, the bf16 mode's f32 GEMVs at 32
+// as two 16-slot launches).
 //
 // One decode iteration = 12 decoder layers (magpie_build_decoder_layer_gpu_cached,
 // magpie.cpp:3484-3528) + the 8-codebook local transformer
@@ -503,9 +504,40 @@ static OpTable make_f32_ops() {
     }
     return t;
 }
+// 32 slots (bf16 mode): an f32 GEMV of the 16-slot instantiation run as two launches, slots
+// 0..15 and 16..31 (its LDS holds 16 rows). Every pointer the three ops below index by slot
+// is moved 16 slots on for the second; per (row, slot) the arithmetic is the 16-slot
+// kernel's, which is every batch size's.
+static GemvP upper_half(const GemvP &p) {
+    constexpr size_t H = 16;
+    GemvP q = p;
+    if (q.src) q.src += H * p.src_ld;
+    if (q.out) q.out += H * p.out_ld;
+    if (q.hidden_out) q.hidden_out += H * D;
+    if (q.trace) q.trace += H * p.trace_steps * D;
+    if (q.step) q.step += H;
+    if (q.lt_s) q.lt_s += H * 9 * LTD;
+    if (q.ltX) q.ltX += H * LTD;
+    if (q.lk) q.lk += H * NCB * LTD;
+    if (q.lv) q.lv += H * NCB * LTD;
+    return q;
+}
+template <int RW, int K, int PRO, int EPI>
+static hipError_t launch_gemv_halves(const GemvP &p, hipStream_t s) {
+    static_assert((PRO == PRO_LN || PRO == PRO_LTX_LN) && (EPI == EPI_STORE || EPI == EPI_BIAS || EPI == EPI_LTKVO),
+                  "upper_half moves these prologues' and epilogues' per-slot pointers");
+    if (hipError_t e = launch_gemv<16, RW, K, PRO, EPI>(p, s)) return e;
+    return launch_gemv<16, RW, K, PRO, EPI>(upper_half(p), s);
+}
+static OpTable make_f32_ops32() {
+    OpTable t{};
+    t.xq = &launch_gemv_halves<1, D, PRO_LN, EPI_STORE>;
+    t.lt_in0 = &launch_gemv_halves<1, D, PRO_LN, EPI_BIAS>;
+    return t;
+}
 const OpTable &f32_ops(int NB) {
-    static const OpTable t[5] = {make_f32_ops<1>(), make_f32_ops<2>(), make_f32_ops<4>(), make_f32_ops<8>(),
-                                 make_f32_ops<16>()};
+    static const OpTable t[OP_NB_COUNT] = {make_f32_ops<1>(), make_f32_ops<2>(), make_f32_ops<4>(), make_f32_ops<8>(),
+                                           make_f32_ops<16>(), make_f32_ops32()};
     return t[op_nb_index(NB)];
 }
 
@@ -680,7 +712,7 @@ hipError_t op_slot_install(const InstallP &p, hipStream_t s) {
         !p.Tn || !p.spkn || !p.pos || !p.step || !p.done || !p.nframes || !p.argeos || !p.codes_prev || !p.codes_out ||
         !p.ndone || !p.cfg || !p.emb || !p.pos_emb || !p.x)
         return hipErrorInvalidValue;
-    if (p.b < 0 || p.b >= 16 || p.nlayers < 1 || p.T < 1 || p.T > p.Tmax || p.Tmax > TMAX_LIMIT || p.smax_seq < CTX ||
+    if (p.b < 0 || p.b >= 32 || p.nlayers < 1 || p.T < 1 || p.T > p.Tmax || p.Tmax > TMAX_LIMIT || p.smax_seq < CTX ||
         p.max_seq < CTX || (p.cache_row16 != D * 4 / 16 && p.cache_row16 != D * 2 / 16) || p.max_steps < 1 ||
         p.audio_bos < 0 || p.audio_bos >= VCB)
         return hipErrorInvalidValue;
@@ -1170,7 +1202,7 @@ __global__ __launch_bounds__(MP_BLOCK) void lt_slot_kernel(const float *logits, 
 hipError_t op_lt_slot(const LtFfn2P &p, int NB, hipStream_t s) {
     if (!p.f.y || !p.f.lnw || !p.w1h || !p.w2h || !p.f.part || (p.gh && (!p.f.out || !p.iter || !p.hx_err)) || !p.ltX || !p.ltk || !p.ltv ||
         !p.qkvtab || !p.votab || !p.ptab || !p.lt_pos || !p.logits || !p.codes_cur || !p.step || !p.smp.cfg ||
-        !p.smp.argeos || p.cb < 0 || p.cb >= NCB || NB < 1 || NB > 16)
+        !p.smp.argeos || p.cb < 0 || p.cb >= NCB || NB < 1 || NB > 32)
         return hipErrorInvalidValue;
     mp::launch(lt_slot_kernel, dim3(LTS_P, NB), dim3(MP_BLOCK), 0, s, p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts, p.cb,
                smp_flags(p.smp), p);
@@ -1397,6 +1429,7 @@ hipError_t op_lt_kvo(const GemvP &p, int NB, hipStream_t s) {
     case 4: return launch_gemv<4, 1, LTD, PRO_LTX_LN, EPI_LTKVO>(p, s);
     case 8: return launch_gemv<8, 1, LTD, PRO_LTX_LN, EPI_LTKVO>(p, s);
     case 16: return launch_gemv<16, 1, LTD, PRO_LTX_LN, EPI_LTKVO>(p, s);
+    case 32: return launch_gemv_halves<1, LTD, PRO_LTX_LN, EPI_LTKVO>(p, s);
     }
     return hipErrorInvalidValue;
 }

@@ -2,7 +2,7 @@
 //
 // Every fused projection of the decode step (qkv, O, FFN up/down of the 12
 // decoder layers; the LT layer and its 8 output heads) as a skinny GEMM
-//   out[b][n] = sum_k W[n][k] * bf16(act[b][k]),  b < NB <= 16
+//   out[b][n] = sum_k W[n][k] * bf16(act[b][k]),  b < NB <= 16 (bf16: 32, gemm_b16x2_kernel)
 // on v_mfma_f32_16x16x32_bf16: the A operand is a 16-row x 32-k weight
 // fragment, the B operand 32 k x 16 utterance columns (columns >= NB are zero),
 // f32 accumulation. Activations are rounded to bf16 exactly as ggml rounds src1
@@ -408,6 +408,220 @@ constexpr int FF2_KS = MP_FF2_KS;
 constexpr int OPROJ_KS = MP_OPROJ_KS;
 int b16_oproj_ks() { return OPROJ_KS; }
 
+// ---------------------------------------------------------------- 32 slots (bf16)
+// The same skinny GEMM for 32 utterance columns: out[b][n], b < 32, on the weight stream
+// of the 16-column kernel. One workgroup still owns one 16-row tile (or one K slice of
+// it), its four waves split K in four, and every packed weight fragment is loaded once --
+// but each fragment now feeds two v_mfma_f32_16x16x32_bf16 accumulators, columns 0..15 from
+// one B fragment and 16..31 from a second, so the weight bytes per slot halve and one packed
+// copy of the model serves every batch size. A column's arithmetic is gemm_b16_kernel's to
+// the bit: the same fragments in the same order into its accumulator (an MFMA output
+// element depends on its own column of B only), the same ((p0 + p1) + p2) + p3 reduction
+// of the waves' partials, the same KS and slice-order granule merge, the same rounding of
+// the activations. That is why this is two 16x16x32 tiles and not one 32x32x16
+// instruction, whose order over K differs and which would need a second weight layout.
+//
+// LDS: the activation tile is 32 rows x (KL + 8) bf16 (48.5 KiB at KL = 768; all 32 columns
+// are slots, so no zero row), two [4][64] floatx4 partial tiles (8 KiB), and behind them
+// whatever the XA tail of the launch declares: under gfx950's 160 KiB with two workgroups
+// per CU, more than any launch here needs (at most 192 row workgroups + 128 tails).
+// Rows -> LDS: every row load of the thread is in flight before the first conversion,
+// KL / 64 items of 8 elements per thread (12 at KL = 768: 96 VGPRs of f32 rows beside 24
+// of weights) in native vector arrays with every element assigned.
+// Only the prologue / epilogue pairs of the 32-slot list exist (make_b16_ops32).
+template <int K, int PRO, int EPI, int KS = 1>
+__global__ __launch_bounds__(MP_BLOCK) void gemm_b16x2_kernel(const unsigned short *Wb, const void *rows, const float *lnw,
+                                                              const float *addsrc, unsigned long long *ts, int src_ld,
+                                                              int nrow_blocks, GemvP p) {
+    // leading arguments: gemm_b16_kernel's (no split-state pointer: no merging prologue here)
+    p.Wb = Wb; p.lnw = lnw; p.addsrc = addsrc; p.ts = ts; p.src_ld = src_ld; p.nrow_blocks = nrow_blocks;
+    if constexpr (PRO == PRO_PLAIN_B16) p.src_b16 = (const unsigned short *)rows;
+    else p.src = (const float *)rows;
+    const unsigned long long t_start = ts_begin(p.ts);
+    constexpr int NB = 32;
+    static_assert(PRO == PRO_LN || PRO == PRO_PLAIN || PRO == PRO_PLAIN_B16, "the 32-slot list's prologues");
+    static_assert(EPI == EPI_QKV || epi_xa(EPI) || EPI == EPI_RESID || EPI == EPI_GELU_B16 || EPI == EPI_ADD_STORE ||
+                      EPI == EPI_BIAS,
+                  "the 32-slot list's epilogues");
+    static_assert(K % (128 * KS) == 0, "K splits into KS slices of 4 waves x 32-wide chunks");
+    static_assert(KS == 1 || PRO == PRO_PLAIN_B16, "split-K stages 16-bit rows");
+    static_assert(16 % KS == 0 && 2 * KS <= KGH_MAX_KS, "a split workgroup merges 16 / KS rows; two tiles of granules per slice");
+    constexpr int KL = K / KS;  // this workgroup's K slice
+    constexpr int KC = K / 32, KCS = KL / 32, KW = KCS / MP_NWAVES;
+    constexpr int KP = KL + 8;  // padded bf16 row: rows land 16 B apart in the banks
+    constexpr int PT = NB * (KL / 8) / MP_BLOCK;  // 8-element items per thread
+    static_assert(PT * MP_BLOCK == NB * (KL / 8) && PT <= 12, "whole rounds of row items, all in flight");
+    __shared__ __attribute__((aligned(16))) unsigned short actb[NB * KP];
+    __shared__ __attribute__((aligned(16))) floatx4 part[2][MP_NWAVES][64];
+    if constexpr (epi_xa(EPI)) {
+        // the launch's last XA_SPLITS x 32 workgroups: cross-attention on this launch's x1 (mp_xa.hpp)
+        if (__builtin_expect((int)blockIdx.x >= p.nrow_blocks, 0)) {
+            xa_tail<EPI == EPI_RESID_XAP>(p, t_start);
+            return;
+        }
+    }
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int rt = KS == 1 ? (int)blockIdx.x : (int)blockIdx.x / KS, ks = KS == 1 ? 0 : (int)blockIdx.x % KS;
+
+    // the rows' loads ahead of the weight stream (vector loads complete in issue order)
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    constexpr bool LNP = PRO == PRO_LN, PLB = PRO == PRO_PLAIN_B16, PLF = PRO == PRO_PLAIN;
+    PreRows<NB, K, PRO> pre;
+    u32x4 vb[PLB ? PT : 1];
+    f32x4 x0p[PLF ? PT : 1], x1p[PLF ? PT : 1];
+    if constexpr (LNP) pre_load<NB, K, PRO>(p, pre);
+    if constexpr (PLB) {
+        const unsigned short *src = p.src_b16 + ks * KL;
+#pragma unroll
+        for (int u = 0; u < PT; ++u) {
+            const int e = u * MP_BLOCK + tid;
+            vb[u] = *(const u32x4 *)(src + (size_t)(e / (KL / 8)) * p.src_ld + (e % (KL / 8)) * 8);
+        }
+    }
+    if constexpr (PLF) {
+#pragma unroll
+        for (int u = 0; u < PT; ++u) {
+            const int e = u * MP_BLOCK + tid;
+            const float *src = p.src + (size_t)(e / (KL / 8)) * p.src_ld + (e % (KL / 8)) * 8;
+            x0p[u] = *(const f32x4 *)src;
+            x1p[u] = *(const f32x4 *)(src + 4);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // issue order: rows, weights, arithmetic
+
+    // weight fragments of this wave's K slice: each loaded once, used for both column tiles
+    const uint4 *wf = (const uint4 *)p.Wb + ((size_t)rt * KC + ks * KCS + w * KW) * 64 + lane + ts_dep(t_start);
+    uint4 a[KW];
+#pragma unroll
+    for (int i = 0; i < KW; ++i) a[i] = K == LTD ? ld_lt(wf + (size_t)i * 64) : ld_weight(wf + (size_t)i * 64);
+    // this thread's outputs: (row, col) and (row, col + 16); their epilogue operands behind the weights
+    const int col = tid & 15;
+    float eop0 = 0.f, eop1 = 0.f;
+    if constexpr (epi_has_operand<EPI>()) {
+        const int rq = KS == 1 ? tid >> 4 : ks * (16 / KS) + (tid >> 4), nq = rt * 16 + rq;
+        if (nq < p.N && (KS == 1 || tid < (16 / KS) * 16)) {
+            eop0 = epi_operand<EPI>(p, nq, col);
+            eop1 = epi_operand<EPI>(p, nq, col + 16);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // the weight stream is issued before anything the prologue reads
+
+    // activation rows -> bf16 in LDS
+    if constexpr (LNP) {
+        // LN rows rounded straight into the tile: the y values and the conversion of the 16-column kernel
+        ln_finish<NB, K>(p, pre.r, [&](int b, int k, float y) {
+            actb[b * KP + k] = __builtin_bit_cast(unsigned short, (__bf16)y);
+        });
+    } else if constexpr (PLB) {
+#pragma unroll
+        for (int u = 0; u < PT; ++u) {
+            const int e = u * MP_BLOCK + tid;
+            *(u32x4 *)(actb + (e / (KL / 8)) * KP + (e % (KL / 8)) * 8) = vb[u];
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < PT; ++u) {
+            const int e = u * MP_BLOCK + tid;
+            uint4 o;
+            o.x = pk_bf16(x0p[u].x, x0p[u].y);
+            o.y = pk_bf16(x0p[u].z, x0p[u].w);
+            o.z = pk_bf16(x1p[u].x, x1p[u].y);
+            o.w = pk_bf16(x1p[u].z, x1p[u].w);
+            *(uint4 *)(actb + (e / (KL / 8)) * KP + (e % (KL / 8)) * 8) = o;
+        }
+    }
+    lds_sync();
+#ifndef MP_TS_PROBE
+    ts_mark(p.ts, t_start);  // profiling: activation tile staged
+#endif
+
+    floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    const unsigned short *brow = actb + (lane & 15) * KP + 8 * (lane >> 4);
+#pragma unroll
+    for (int i = 0; i < KW; ++i) {
+        const int kc = w * KW + i;
+        const uint4 b0 = *(const uint4 *)(brow + kc * 32), b1 = *(const uint4 *)(brow + 16 * KP + kc * 32);
+        acc0 = mfma16<false>(a[i], b0, acc0);
+        acc1 = mfma16<false>(a[i], b1, acc1);
+    }
+    part[0][w][lane] = acc0;
+    part[1][w][lane] = acc1;
+    lds_sync();
+    // thread t -> row t/16, columns t%16 and t%16 + 16; D[row][c] of a tile sits in lane (row/4)*16 + c, register row%4
+    int row = tid >> 4;
+    float v0, v1;
+    {
+        const int ls = (row >> 2) * 16 + col, rg = row & 3;
+        v0 = ((part[0][0][ls][rg] + part[0][1][ls][rg]) + part[0][2][ls][rg]) + part[0][3][ls][rg];
+        v1 = ((part[1][0][ls][rg] + part[1][1][ls][rg]) + part[1][2][ls][rg]) + part[1][3][ls][rg];
+    }
+    if constexpr (KS > 1) {
+        // publish this slice's two partial tiles (kgh[tile][KS][2][256]) and merge rows
+        // [ks * 16 / KS, (ks + 1) * 16 / KS) of the tile: the KS partials of an output added in
+        // slice order (a bounded sweep; poisoned + HX_ERR_KS if a sibling never publishes)
+        using gu64 = __attribute__((address_space(1))) unsigned long long;
+        const unsigned tag = (unsigned)p.iter[0] * 64u + p.layer + 1u;
+        gu64 *gt = (gu64 *)p.kgh + (size_t)rt * KS * 512;
+        __hip_atomic_store(gt + ks * 512 + tid, ((unsigned long long)tag << 32) | __float_as_uint(v0), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(gt + ks * 512 + 256 + tid, ((unsigned long long)tag << 32) | __float_as_uint(v1), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        constexpr int MR = 16 / KS;
+        if (tid >= MR * 16) return;
+        row = ks * MR + (tid >> 4);
+        const int gi = row * 16 + col;
+        float pv0[KS], pv1[KS];
+        for (unsigned spins = 0;; ++spins) {
+            bool ok = true;
+#pragma unroll
+            for (int s2 = 0; s2 < KS; ++s2) {
+                const unsigned long long u0 = __hip_atomic_load(gt + s2 * 512 + gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned long long u1 = __hip_atomic_load(gt + s2 * 512 + 256 + gi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ok &= (unsigned)(u0 >> 32) == tag && (unsigned)(u1 >> 32) == tag;
+                pv0[s2] = __uint_as_float((unsigned)u0);
+                pv1[s2] = __uint_as_float((unsigned)u1);
+            }
+            if (__all(ok)) break;
+            if (spins >= HX_SPIN_LIMIT) {
+                if ((tid & 63) == 0) __hip_atomic_fetch_or((__attribute__((address_space(1))) int *)p.hx_err, HX_ERR_KS,
+                                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+                for (int s2 = 0; s2 < KS; ++s2) pv0[s2] = pv1[s2] = __builtin_nanf("");
+                break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        v0 = pv0[0];
+        v1 = pv1[0];
+#pragma unroll
+        for (int s2 = 1; s2 < KS; ++s2) { v0 = v0 + pv0[s2]; v1 = v1 + pv1[s2]; }
+    }
+    const int n = rt * 16 + row;
+    if (n >= p.N) return;
+    // the per-(n, col) epilogues of mp_fused.hpp / mp_xa.hpp, once for each of the thread's two columns
+    auto epilogue = [&](float v, int c, float eop) {
+        if constexpr (epi_xa(EPI)) publish_x1_op(p, v, n, c, eop);
+        else if constexpr (EPI == EPI_BIAS || EPI == EPI_RESID || EPI == EPI_ADD_STORE) epi_store_op<EPI>(p, v, n, c, eop);
+        else epi_store<EPI>(p, v, n, c);
+    };
+    epilogue(v0, col, eop0);
+    epilogue(v1, col + 16, eop1);
+    ts_end(p.ts, t_start);
+}
+
+template <int K, int PRO, int EPI, int KS = 1>
+static hipError_t launch_b16x2(const GemvP &p, hipStream_t s) {
+    if (!p.Wb || p.N <= 0 || !gemv_args_ok<PRO, EPI>(p)) return hipErrorInvalidValue;
+    if (KS > 1 && (!p.kgh || !p.iter || !p.hx_err)) return hipErrorInvalidValue;
+    GemvP q = p;
+    q.nrow_blocks = (p.N + 15) / 16 * KS;  // row workgroups (KS per 16-row tile)
+    const int grid = q.nrow_blocks + (epi_xa(EPI) ? XA_SPLITS * 32 : 0);
+    mp::launch((gemm_b16x2_kernel<K, PRO, EPI, KS>), dim3(grid), dim3(MP_BLOCK), 0, s, q.Wb,
+               PRO == PRO_PLAIN_B16 ? (const void *)q.src_b16 : (const void *)q.src, q.lnw, q.addsrc, q.ts, q.src_ld,
+               q.nrow_blocks, q);
+    return hipGetLastError();
+}
+
 // The family's op tables (mp_ops.hpp), bf16 and F16 weights. The bf16 mode runs its local
 // transformer on lt_slot_kernel (mp_decode.hip), so its table holds only the heads of it;
 // the F16 mode runs build_lt's generic steps on this family, the LT in_proj included
@@ -447,12 +661,26 @@ static OpTable make_b16_ops() {
     }
     return t;
 }
+// 32 slots, bf16 only, on gemm_b16x2_kernel: the SA a launch of its own whose split workgroups
+// merge sa_out (plain rows for the O-projection), x2 merged by the XA tails or written by
+// the direct XA (plain LN rows for the FFN-up), the LT heads on y2
+static OpTable make_b16_ops32() {
+    OpTable t{};
+    t.qkv = &launch_b16x2<D, PRO_LN, EPI_QKV>;
+    t.oproj_pm = &launch_b16x2<D, PRO_PLAIN, EPI_RESID>;
+    t.oproj_xa_pm = &launch_b16x2<D, PRO_PLAIN, EPI_RESID_XA>;
+    t.oproj_xap_pm = &launch_b16x2<D, PRO_PLAIN, EPI_RESID_XAP>;
+    t.ff1 = &launch_b16x2<D, PRO_LN, EPI_GELU_B16>;
+    t.ff2 = &launch_b16x2<DFF, PRO_PLAIN_B16, EPI_ADD_STORE, FF2_KS>;
+    t.lt_e = &launch_b16x2<LTD, PRO_PLAIN, EPI_BIAS>;
+    return t;
+}
 const OpTable &b16_ops(int NB, bool f16) {
-    static const OpTable t[2][5] = {
+    static const OpTable t[2][OP_NB_COUNT] = {
         {make_b16_ops<1, false>(), make_b16_ops<2, false>(), make_b16_ops<4, false>(), make_b16_ops<8, false>(),
-         make_b16_ops<16, false>()},
+         make_b16_ops<16, false>(), make_b16_ops32()},
         {make_b16_ops<1, true>(), make_b16_ops<2, true>(), make_b16_ops<4, true>(), make_b16_ops<8, true>(),
-         make_b16_ops<16, true>()}};
+         make_b16_ops<16, true>(), OpTable{}}};  // (F16: no 32-slot kernels, Emit::gemv answers MP_ERR_UNSUPPORTED)
     return t[f16][op_nb_index(NB)];
 }
 

@@ -1082,7 +1082,8 @@ static OpTable make_q8_ops() {
     return t;
 }
 const OpTable &q8_ops(int NB) {
-    static const OpTable t[5] = {make_q8_ops<1>(), make_q8_ops<2>(), make_q8_ops<4>(), make_q8_ops<8>(), make_q8_ops<16>()};
+    static const OpTable t[OP_NB_COUNT] = {make_q8_ops<1>(), make_q8_ops<2>(), make_q8_ops<4>(), make_q8_ops<8>(), make_q8_ops<16>(),
+                                           OpTable{}};  // (32 slots: the bf16 mode only)
     return t[op_nb_index(NB)];
 }
 

@@ -19,6 +19,7 @@ struct OpTable {
     GemvFn qkv;          // LN + QKV + KV append, the SA a launch of its own
     GemvFn qkv_sa;       // the same + the SA in the launch (EPI_QKV_SA)
     GemvFn oproj;        // SA split states merged + O-projection + residual
+    GemvFn oproj_pm;     // oproj on an SA output its split workgroups merged (plain rows; bf16, 32 slots, direct XA)
     GemvFn oproj_xa;     // the same + the fused XA in the launch (EPI_RESID_XA)
     GemvFn oproj_xa_pm;  // oproj_xa on an SA output its split workgroups merged (plain rows; bf16, 8 and 16 slots)
     GemvFn oproj_xap;    // oproj_xa with the attention prior in its XA workgroups (EPI_RESID_XAP; f32 and bf16 modes)
@@ -41,9 +42,11 @@ struct OpTable {
     GemvFn lt_emf;       // the head with lt_ffn_kernel's partial sums merged first (batch 1)
 };
 
-inline int op_nb_index(int NB) { return NB == 1 ? 0 : NB == 2 ? 1 : NB == 4 ? 2 : NB == 8 ? 3 : 4; }
+inline int op_nb_index(int NB) { return NB == 1 ? 0 : NB == 2 ? 1 : NB == 4 ? 2 : NB == 8 ? 3 : NB == 16 ? 4 : 5; }
+constexpr int OP_NB_COUNT = 6;
 
-// The families' tables, NB in {1, 2, 4, 8, 16}; each defined beside its launch_*<> template.
+// The families' tables, NB in {1, 2, 4, 8, 16, 32}; each defined beside its launch_*<> template. 32 slots exist
+// in the bf16 mode only: the F16 and Q8_0 tables are empty there, the f32 one holds what the bf16 list takes from it.
 const OpTable &f32_ops(int NB);            // mp_decode.hip (16 slots: only what another mode's list takes from it)
 const OpTable &b16_ops(int NB, bool f16);  // mp_decode_b16.hip
 const OpTable &q8_ops(int NB);             // mp_decode_q8.hip

@@ -127,7 +127,7 @@ struct SmpCfg {                // device-resident, so a captured graph serves an
     int top_k;                 // 1..VCB
     unsigned long long seed;
     int stream_base;           // the batch's first draw stream (mp_params::stream_base)
-    int stream[16];            // draw stream of slot b: stream_base + b from mp_hip_begin_batch; a slot
+    int stream[32];            // draw stream of slot b: stream_base + b from mp_hip_begin_batch; a slot
                                // refilled by mp_hip_decode_queue carries its utterance's
                                // (slot_install_kernel), so a draw follows the utterance, not the slot
     // Classifier-free guidance (mp_hip_set_cfg). A guided utterance is two slots, the
@@ -135,7 +135,7 @@ struct SmpCfg {                // device-resident, so a captured graph serves an
     // stream[u] = stream[c]. Both pick every code from cfg_mix of their two logit rows
     // (cfg_logit_rows, mp_fused.hpp), so both arrive at the same code. -1: unpaired.
     float cfg_scale;
-    int partner[16];
+    int partner[32];
 };
 struct Sampling {
     int on;                    // temperature >= 0.01 (baked into the captured graph)

@@ -3,8 +3,8 @@
 // Exposes the C-ABI declared in include/magpie_hip.h.
 //
 // Design: one mp_dev per GPU. Weights are uploaded once (f32, one
-// arena). A batch of B utterances (1..8 with f32 weights, 1..16 in the bf16 / F16 /
-// Q8_0 / Q4_0 modes: mp_hip_max_batch) occupies NB = next_pow2(B) slots; every
+// arena). A batch of B utterances (1..8 with f32 weights, 1..32 with bf16 weights, 1..16 in
+// the F16 / Q8_0 / Q4_0 modes: mp_hip_max_batch) occupies NB = next_pow2(B) slots; every
 // per-utterance quantity (residual stream, KV cache, XA K/V, codes, position,
 // done flag) lives in HBM and is addressed by slot, so one decode iteration
 // (12 decoder layers + 8-codebook local transformer + EOS bookkeeping, 65
@@ -45,6 +45,9 @@ static OpTable table_for(int NB, int weight_mode) {
     }
     return t;
 }
+
+// slots of a batch that holds `slots` live ones: the next power of two
+static int slots_nb(int slots) { return slots <= 1 ? 1 : slots <= 2 ? 2 : slots <= 4 ? 4 : slots <= 8 ? 8 : slots <= 16 ? 16 : 32; }
 
 enum OpKind { K_GEMV = 0, K_ATTN = 1, K_FIN = 2, K_XA = 3, K_XAQ8 = 5, K_LTFFN = 6, K_LTMERGE = 7, K_LTPICK = 8,
               K_LTFFN2 = 10, K_LTKVO = 11, K_LTSLOT = 12, K_LTFRONT = 13, K_LTSLOTQ8 = 14, K_ALIGN = 15 };
@@ -174,8 +177,8 @@ struct mp_dev {
     mp::Event sev[2];           // streaming: the two chunk snapshots landed
     mp::Pinned h_codes_pin;     // streaming: pinned mirrors of codes_out and the snapshots (StreamRun's layout)
     float *sa_part = nullptr, *xa_part = nullptr;  // split-K attention states [NB][12][4][68], [NB][4][772]
-    unsigned long long *sagh = nullptr, *xagh = nullptr;  // 16-slot merges: split-state granules
-    unsigned long long *kgh = nullptr;  // split-K FFN-down partial tiles (16-bit modes): [48][KS][256]
+    unsigned long long *sagh = nullptr, *xagh = nullptr;  // 8-, 16- and 32-slot merges: split-state granules
+    unsigned long long *kgh = nullptr;  // split-K FFN-down partial tiles (16-bit modes): [48][KS][256] (32 slots: [48][KS][2][256])
     unsigned long long *xh = nullptr;  // O-projection -> XA hand-off granules [NB][768] (EPI_RESID_XA)
     unsigned long long *qh = nullptr;  // QKV -> SA hand-off granules [NB][2304] (EPI_QKV_SA)
     unsigned long long *xqh = nullptr; // Q8_0 XA q_net -> attention hand-off granules [NB][128] (EPI_RESID_XQ8)
@@ -308,7 +311,7 @@ static hipError_t alloc_pre_scratch(mp::DevBlocks &mem, float **const (&p)[8], s
 int alloc_batch(mp_dev *dev, int B, bool guided, bool prior, int Tmax, int max_steps, bool trace) {
     free_batch(dev);
     const int slots = guided ? 2 * B : B;
-    const int NB = slots <= 1 ? 1 : slots <= 2 ? 2 : slots <= 4 ? 4 : slots <= 8 ? 8 : 16;
+    const int NB = mp::slots_nb(slots);
     const int L = dev->m.dec_layers;
     dev->B = B;
     dev->slots = slots;
@@ -707,12 +710,15 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     // workgroup's prologue (196 / 245 KiB each at 16 slots); the same arithmetic, so
     // batches still reproduce single runs (at 8 slots the SA merge runs in the QKV launch)
     const bool mb16 = m.weight_mode == MP_WEIGHTS_BF16 && !dev->xa_direct;
-    const bool merge_sa = mb16 && (NB >= 16 || (NB == 8 && (split_merge8() & 1)));
+    // 32 slots (bf16 only): the SA a launch of its own, sa_out always merged by its split
+    // workgroups, in the direct XA form too (the 32-column kernel has no merging prologue)
+    const bool merge_sa = (mb16 && (NB >= 16 || (NB == 8 && (split_merge8() & 1)))) || NB == 32;
     const bool merge_xa = mb16 && (NB >= 16 || (NB == 8 && (split_merge8() & 2)));
     // (Q8_0: the same hand-off in the int8 MFMA launch, mp_decode_q8.hip; MAGPIE_Q8_UNFUSED=1
     // keeps the separate launches, which compute the same bits)
     const bool q8_fuse = !q8_unfused();
-    // (at 16 slots too unless MAGPIE_SA16=0, sa16_fused; both forms compute the same bits)
+    // (at 16 slots too unless MAGPIE_SA16=0, sa16_fused; both forms compute the same bits;
+    // at 32 the table has no qkv_sa)
     const bool sa16 = NB < 16 || sa16_fused(m.weight_mode);
     for (int l = 0; l < L; ++l) {
         const mp::DecLayerW &W = m.dec[l];
@@ -750,7 +756,7 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
         const double xa_bytes = A * act * (768.0 + 2.0 * 768 * dev->Tmax + mp::XA_SPLITS * mp::XA_PART);
         // direct XA (Q8_0 q_net / o_net, or long texts: mp_hip_set_xa_mode): x2 materialised
         const bool xa_dir = W.xq8 || dev->xa_direct;
-        const bool xa_in_oproj = tb.oproj_xa && !W.o8 && !xa_dir;
+        const bool xa_in_oproj = (tb.oproj_xa || tb.oproj_xa_pm) && !W.o8 && !xa_dir;
         // Q8_0 file: the whole direct Q8_0 cross-attention rides in the Q8_0 O-projection's
         // launch (EPI_RESID_XQ8): q_net workgroups on a hand-off of x1, then attention +
         // o_net workgroups on a hand-off of q (up to XQ8_QIN_NB slots: the attention
@@ -779,9 +785,13 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
             if (merge_xa) { xp.x2 = dev->x2; xp.gh = dev->xagh; }  // x2 merged by the XA workgroups
             g.xa = xp; g.xh = dev->xh; set_handoff(g, dev->ndone);
             if (int rc = e.gemv("oproj_xa", fn, g, F * (768.0 * 768) + A * act * (768 * 3) + xa_bytes)) return rc;
-        } else if (int rc = e.gemv("oproj", fam(W.o8).oproj, g,
-                                   weight_bytes(W.o8, F) * (768.0 * 768) + A * act * (768 * 3))) {
-            return rc;
+        } else {
+            mp::GemvFn fn = fam(W.o8).oproj;
+            if (NB == 32) {  // (direct XA) plain rows of the SA output its split workgroups merged
+                g.part = nullptr; g.src = dev->sa_out; g.src_ld = 768;
+                fn = tb.oproj_pm;
+            }
+            if (int rc = e.gemv("oproj", fn, g, weight_bytes(W.o8, F) * (768.0 * 768) + A * act * (768 * 3))) return rc;
         }
         if (xa_dir && !xq8_in_oproj) {
             // cross-attention as ggml computes it (1713-1767): q = q_net LN(x) (GEMV), then
@@ -1183,6 +1193,7 @@ int mp_hip_model_info(mp_dev *dev, int *dec_layers, int *enc_layers, size_t *wei
 int mp_hip_weight_mode(mp_dev *dev) { return dev && dev->loaded ? dev->m.weight_mode : MP_ERR_STATE; }
 int mp_hip_max_batch(mp_dev *dev) {
     if (!dev || !dev->loaded) return MP_ERR_STATE;
+    if (dev->m.weight_mode == MP_WEIGHTS_BF16) return 32;  // gemm_b16x2_kernel (mp_decode_b16.hip)
     return mp::h16_mode(dev->m.weight_mode) || (dev->m.weight_mode == MP_WEIGHTS_Q8 && dev->m.q8_all) ? 16 : 8;
 }
 
@@ -1288,7 +1299,7 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
     if (!dev->loaded) return fail(dev, MP_ERR_STATE, "no model loaded");
     const int bmax = mp_hip_max_batch(dev);
     if (!tokens || !n_tokens || !speaker || B < 1 || B > bmax || tmax < 1 || !params)
-        return fail(dev, MP_ERR_ARG, "invalid arguments (B must be 1..mp_hip_max_batch: 8 with f32 weights, 16 in the bf16 / F16 / Q8_0 / Q4_0 modes)");
+        return fail(dev, MP_ERR_ARG, "invalid arguments (B must be 1..mp_hip_max_batch: 8 with f32 weights, 32 with bf16 weights, 16 in the F16 / Q8_0 / Q4_0 modes)");
     // classifier-free guidance (mp_hip_set_cfg): two slots per utterance
     const bool guided = dev->cfg_scale != 0.f;
     if (guided) {
@@ -1315,7 +1326,8 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
         // direct form, both of which have a PRIOR kernel; the f32 family stops at 8 slots
         // (mp_hip_max_batch), so no list falls back to the standalone xa_part_kernel
         const int slots = guided ? 2 * B : B;
-        if (!mp::table_for(slots <= 1 ? 1 : slots <= 2 ? 2 : slots <= 4 ? 4 : slots <= 8 ? 8 : 16, wm).oproj_xap)
+        const mp::OpTable tp = mp::table_for(mp::slots_nb(slots), wm);
+        if (!tp.oproj_xap && !tp.oproj_xap_pm)
             return fail(dev, MP_ERR_UNSUPPORTED, "attention prior: no O-projection + XA kernel with a prior at this batch size");
     }
     int Tmax = 0, max_steps = 0;
@@ -1350,7 +1362,7 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
     {   // sampling settings live on the device: the captured graph serves any of them
         mp::SmpCfg cfg{params->temperature, params->top_k, (unsigned long long)params->seed, params->stream_base, {},
                        dev->cfg_scale, {}};
-        for (int b = 0; b < 16; ++b) { cfg.stream[b] = params->stream_base + b; cfg.partner[b] = -1; }
+        for (int b = 0; b < 32; ++b) { cfg.stream[b] = params->stream_base + b; cfg.partner[b] = -1; }
         if (guided)  // the pair draws from the utterance's stream
             for (int b = 0; b < B; ++b) { cfg.partner[b] = B + b; cfg.partner[B + b] = b; cfg.stream[B + b] = cfg.stream[b]; }
         HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
@@ -1719,7 +1731,7 @@ static int pool_start(mp_dev *dev, PoolRun &r, std::vector<int> &occ) {
         if (int rc = begin_batch(dev, tok.data(), nt.data(), spk.data(), B, r.tmax, &r.params, r.tmax)) return rc;
         // the draw streams follow the utterances, not the slots
         mp::SmpCfg cfg{r.params.temperature, r.params.top_k, (unsigned long long)r.params.seed, r.params.stream_base, {}, 0.f, {}};
-        for (int b = 0; b < 16; ++b) { cfg.stream[b] = r.params.stream_base + (b < B ? occ[b] : b); cfg.partner[b] = -1; }
+        for (int b = 0; b < 32; ++b) { cfg.stream[b] = r.params.stream_base + (b < B ? occ[b] : b); cfg.partner[b] = -1; }
         HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
         HIPCHK(hipStreamSynchronize(dev->stream));
     }
@@ -1734,8 +1746,8 @@ static int pool_run(mp_dev *dev, PoolRun &r) {
     const int B = (int)occ.size();
     if (B == 0) return MP_OK;
     const int NB = dev->NB, S = dev->max_steps;
-    HIPCHK(r.h.reserve((size_t)(36 + S * 8) * 4));
-    int32_t *h_nd = r.h.as<int32_t>(), *h_done = h_nd + 4, *h_nf = h_nd + 20, *h_codes = h_nd + 36;
+    HIPCHK(r.h.reserve((size_t)(4 + 2 * NB + S * 8) * 4));
+    int32_t *h_nd = r.h.as<int32_t>(), *h_done = h_nd + 4, *h_nf = h_done + NB, *h_codes = h_nf + NB;
     HIPCHK(r.e0.create());
     HIPCHK(r.e1.create());
     HIPCHK(hipEventRecord(r.e0, dev->stream));
@@ -1788,7 +1800,7 @@ static int pool_call(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens
     if (!tokens || !n_tokens || !speaker || N < 1 || tmax < 1 || !params)
         return fail(dev, MP_ERR_ARG, "invalid arguments");
     if (slots < 1 || slots > bmax)
-        return fail(dev, MP_ERR_ARG, "invalid arguments (slots must be 1..mp_hip_max_batch: 8 with f32 weights, 16 in the bf16 / F16 / Q8_0 / Q4_0 modes)");
+        return fail(dev, MP_ERR_ARG, "invalid arguments (slots must be 1..mp_hip_max_batch: 8 with f32 weights, 32 with bf16 weights, 16 in the F16 / Q8_0 / Q4_0 modes)");
     if (params->trace_hidden) return fail(dev, MP_ERR_ARG, "trace_hidden is not available with a slot pool");
     int Tmax = 0, max_steps = 0;
     if (int rc = check_params(dev, params, &max_steps)) return rc;

@@ -251,7 +251,7 @@ class Device:
 
     def __init__(self, model_path: str, device: int = 0, weights: str = "f32", kv: str = "f32", xa: str = "auto"):
         """weights: "f32" (as stored, widened to f32), "bf16" (decode projections
-        on bf16 MFMA, activations rounded to bf16; batches up to 16) or "q8" / "q4"
+        on bf16 MFMA, activations rounded to bf16; batches up to 32, 16 under set_cfg) or "q8" / "q4"
         (the file's Q8_0 / Q4_0 tensors kept as int8 (Q4_0: q - 8, losslessly),
         multiplied with ggml's semantics: activations quantised to Q8_0 per
         32-block, integer dots scaled by d_w * d_a; batches up to 16 when every
@@ -287,7 +287,8 @@ class Device:
         """mp_hip_set_cfg: classifier-free guidance from the next begin(); 0 is off. Every
         utterance then decodes as a pair of slots (conditional, text-free) whose logits are
         mixed in every code pick, scale * cond + (1 - scale) * uncond, so a batch holds at
-        most max_batch() // 2 utterances. f32 and bf16 weights; the queue calls refuse."""
+        most max_batch() // 2 utterances (16 with bf16 weights). f32 and bf16 weights; the queue
+        calls refuse."""
         if not hasattr(self.lib, "mp_hip_set_cfg"):
             raise MagpieError("this libmagpie_hip.so has no classifier-free guidance")
         self._check(self.lib.mp_hip_set_cfg(self.h, float(scale)))
