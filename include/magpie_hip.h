@@ -434,6 +434,60 @@ int mp_hip_codec_stream_decode_ragged(mp_codec_stream *s, const int32_t *lane_id
 /* back to the start of an utterance; lane < 0: all lanes */
 int mp_hip_codec_stream_reset(mp_codec_stream *s, int lane);
 void mp_hip_codec_stream_free(mp_codec_stream *s);
+
+/* --- PCM output: resampled, f32 or 16-bit ---------------------------------------- */
+/* The codec's waveform resampled on the device and delivered in the caller's sample format
+ * (resample_kernel, mp_codec.hip); only the output format's bytes are copied to the host. No
+ * reference counterpart but the S16 conversion (the reference writes 22 050 Hz only).
+ *
+ * Definition (the one place: the kernel, the host tables and the tests restate it).
+ *   x: the codec's f32 waveform at 22 050 Hz, x[j] = 0 for j < 0. The output rate R is one of
+ *   8000, 16000, 22050, 24000, 44100, 48000 Hz (anything else: MP_ERR_ARG); L / M = R / 22050
+ *   reduced: 160/441, 320/441, 1/1, 160/147, 2/1, 320/147.
+ *     i_n = floor(n M / L),  p_n = (n M) mod L                       (64-bit integers)
+ *     y[n] = sum_{k = 0}^{NT - 1} h[p_n][k] x[i_n - k]               f32: acc = 0, then
+ *                                                   acc = fmaf(h[p_n][k], x[i_n - k], acc), k ascending
+ *   N input samples give ceil(N L / M) outputs; there is no flush. A stream lane that has consumed
+ *   S input samples in total has emitted ceil(S L / M) outputs; a chunk emits the difference, and
+ *   every output is the same sum whatever the chunking, so chunks equal the one-shot call bit for
+ *   bit. The filter is causal: y lags x by the group delay of C input samples.
+ *   Coefficients, computed on the host in double when a rate is first used, stored as f32:
+ *     Z = 16 zero crossings, s = max(1, M / L), NT = 2 ceil(Z s) (32 taps when upsampling, 46 at
+ *     16 kHz, 90 at 8 kHz), C = NT / 2, fc = 0.9 / s, d = k + p / L - C,
+ *     h[p][k] = fc sinc(fc d) I0(9 sqrt(1 - (d / C)^2)) / I0(9) for |d| < C, else 0
+ *     (sinc(t) = sin(pi t) / (pi t), I0 the modified Bessel function: a Kaiser window, beta = 9),
+ *     then every row p is scaled so that sum_k h[p][k] = 1 in double.
+ *   R = 22050 is the identity: NT = 1, h = 1, C = 0, y = x exactly.
+ *   (Stopband below -87 dB from 1.1 x the lower Nyquist frequency at every rate: DESIGN.md 5.6.)
+ * Formats: MP_PCM_F32 is y. MP_PCM_S16 is the reference's WAV conversion (src/magpie-tts.cpp:59-63):
+ * y clamped to [-1, 1], then (int16_t)(y * 32767.0f), truncating toward zero; at R = 22050 it is
+ * byte for byte what the CLI writes.
+ * Not covered (follow-ups): the mp_audio_cb callbacks of mp_hip_decode_stream and
+ * mp_hip_decode_queue_stream still deliver f32 at 22 050 Hz; the last C input samples' worth of
+ * filter tail is not flushed. */
+#define MP_PCM_F32 0
+#define MP_PCM_S16 1
+/* samples a decode of n_frames frames yields at `rate`: ceil(n_frames * 1024 * L / M);
+ * MP_ERR_ARG (< 0) for another rate or n_frames < 0 */
+int64_t mp_hip_pcm_samples(int n_frames, int rate);
+/* mp_hip_codec_decode followed by the resampler: out holds `cap` samples of `format`, *n_out
+ * (nullable) the count written, mp_hip_pcm_samples(n_frames, rate). MP_ERR_ARG for a bad rate or
+ * format or a cap too small (the message names the size needed), before anything runs.
+ * mp_hip_codec_last_ms covers the resampler. */
+int mp_hip_codec_decode_pcm(mp_codec *c, const int32_t *codes, int n_frames, int rate, int format, void *out,
+                            int64_t cap, int64_t *n_out);
+/* mp_hip_codec_stream_decode_ragged followed by the resampler on the same lanes: out [n][stride]
+ * samples of `format`, n_out [n]; lane q's n_out[q] outputs are the next ceil-difference of its
+ * running count. Beside the codec's state a lane keeps its last NT - 1 waveform samples and its
+ * 64-bit counts of samples consumed and emitted (allocated when the stream first takes this
+ * call; mp_hip_codec_stream_reset zeroes them with the rest). One rate per stream: another rate
+ * is MP_ERR_STATE until mp_hip_codec_stream_reset(s, -1). A lane's chunks all go through this
+ * call between two resets (the f32 calls do not advance the resampler). MP_ERR_ARG as for the
+ * ragged call, for a bad rate or format and for a stride below the largest n_out of the call (the
+ * message names it); a failed call advances nothing. */
+int mp_hip_codec_stream_decode_pcm(mp_codec_stream *s, const int32_t *lane_ids, int n, const int32_t *codes,
+                                   const int32_t *n_frames, int max_frames, int rate, int format, void *out,
+                                   int64_t stride, int64_t *n_out);
 void mp_hip_codec_free(mp_codec *c);
 const char *mp_hip_codec_error(mp_codec *c);
 

@@ -1276,6 +1276,114 @@ __global__ __launch_bounds__(256) void post_conv_kernel(PostP p, H... hh) {
     p.audio[cbase + t] = tanhf(acc + p.bias[0]);
 }
 
+// ---------------------------------------------------------------- PCM output: the resampler
+// y[n] = sum_k h[(n M) mod L][k] x[floor(n M / L) - k], the polyphase FIR include/magpie_hip.h
+// defines (mp_hip_codec_decode_pcm), over the waveform post_conv_kernel left in c->audio.
+//
+// Every L of the six rates divides 320 (1, 2, 160, 320). A workgroup is therefore 320 threads
+// (5 waves) and owns RS_ITERS * 320 consecutive outputs of one chunk; thread t computes outputs
+// r0 + t + 320 it. Its phase (n M) mod L is the same at every step, wherever the tile starts, so
+// it loads its coefficient row once into NT registers and its input index advances by the
+// constant 320 M / L per step: phase-stationary with no whole-period alignment, hence no
+// separate path for a chunk's partial first and last periods. Consecutive threads write
+// consecutive outputs. The tile's input span (at most RS_ITERS * 320 M / L + NT floats; 14.5 KB
+// at 8 kHz) is staged into LDS once with 16-byte loads, the NT - 1 samples before the chunk from
+// the lane's history (zeros for a first chunk and for the one-shot call). The operator is
+// Toeplitz with one FMA per coefficient and per LDS read: there is no MFMA shape in it.
+// Each output's taps are one serial fmaf chain, k ascending from 0, whatever the tile, chunk or
+// lane: chunks equal the one-shot decode bit for bit.
+constexpr int RS_WG = 320, RS_ITERS = 4, RS_TILE = RS_WG * RS_ITERS;
+constexpr int RS_HIST = 92;  // floats of history a lane keeps per parity: NT - 1 <= 89, 16-byte rows
+constexpr int RS_NRATE = 6;
+constexpr int RS_RATE[RS_NRATE] = {8000, 16000, 22050, 24000, 44100, 48000};
+constexpr int RS_L[RS_NRATE] = {160, 320, 1, 160, 2, 320}, RS_M[RS_NRATE] = {441, 441, 1, 147, 1, 147};
+constexpr int RS_NT[RS_NRATE] = {90, 46, 1, 32, 32, 32};  // 2 ceil(16 max(1, M / L)); 1: the identity
+struct RsChunk {
+    long long S, n0;  // input samples the lane consumed, outputs it emitted, before this chunk
+    int N, nout;      // the chunk's own input samples and outputs
+    int lane, par;    // stream lane (-1: stateless, zeros before the chunk) and the history parity read
+};
+struct RsP {
+    const float *x;     // [chunk][Tin] the codec's waveform
+    const float *h;     // [L][NT]
+    const RsChunk *ch;  // [chunk]
+    float *hist;        // [2 parities][nlanes][RS_HIST]
+    void *out;          // [chunk][ostride] float or int16_t
+    int Tin, nlanes;
+    long long ostride;  // a multiple of 8 samples
+};
+
+template <int L, int M, int NT, int FMT>
+__global__ __launch_bounds__(RS_WG) void resample_kernel(RsP p) {
+    constexpr int STEP = RS_WG / L * M;                         // input samples per 320 outputs
+    constexpr int LDSN = (RS_ITERS * STEP + NT + 8 + 3) & ~3;   // span + alignment slack
+    __shared__ __attribute__((aligned(16))) float xs[LDSN];
+    const int tid = threadIdx.x, chunk = blockIdx.y;
+    const RsChunk d = p.ch[chunk];
+    const float *x = p.x + (size_t)chunk * p.Tin;
+    const float *hr = d.lane >= 0 ? p.hist + ((size_t)d.par * p.nlanes + d.lane) * RS_HIST : nullptr;
+    // the lane's next history: the chunk's last NT - 1 samples (a chunk is >= 1024 samples), other parity
+    if (blockIdx.x == 0 && d.lane >= 0 && tid < NT - 1)
+        p.hist[((size_t)(d.par ^ 1) * p.nlanes + d.lane) * RS_HIST + tid] = x[d.N - (NT - 1) + tid];
+    const int r0 = blockIdx.x * RS_TILE;
+    if (r0 >= d.nout) return;
+    const int r1 = min(r0 + RS_TILE, d.nout);
+    // the tile's inputs, as indices into the chunk: [a, b], a >= -(NT - 1), b <= N - 1
+    const int a = (int)(((d.n0 + r0) * M) / L - d.S) - (NT - 1), b = (int)(((d.n0 + r1 - 1) * M) / L - d.S);
+    const int a4 = a & ~3;  // rounded down to a 16-byte boundary of the chunk's row
+    const int nq = min((b - a4) / 4 + 1, LDSN / 4);
+    for (int v = tid; v < nq; v += RS_WG) {
+        const int j = a4 + 4 * v;
+        float4 q;
+        if (j >= 0 && j + 3 < d.N) {
+            q = *(const float4 *)(x + j);
+        } else {
+            float e[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int idx = j + u;
+                e[u] = idx >= 0 ? (idx < d.N ? x[idx] : 0.f) : (hr && idx >= -(NT - 1) ? hr[NT - 1 + idx] : 0.f);
+            }
+            q = make_float4(e[0], e[1], e[2], e[3]);
+        }
+        *(float4 *)&xs[4 * v] = q;
+    }
+    __syncthreads();
+    const long long nm = (d.n0 + r0 + tid) * M;
+    int li = (int)(nm / L - d.S) - a4;  // xs index of x[i_n]; li - k >= a - a4 >= 0
+    float hc[NT];
+    const float *hrow = p.h + (size_t)(nm % L) * NT;
+#pragma unroll
+    for (int k = 0; k < NT; ++k) hc[k] = hrow[k];
+#pragma unroll
+    for (int it = 0; it < RS_ITERS; ++it, li += STEP) {
+        const int r = r0 + tid + it * RS_WG;
+        float acc = 0.f;
+        if (r < r1) {
+            if constexpr (NT == 1) {
+                acc = xs[li];  // the identity, y = x exactly
+            } else {
+#pragma unroll
+                for (int k = 0; k < NT; ++k) acc = fmaf(hc[k], xs[li - k], acc);
+            }
+        }
+        if constexpr (FMT == MP_PCM_F32) {
+            if (r < r1) ((float *)p.out)[(size_t)chunk * p.ostride + r] = acc;
+        } else {
+            // clamp, scale, truncate (the reference's WAV writer); two samples per dword: r0 and
+            // the wave's first lane are even, so an even r's neighbour is the next lane's
+            const float s = fminf(fmaxf(acc, -1.f), 1.f);
+            const int v = (int)(unsigned short)(short)(int)(s * 32767.0f);
+            const int up = __shfl_down(v, 1);
+            short *o = (short *)p.out + (size_t)chunk * p.ostride + r;
+            if (!(tid & 1)) {
+                if (r + 1 < r1) *(int *)o = v | (up << 16);
+                else if (r < r1) *o = (short)v;
+            }
+        }
+    }
+}
+
 }  // namespace mpc
 
 // ====================================================================== runtime
@@ -1304,6 +1412,14 @@ struct mp_codec {
     // (configs[2]: each overlapped round's codec finished only after the decode's next chunk)
     mp::Pinned codes_pin, audio_pin;
     float last_ms = 0.f;  // device time of the last decode (launch sequence only)
+    // PCM output (mp_hip_codec_decode_pcm): a rate's coefficient table [L][NT], built when first
+    // used; the call's chunk descriptors and its resampled output, each with its pinned twin
+    mp::DevBlocks rs_tables, rs_mem;
+    float *rs_h[mpc::RS_NRATE] = {};
+    mpc::RsChunk *rs_desc = nullptr;
+    void *rs_out = nullptr;
+    size_t rs_desc_cap = 0, rs_out_cap = 0;  // chunks, bytes
+    mp::Pinned rs_desc_pin, rs_out_pin;
     // diagnostics (MAGPIE_CODEC_TS=stage,block,file): the phase stamps of one rb_kernel launch
     mp::DevBlocks ts_mem;
     unsigned long long *ts_dev = nullptr;
@@ -1327,6 +1443,14 @@ struct mp_codec_stream {
     float *post_hs = nullptr;                   // [2][28] floats
     std::vector<int> parity, started;           // per lane: the parity the next call reads; a chunk was decoded
     std::vector<int32_t> hist;                  // per lane [8][6]: the last 6 frames of codes, -1 before the first
+    // the resampler's side of a lane (PCM calls; allocated by the first one): the last NT - 1
+    // waveform samples (device, both parities, mpc::RS_HIST floats each), the parity the next
+    // call reads, the samples consumed (S) and emitted (n) so far; rs_rate: the stream's one rate
+    mp::DevBlocks rs_mem;
+    float *rs_hist = nullptr;
+    int rs_rate = 0;
+    std::vector<int> rs_par;
+    std::vector<long long> rs_S, rs_n;
     static int pad(int j, int k, int sk) { return (mpc::KS[j] - 1) * (sk ? 1 : mpc::DIL[k]); }
 };
 
@@ -1715,6 +1839,118 @@ int stream_reset_lane(mp_codec_stream *st, int lane) {
         CHK(hipMemsetAsync(st->state + ((size_t)par * st->lanes + lane) * st->lbytes, 0, st->lbytes, c->stream));
     st->parity[lane] = st->started[lane] = 0;
     std::fill(st->hist.begin() + (size_t)lane * 48, st->hist.begin() + (size_t)(lane + 1) * 48, -1);
+    if (st->rs_hist) {  // the resampler's side: no samples before the lane's next chunk, counts at 0
+        for (int par = 0; par < 2; ++par)
+            CHK(hipMemsetAsync(st->rs_hist + ((size_t)par * st->lanes + lane) * mpc::RS_HIST, 0, mpc::RS_HIST * 4, c->stream));
+        st->rs_par[lane] = 0;
+        st->rs_S[lane] = st->rs_n[lane] = 0;
+    }
+    return MP_OK;
+}
+
+// ---- PCM output
+int rs_rate_index(int rate) {
+    for (int i = 0; i < mpc::RS_NRATE; ++i)
+        if (mpc::RS_RATE[i] == rate) return i;
+    return -1;
+}
+// outputs after S input samples: ceil(S L / M)
+long long rs_count(long long S, int ri) { return (S * mpc::RS_L[ri] + mpc::RS_M[ri] - 1) / mpc::RS_M[ri]; }
+size_t rs_sample_bytes(int fmt) { return fmt == MP_PCM_S16 ? 2 : 4; }
+
+// I0 by its power series, sum ((x / 2)^k / k!)^2 (x <= 9: below 1e-17 of the sum after 40 terms)
+double rs_i0(double x) {
+    double t = 1.0, sum = 1.0;
+    for (int k = 1; k < 60; ++k) {
+        t *= (x / 2) / k;
+        sum += t * t;
+    }
+    return sum;
+}
+
+// the rate's coefficient table h[L][NT] (include/magpie_hip.h), in double, stored as f32
+int rs_table(mp_codec *c, int ri) {
+    if (c->rs_h[ri]) return MP_OK;
+    const int L = mpc::RS_L[ri], M = mpc::RS_M[ri], NT = mpc::RS_NT[ri];
+    std::vector<float> h((size_t)L * NT, 1.f);
+    if (NT > 1) {
+        const double s = std::max(1.0, (double)M / L), fc = 0.9 / s, C = NT / 2, i0b = rs_i0(9.0);
+        std::vector<double> row(NT);
+        for (int p = 0; p < L; ++p) {
+            double sum = 0;
+            for (int k = 0; k < NT; ++k) {
+                const double d = k + (double)p / L - C, t = M_PI * fc * d, u = d / C;
+                row[k] = fabs(d) < C ? fc * (t == 0 ? 1.0 : sin(t) / t) * rs_i0(9.0 * sqrt(1 - u * u)) / i0b : 0.0;
+                sum += row[k];
+            }
+            for (int k = 0; k < NT; ++k) h[(size_t)p * NT + k] = (float)(row[k] / sum);
+        }
+    }
+    float *dev = nullptr;
+    CHK(c->rs_tables.bytes(&dev, h.size() * 4));
+    CHK(hipMemcpy(dev, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    c->rs_h[ri] = dev;
+    return MP_OK;
+}
+
+// A PCM call's side of decode_call: the resampler runs behind the launch sequence, inside
+// last_ms's events, and what comes down is the resampled output in the caller's format
+// (c->rs_out_pin: [chunk][ostride] samples), not the f32 waveform.
+struct PcmCtx {
+    int ri, fmt;
+    mp_codec_stream *st;           // the stream whose lanes the chunks are (null: stateless)
+    std::vector<mpc::RsChunk> ch;  // [chunk]
+    size_t ostride = 0;            // samples per chunk row: the call's largest nout, up to a multiple of 8
+};
+
+// before the sequence: the table, the buffers, the chunk descriptors up
+int pcm_prepare(mp_codec *c, PcmCtx &px) {
+    if (int rc = rs_table(c, px.ri)) return rc;
+    const size_t nchunk = px.ch.size();
+    int most = 0;
+    for (const mpc::RsChunk &d : px.ch) most = std::max(most, d.nout);
+    px.ostride = ((size_t)most + 7) & ~(size_t)7;
+    const size_t obytes = nchunk * px.ostride * rs_sample_bytes(px.fmt);
+    if (nchunk > c->rs_desc_cap || obytes > c->rs_out_cap) {
+        c->rs_mem.clear();
+        c->rs_desc_cap = c->rs_out_cap = 0;
+        CHK(c->rs_mem.bytes(&c->rs_desc, nchunk * sizeof(mpc::RsChunk)));
+        CHK(c->rs_mem.bytes(&c->rs_out, obytes));
+        c->rs_desc_cap = nchunk;
+        c->rs_out_cap = obytes;
+    }
+    CHK(c->rs_desc_pin.reserve(nchunk * sizeof(mpc::RsChunk)));
+    CHK(c->rs_out_pin.reserve(obytes));
+    memcpy(c->rs_desc_pin.p, px.ch.data(), nchunk * sizeof(mpc::RsChunk));
+    CHK(hipMemcpyAsync(c->rs_desc, c->rs_desc_pin.p, nchunk * sizeof(mpc::RsChunk), hipMemcpyHostToDevice, c->stream));
+    return MP_OK;
+}
+
+template <int FMT> void launch_resample(int ri, const mpc::RsP &p, dim3 grid, hipStream_t s) {
+    using namespace mpc;
+    const dim3 wg(RS_WG);
+    switch (ri) {  // RS_RATE's order
+        case 0: hipLaunchKernelGGL((resample_kernel<160, 441, 90, FMT>), grid, wg, 0, s, p); break;
+        case 1: hipLaunchKernelGGL((resample_kernel<320, 441, 46, FMT>), grid, wg, 0, s, p); break;
+        case 2: hipLaunchKernelGGL((resample_kernel<1, 1, 1, FMT>), grid, wg, 0, s, p); break;
+        case 3: hipLaunchKernelGGL((resample_kernel<160, 147, 32, FMT>), grid, wg, 0, s, p); break;
+        case 4: hipLaunchKernelGGL((resample_kernel<2, 1, 32, FMT>), grid, wg, 0, s, p); break;
+        default: hipLaunchKernelGGL((resample_kernel<320, 147, 32, FMT>), grid, wg, 0, s, p); break;
+    }
+}
+
+// behind the sequence: c->audio [chunk][F * 1024] -> c->rs_out
+int pcm_run(mp_codec *c, int F, const PcmCtx &px) {
+    mpc::RsP p{};
+    p.x = c->audio; p.h = c->rs_h[px.ri]; p.ch = c->rs_desc; p.out = c->rs_out;
+    p.hist = px.st ? px.st->rs_hist : nullptr;
+    p.nlanes = px.st ? px.st->lanes : 0;
+    p.Tin = F * mpc::HOP;
+    p.ostride = (long long)px.ostride;
+    const dim3 grid((unsigned)((px.ostride + mpc::RS_TILE - 1) / mpc::RS_TILE), (unsigned)px.ch.size());
+    if (px.fmt == MP_PCM_S16) launch_resample<MP_PCM_S16>(px.ri, p, grid, c->stream);
+    else launch_resample<MP_PCM_F32>(px.ri, p, grid, c->stream);
+    CHK(hipGetLastError());
     return MP_OK;
 }
 
@@ -1722,22 +1958,33 @@ int stream_reset_lane(mp_codec_stream *st, int lane) {
 // buffers, the codes up through pinned memory, the sequence between the two events of
 // last_ms, the audio down and out. stage(host codes) writes the call's nchunk * 8 * F +
 // codes_extra ints; it runs once the device buffers stand, so it may take c->codes' address.
+// px set (a PCM call): the resampler joins the sequence and its output comes down instead,
+// into c->rs_out_pin (audio_out unused).
 template <class Stage>
-int decode_call(mp_codec *c, int nchunk, int F, size_t codes_extra, StreamCtx *sx, float *audio_out, Stage stage) {
+int decode_call(mp_codec *c, int nchunk, int F, size_t codes_extra, StreamCtx *sx, float *audio_out, Stage stage,
+                PcmCtx *px = nullptr) {
     if (int rc = ensure_buffers(c, nchunk, F, codes_extra)) return rc;
     const size_t ncodes = (size_t)nchunk * 8 * F + codes_extra, nsamp = (size_t)nchunk * F * mpc::HOP;
     CHK(c->codes_pin.reserve(ncodes * 4));
-    CHK(c->audio_pin.reserve(nsamp * 4));
+    if (!px) CHK(c->audio_pin.reserve(nsamp * 4));
     stage((int32_t *)c->codes_pin.p);
     CHK(hipMemcpyAsync(c->codes, c->codes_pin.p, ncodes * 4, hipMemcpyHostToDevice, c->stream));
+    if (px)
+        if (int rc = pcm_prepare(c, *px)) return rc;
     CHK(c->ev0.create());
     CHK(c->ev1.create());
     CHK(hipEventRecord(c->ev0, c->stream));
     if (int rc = codec_run(c, nchunk, F, sx)) return rc;
+    if (px)
+        if (int rc = pcm_run(c, F, *px)) return rc;
     CHK(hipEventRecord(c->ev1, c->stream));
-    CHK(hipMemcpyAsync(c->audio_pin.p, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
+    if (px)
+        CHK(hipMemcpyAsync(c->rs_out_pin.p, c->rs_out, (size_t)nchunk * px->ostride * rs_sample_bytes(px->fmt),
+                           hipMemcpyDeviceToHost, c->stream));
+    else
+        CHK(hipMemcpyAsync(c->audio_pin.p, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
     CHK(hipStreamSynchronize(c->stream));
-    memcpy(audio_out, c->audio_pin.p, nsamp * 4);
+    if (!px) memcpy(audio_out, c->audio_pin.p, nsamp * 4);
     CHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
     return MP_OK;
 }
@@ -1771,6 +2018,89 @@ int ts_dump(mp_codec *c) {
     if (FILE *f = fopen(c->ts_file.c_str(), "wb")) {
         fwrite(h.data(), 8, h.size(), f);
         fclose(f);
+    }
+    return MP_OK;
+}
+
+// rate and format of a PCM call: the rate's index, or MP_ERR_ARG with the message
+int pcm_check(mp_codec *c, int rate, int format) {
+    const int ri = rs_rate_index(rate);
+    if (ri < 0) {
+        c->err = "pcm: sample rate " + std::to_string(rate) + " is not one of 8000, 16000, 22050, 24000, 44100, 48000";
+        return MP_ERR_ARG;
+    }
+    if (format != MP_PCM_F32 && format != MP_PCM_S16) {
+        c->err = "pcm: format " + std::to_string(format) + " is neither MP_PCM_F32 nor MP_PCM_S16";
+        return MP_ERR_ARG;
+    }
+    return ri;
+}
+
+// the arguments of a ragged stream decode (`out`: the caller's output buffer, of either kind)
+int check_ragged(mp_codec_stream *st, const int32_t *lane_ids, int n, const int32_t *codes, const int32_t *n_frames,
+                 int max_frames, const void *out) {
+    mp_codec *c = st->c;
+    if (!lane_ids || !codes || !n_frames || !out || n < 1 || max_frames < 1) {
+        c->err = "stream decode: invalid arguments";
+        return MP_ERR_ARG;
+    }
+    if (n > st->lanes) { c->err = "stream decode: more lanes than the stream has"; return MP_ERR_ARG; }
+    for (int q = 0; q < n; ++q) {
+        if (lane_ids[q] < 0 || lane_ids[q] >= st->lanes) {
+            c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " out of range";
+            return MP_ERR_ARG;
+        }
+        for (int r = 0; r < q; ++r)
+            if (lane_ids[r] == lane_ids[q]) {
+                c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " given twice";
+                return MP_ERR_ARG;
+            }
+        if (n_frames[q] < 1 || n_frames[q] > max_frames) {
+            c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " has " + std::to_string(n_frames[q]) +
+                     " frames, not 1.." + std::to_string(max_frames);
+            return MP_ERR_ARG;
+        }
+    }
+    return MP_OK;
+}
+
+// the checked ragged stream decode: the f32 waveform into audio_out, or (px) resampled into c->rs_out_pin
+int run_ragged(mp_codec_stream *st, const int32_t *lane_ids, int n, const int32_t *codes, const int32_t *n_frames,
+               int max_frames, float *audio_out, PcmCtx *px) {
+    mp_codec *c = st->c;
+    const int F = max_frames, FH = F + 6;
+    CHK(hipSetDevice(c->device));
+    // behind the codes [n][8][FH]: the lane table [n] and the chunks' own frame counts [n]
+    const size_t ncodes = (size_t)n * 8 * FH;
+    StreamCtx sx{st, {}};
+    sx.h.maxf = F;
+    sx.h.nlanes = st->lanes;
+    sx.h.lbytes = st->lbytes;
+    int32_t *hc = nullptr;
+    const auto stage = [&](int32_t *pin) {
+        hc = pin;
+        for (int q = 0; q < n; ++q) {
+            const int ln = lane_ids[q], nf = n_frames[q];
+            for (int cb = 0; cb < 8; ++cb) {  // [6 of history | the chunk's own frames | -1: a zero operand]
+                int32_t *row = hc + ((size_t)q * 8 + cb) * FH;
+                memcpy(row, st->hist.data() + (size_t)ln * 48 + cb * 6, 6 * 4);
+                memcpy(row + 6, codes + ((size_t)q * 8 + cb) * F, (size_t)nf * 4);
+                std::fill(row + 6 + nf, row + FH, -1);
+            }
+            hc[ncodes + q] = ln * 4 + 2 * st->started[ln] + st->parity[ln];
+            hc[ncodes + n + q] = nf;
+        }
+        sx.h.lanes = c->codes + ncodes;
+        sx.h.nfr = sx.h.lanes + n;
+    };
+    if (int rc = decode_call(c, n, F, (size_t)n * 8 * 6 + 2 * (size_t)n, &sx, audio_out, stage, px)) return rc;
+    // the call succeeded: every lane's state advances (the parity just written becomes the one read)
+    for (int q = 0; q < n; ++q) {
+        const int ln = lane_ids[q];
+        st->parity[ln] ^= 1;
+        st->started[ln] = 1;
+        for (int cb = 0; cb < 8; ++cb)  // the last 6 of (history ++ the chunk's own frames)
+            memcpy(st->hist.data() + (size_t)ln * 48 + cb * 6, hc + ((size_t)q * 8 + cb) * FH + n_frames[q], 6 * 4);
     }
     return MP_OK;
 }
@@ -1871,61 +2201,83 @@ int mp_hip_codec_stream_create(mp_codec *c, int lanes, mp_codec_stream **out) {
 int mp_hip_codec_stream_decode_ragged(mp_codec_stream *st, const int32_t *lane_ids, int n, const int32_t *codes,
                                       const int32_t *n_frames, int max_frames, float *audio_out) {
     if (!st) return MP_ERR_ARG;
-    mp_codec *c = st->c;
-    if (!lane_ids || !codes || !n_frames || !audio_out || n < 1 || max_frames < 1) {
-        c->err = "stream decode: invalid arguments";
+    if (int rc = check_ragged(st, lane_ids, n, codes, n_frames, max_frames, audio_out)) return rc;
+    return run_ragged(st, lane_ids, n, codes, n_frames, max_frames, audio_out, nullptr);
+}
+
+int64_t mp_hip_pcm_samples(int n_frames, int rate) {
+    const int ri = rs_rate_index(rate);
+    return ri < 0 || n_frames < 0 ? MP_ERR_ARG : rs_count((long long)n_frames * mpc::HOP, ri);
+}
+
+int mp_hip_codec_decode_pcm(mp_codec *c, const int32_t *codes, int n_frames, int rate, int format, void *out,
+                            int64_t cap, int64_t *n_out) {
+    if (!c) return MP_ERR_ARG;
+    if (!codes || !out || n_frames < 1) { c->err = "pcm: invalid arguments"; return MP_ERR_ARG; }
+    const int ri = pcm_check(c, rate, format);
+    if (ri < 0) return ri;
+    const long long need = rs_count((long long)n_frames * mpc::HOP, ri);
+    if (cap < need || need > INT32_MAX) {
+        c->err = "pcm: out holds " + std::to_string(cap) + " samples, " + std::to_string(n_frames) + " frames at " +
+                 std::to_string(rate) + " Hz are " + std::to_string(need);
         return MP_ERR_ARG;
     }
-    if (n > st->lanes) { c->err = "stream decode: more lanes than the stream has"; return MP_ERR_ARG; }
-    for (int q = 0; q < n; ++q) {
-        if (lane_ids[q] < 0 || lane_ids[q] >= st->lanes) {
-            c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " out of range";
-            return MP_ERR_ARG;
-        }
-        for (int r = 0; r < q; ++r)
-            if (lane_ids[r] == lane_ids[q]) {
-                c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " given twice";
-                return MP_ERR_ARG;
-            }
-        if (n_frames[q] < 1 || n_frames[q] > max_frames) {
-            c->err = "stream decode: lane " + std::to_string(lane_ids[q]) + " has " + std::to_string(n_frames[q]) +
-                     " frames, not 1.." + std::to_string(max_frames);
-            return MP_ERR_ARG;
-        }
-    }
-    const int F = max_frames, FH = F + 6;
     CHK(hipSetDevice(c->device));
-    // behind the codes [n][8][FH]: the lane table [n] and the chunks' own frame counts [n]
-    const size_t ncodes = (size_t)n * 8 * FH;
-    StreamCtx sx{st, {}};
-    sx.h.maxf = F;
-    sx.h.nlanes = st->lanes;
-    sx.h.lbytes = st->lbytes;
-    int32_t *hc = nullptr;
-    const auto stage = [&](int32_t *pin) {
-        hc = pin;
-        for (int q = 0; q < n; ++q) {
-            const int ln = lane_ids[q], nf = n_frames[q];
-            for (int cb = 0; cb < 8; ++cb) {  // [6 of history | the chunk's own frames | -1: a zero operand]
-                int32_t *row = hc + ((size_t)q * 8 + cb) * FH;
-                memcpy(row, st->hist.data() + (size_t)ln * 48 + cb * 6, 6 * 4);
-                memcpy(row + 6, codes + ((size_t)q * 8 + cb) * F, (size_t)nf * 4);
-                std::fill(row + 6 + nf, row + FH, -1);
-            }
-            hc[ncodes + q] = ln * 4 + 2 * st->started[ln] + st->parity[ln];
-            hc[ncodes + n + q] = nf;
-        }
-        sx.h.lanes = c->codes + ncodes;
-        sx.h.nfr = sx.h.lanes + n;
-    };
-    if (int rc = decode_call(c, n, F, (size_t)n * 8 * 6 + 2 * (size_t)n, &sx, audio_out, stage)) return rc;
-    // the call succeeded: every lane's state advances (the parity just written becomes the one read)
+    PcmCtx px{ri, format, nullptr, {mpc::RsChunk{0, 0, n_frames * mpc::HOP, (int)need, -1, 0}}};
+    const size_t ncodes = (size_t)8 * n_frames;
+    if (int rc = decode_call(c, 1, n_frames, 0, nullptr, nullptr, [&](int32_t *hc) { memcpy(hc, codes, ncodes * 4); }, &px))
+        return rc;
+    memcpy(out, c->rs_out_pin.p, (size_t)need * rs_sample_bytes(format));
+    if (n_out) *n_out = need;
+    return MP_OK;
+}
+
+int mp_hip_codec_stream_decode_pcm(mp_codec_stream *st, const int32_t *lane_ids, int n, const int32_t *codes,
+                                   const int32_t *n_frames, int max_frames, int rate, int format, void *out,
+                                   int64_t stride, int64_t *n_out) {
+    if (!st) return MP_ERR_ARG;
+    mp_codec *c = st->c;
+    if (int rc = check_ragged(st, lane_ids, n, codes, n_frames, max_frames, out)) return rc;
+    if (!n_out) { c->err = "pcm: invalid arguments"; return MP_ERR_ARG; }
+    const int ri = pcm_check(c, rate, format);
+    if (ri < 0) return ri;
+    if (st->rs_rate && st->rs_rate != rate) {
+        c->err = "pcm: the stream resamples to " + std::to_string(st->rs_rate) + " Hz until mp_hip_codec_stream_reset(s, -1), not to " +
+                 std::to_string(rate);
+        return MP_ERR_STATE;
+    }
+    PcmCtx px{ri, format, st, {}};
+    long long most = 0;
     for (int q = 0; q < n; ++q) {
         const int ln = lane_ids[q];
-        st->parity[ln] ^= 1;
-        st->started[ln] = 1;
-        for (int cb = 0; cb < 8; ++cb)  // the last 6 of (history ++ the chunk's own frames)
-            memcpy(st->hist.data() + (size_t)ln * 48 + cb * 6, hc + ((size_t)q * 8 + cb) * FH + n_frames[q], 6 * 4);
+        const long long S = st->rs_hist ? st->rs_S[ln] : 0, n0 = st->rs_hist ? st->rs_n[ln] : 0;
+        const int N = n_frames[q] * mpc::HOP;
+        px.ch.push_back(mpc::RsChunk{S, n0, N, (int)(rs_count(S + N, ri) - n0), ln, st->rs_hist ? st->rs_par[ln] : 0});
+        most = std::max<long long>(most, px.ch.back().nout);
+    }
+    if (stride < most) {
+        c->err = "pcm: stride " + std::to_string(stride) + " is below the " + std::to_string(most) + " samples a lane of this call yields";
+        return MP_ERR_ARG;
+    }
+    CHK(hipSetDevice(c->device));
+    if (!st->rs_hist) {  // the stream's first PCM call: every lane's history, zero
+        const size_t bytes = 2 * (size_t)st->lanes * mpc::RS_HIST * 4;
+        CHK(st->rs_mem.bytes(&st->rs_hist, bytes));
+        CHK(hipMemsetAsync(st->rs_hist, 0, bytes, c->stream));
+        st->rs_par.assign(st->lanes, 0);
+        st->rs_S.assign(st->lanes, 0);
+        st->rs_n.assign(st->lanes, 0);
+    }
+    if (int rc = run_ragged(st, lane_ids, n, codes, n_frames, max_frames, nullptr, &px)) return rc;
+    st->rs_rate = rate;
+    const size_t sb = rs_sample_bytes(format);
+    for (int q = 0; q < n; ++q) {  // the call succeeded: the lanes' resamplers advance with their codec state
+        const mpc::RsChunk &d = px.ch[q];
+        st->rs_par[d.lane] ^= 1;
+        st->rs_S[d.lane] += d.N;
+        st->rs_n[d.lane] += d.nout;
+        memcpy((char *)out + (size_t)q * stride * sb, (const char *)c->rs_out_pin.p + (size_t)q * px.ostride * sb, (size_t)d.nout * sb);
+        n_out[q] = d.nout;
     }
     return MP_OK;
 }
@@ -1946,6 +2298,7 @@ int mp_hip_codec_stream_reset(mp_codec_stream *st, int lane) {
     CHK(hipSetDevice(c->device));
     for (int ln = lane < 0 ? 0 : lane; ln < (lane < 0 ? st->lanes : lane + 1); ++ln)
         if (int rc = stream_reset_lane(st, ln)) return rc;
+    if (lane < 0) st->rs_rate = 0;  // every lane is back at its start: the stream may take another PCM rate
     return MP_OK;
 }
 

@@ -126,14 +126,25 @@ SYMBOLS = [
     ("mp_hip_set_attn_prior", _I, [_P, ctypes.POINTER(mp_attn_prior)]),
     ("mp_hip_get_alignment", _I, [_P, _P]),
     ("mp_hip_alignment_shape", _I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    ("mp_hip_pcm_samples", ctypes.c_int64, [_I, _I]),
+    ("mp_hip_codec_decode_pcm", _I, [_P, _P, _I, _I, _I, _P, ctypes.c_int64, _P]),
+    ("mp_hip_codec_stream_decode_pcm", _I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_int64, _P]),
 ]
+
+PCM_F32, PCM_S16 = 0, 1  # MP_PCM_*: the sample formats of the decode_pcm calls
+_PCM_DTYPE = {PCM_F32: np.float32, PCM_S16: np.int16}
+
+
+def pcm_samples(n_frames: int, rate: int) -> int:
+    """Samples n_frames codec frames yield at `rate` Hz (mp_hip_pcm_samples); < 0: not a PCM rate."""
+    return int(load_library().mp_hip_pcm_samples(n_frames, rate))
 
 # entry points added after round 4: absent from the A/B baseline libraries
 OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue", "mp_hip_codec_stream_create", "mp_hip_codec_stream_decode",
             "mp_hip_codec_stream_reset", "mp_hip_codec_stream_free", "mp_hip_set_stream_codec_mode",
             "mp_hip_codec_stream_decode_ragged", "mp_hip_decode_queue_stream", "mp_hip_set_cfg",
             "mp_hip_get_trace_uncond", "mp_hip_set_attn_prior", "mp_hip_get_alignment",
-            "mp_hip_alignment_shape"}
+            "mp_hip_alignment_shape", "mp_hip_pcm_samples", "mp_hip_codec_decode_pcm", "mp_hip_codec_stream_decode_pcm"}
 
 _lib = None
 
@@ -688,6 +699,22 @@ class Codec:
             raise MagpieError(f"{_ERRS.get(rc, rc)}: {self.lib.mp_hip_codec_error(self.h).decode(errors='replace')}")
         return out
 
+    def decode_pcm(self, codes_cb_major: np.ndarray, rate: int, fmt: int = PCM_S16, cap: Optional[int] = None) -> np.ndarray:
+        """decode, resampled on the device to `rate` Hz (8000, 16000, 22050, 24000, 44100, 48000)
+        and delivered as fmt (PCM_F32, PCM_S16): mp_hip_codec_decode_pcm. cap: the output
+        buffer's samples (default: what the decode yields)."""
+        codes = np.ascontiguousarray(codes_cb_major, np.int32)
+        assert codes.ndim == 2 and codes.shape[0] == 8
+        F = codes.shape[1]
+        if cap is None:
+            cap = max(pcm_samples(F, rate), 0)
+        out = np.zeros(cap, _PCM_DTYPE.get(fmt, np.float32))
+        n = ctypes.c_int64(0)
+        rc = self.lib.mp_hip_codec_decode_pcm(self.h, codes.ctypes.data, F, rate, fmt, out.ctypes.data, cap, ctypes.byref(n))
+        if rc != MP_OK:
+            raise MagpieError(f"{_ERRS.get(rc, rc)}: {self.lib.mp_hip_codec_error(self.h).decode(errors='replace')}")
+        return out[:n.value]
+
     def last_ms(self) -> float:
         ms = ctypes.c_float()
         self.lib.mp_hip_codec_last_ms(self.h, ctypes.byref(ms))
@@ -754,6 +781,16 @@ class CodecStream:
         (laid out for the longest). Returns n arrays of n_frames[q] * 1024 samples."""
         if not hasattr(self.lib, "mp_hip_codec_stream_decode_ragged"):
             raise MagpieError("this libmagpie_hip.so has no ragged stream decode")
+        codes, nf, ids = self._ragged_args(codes, n_frames, lanes)
+        n, _, F = codes.shape
+        out = np.zeros((n, F * 1024), np.float32)
+        self._check(self.lib.mp_hip_codec_stream_decode_ragged(self.h, ids.ctypes.data, n, codes.ctypes.data,
+                                                               nf.ctypes.data, F, out.ctypes.data))
+        return [out[q, :int(nf[q]) * 1024].copy() for q in range(n)]
+
+    @staticmethod
+    def _ragged_args(codes, n_frames, lanes):
+        """codes as [n][8][max_frames] int32 (from that, or from n arrays [8][>= n_frames[q]]), n_frames, lane ids"""
         if not (isinstance(codes, np.ndarray) and codes.ndim == 3):
             rows = [np.asarray(c, np.int32) for c in codes]
             F = max([r.shape[1] for r in rows] + [1])
@@ -767,10 +804,21 @@ class CodecStream:
         nf = np.ascontiguousarray(n_frames, np.int32)
         ids = np.ascontiguousarray(np.arange(n) if lanes is None else lanes, np.int32)
         assert ids.shape == (n,) and nf.shape == (n,)
-        out = np.zeros((n, F * 1024), np.float32)
-        self._check(self.lib.mp_hip_codec_stream_decode_ragged(self.h, ids.ctypes.data, n, codes.ctypes.data,
-                                                               nf.ctypes.data, F, out.ctypes.data))
-        return [out[q, :int(nf[q]) * 1024].copy() for q in range(n)]
+        return codes, nf, ids
+
+    def decode_pcm(self, codes, n_frames: Sequence[int], rate: int, fmt: int = PCM_S16,
+                   lanes: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+        """decode_ragged with the device resampler behind it (mp_hip_codec_stream_decode_pcm): lane
+        q's next samples at `rate` Hz as fmt, seamless from chunk to chunk; a lane's concatenation
+        is Codec.decode_pcm of its frames bit for bit. One rate per stream until reset(-1)."""
+        codes, nf, ids = self._ragged_args(codes, n_frames, lanes)
+        n, _, F = codes.shape
+        stride = max(pcm_samples(F, rate), 1)  # a chunk's ceil-difference never exceeds its own ceil
+        out = np.zeros((n, stride), _PCM_DTYPE.get(fmt, np.float32))
+        cnt = np.zeros(n, np.int64)
+        self._check(self.lib.mp_hip_codec_stream_decode_pcm(self.h, ids.ctypes.data, n, codes.ctypes.data, nf.ctypes.data,
+                                                            F, rate, fmt, out.ctypes.data, stride, cnt.ctypes.data))
+        return [out[q, :int(cnt[q])].copy() for q in range(n)]
 
     def reset(self, lane: int = -1) -> None:
         """Back to the start of an utterance on `lane` (-1: every lane)."""

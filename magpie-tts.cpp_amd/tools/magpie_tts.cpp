@@ -4,7 +4,8 @@
 // 16-bit mono WAV at 22050 Hz. Extra flags: --stream (sentence-chunked streaming
 // synthesis, magpie.cpp:4843-4863), --bf16 (bf16 decode projections), --seed,
 // --continuous-codec (the codec carries its conv state from chunk to chunk: the chunks'
-// audio is one decode of all the frames; with --stream, of each sentence's frames).
+// audio is one decode of all the frames; with --stream, of each sentence's frames),
+// --sample-rate (the chunks resampled and converted to 16-bit on the device: the PCM calls).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -37,6 +38,10 @@ void usage(const char *prog) {
             "  --stream             sentence-chunked streaming synthesis (4-frame codec chunks)\n"
             "  --continuous-codec   codec chunks carry their conv state: seamless across chunks\n"
             "  --bf16               bf16 decode projections (MFMA)\n"
+            "  --sample-rate R      output rate: 8000, 16000, 22050, 24000, 44100 or 48000 Hz. The codec's\n"
+            "                       chunks are resampled and converted to 16-bit on the device; a rate\n"
+            "                       other than 22050 implies --continuous-codec (the filter spans the\n"
+            "                       chunks). Default: 22050, converted on the host. Not with --stream.\n"
             "  -q, --quiet          minimal output\n"
             "  -h, --help           this help\n",
             prog);
@@ -44,7 +49,7 @@ void usage(const char *prog) {
 
 // RIFF/WAVE, PCM 16-bit mono; samples clamped to [-1, 1] and scaled by 32767
 // with truncation, as the reference writer does (magpie-tts.cpp:31-69).
-bool write_wav(const char *path, const std::vector<float> &audio, int rate) {
+bool write_wav(const char *path, const std::vector<int16_t> &pcm, int rate) {
     FILE *f = fopen(path, "wb");
     if (!f) return false;
     struct {
@@ -59,17 +64,20 @@ bool write_wav(const char *path, const std::vector<float> &audio, int rate) {
         char data[4] = {'d', 'a', 't', 'a'};
         int32_t data_size;
     } __attribute__((packed)) h;
-    h.data_size = (int32_t)(audio.size() * 2);
+    h.data_size = (int32_t)(pcm.size() * 2);
     h.riff_size = 36 + h.data_size;
     h.rate = rate;
     h.byte_rate = rate * 2;
+    const bool ok = fwrite(&h, sizeof h, 1, f) == 1 && fwrite(pcm.data(), 2, pcm.size(), f) == pcm.size();
+    return fclose(f) == 0 && ok;
+}
+bool write_wav(const char *path, const std::vector<float> &audio, int rate) {
     std::vector<int16_t> pcm(audio.size());
     for (size_t i = 0; i < audio.size(); ++i) {
         const float s = audio[i] > 1.f ? 1.f : audio[i] < -1.f ? -1.f : audio[i];
         pcm[i] = (int16_t)(s * 32767.0f);
     }
-    const bool ok = fwrite(&h, sizeof h, 1, f) == 1 && fwrite(pcm.data(), 2, pcm.size(), f) == pcm.size();
-    return fclose(f) == 0 && ok;
+    return write_wav(path, pcm, rate);
 }
 
 bool collect(const float *x, int n, void *user) {
@@ -85,7 +93,7 @@ int main(int argc, char **argv) {
     const char *text = nullptr, *out = "output.wav";
     int speaker = 0, top_k = 80;
     float temp = 0.7f, cfg_scale = 0.f, prior_eps = 0.f;
-    int prior_w = 5, prior_start = 0;
+    int prior_w = 5, prior_start = 0, sample_rate = -1;  // -1: no --sample-rate
     unsigned long long seed = 0;
     bool quiet = false, stream = false, bf16 = false, continuous = false;
     for (int i = 1; i < argc; ++i) {
@@ -113,6 +121,7 @@ int main(int argc, char **argv) {
         else if (a == "--stream") stream = true;
         else if (a == "--continuous-codec") continuous = true;
         else if (a == "--bf16") bf16 = true;
+        else if (a == "--sample-rate") sample_rate = atoi(val("--sample-rate"));
         else if (a == "-q" || a == "--quiet") quiet = true;
         else {
             fprintf(stderr, "Unknown option: %s\n", argv[i]);
@@ -123,6 +132,15 @@ int main(int argc, char **argv) {
     if (!text) {
         fprintf(stderr, "Error: --text is required\n\n");
         usage(argv[0]);
+        return 1;
+    }
+    const bool pcm_out = sample_rate != -1;
+    if (pcm_out && mp_hip_pcm_samples(0, sample_rate) < 0) {
+        fprintf(stderr, "Error: --sample-rate must be 8000, 16000, 22050, 24000, 44100 or 48000\n");
+        return 1;
+    }
+    if (pcm_out && stream) {  // the streaming calls hand out f32 at 22050 Hz through their callbacks
+        fprintf(stderr, "Error: --sample-rate does not apply to --stream\n");
         return 1;
     }
     if (bf16) setenv("MAGPIE_WEIGHTS", "bf16", 1);
@@ -147,6 +165,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     std::vector<float> audio;
+    std::vector<int16_t> pcm;  // --sample-rate: the device's 16-bit samples instead
     int rc = 0;
     if (stream) {
         magpie_stream_params sp;
@@ -166,8 +185,14 @@ int main(int argc, char **argv) {
             const std::vector<int32_t> codes = magpie_synthesize_codes_graph_reuse(ctx, tokens.data(), (int)tokens.size());
             const int n = (int)codes.size() / 8;
             if (codes.empty()) rc = 1;
-            magpie_codec_stream *cs = continuous ? magpie_codec_stream_init(codec) : nullptr;
-            if (continuous && !cs) rc = 1;
+            magpie_codec_stream *cs = continuous && !pcm_out ? magpie_codec_stream_init(codec) : nullptr;
+            if (continuous && !pcm_out && !cs) rc = 1;
+            // --sample-rate: the same chunks through the PCM calls, on one stream lane when the codec
+            // is continuous or the rate's filter has to span the chunks (any rate but 22050)
+            mp_codec_stream *ps = nullptr;
+            if (rc == 0 && pcm_out && (continuous || sample_rate != 22050) &&
+                mp_hip_codec_stream_create(codec->dev, 1, &ps) != MP_OK)
+                rc = 1;
             // stateless 32-frame codec chunks, frame-major -> codebook-major (magpie-tts.cpp:181-206);
             // --continuous-codec: the same chunks through one stream lane
             for (int c0 = 0; rc == 0 && c0 < n; c0 += 32) {
@@ -175,20 +200,39 @@ int main(int argc, char **argv) {
                 std::vector<int32_t> cb((size_t)8 * f);
                 for (int t = 0; t < f; ++t)
                     for (int k = 0; k < 8; ++k) cb[(size_t)k * f + t] = codes[(size_t)(c0 + t) * 8 + k];
+                if (pcm_out) {
+                    const int64_t cap = mp_hip_pcm_samples(f, sample_rate);
+                    const int32_t lane = 0;
+                    int64_t got = 0;
+                    const size_t at = pcm.size();
+                    pcm.resize(at + (size_t)cap);
+                    const int e = ps ? mp_hip_codec_stream_decode_pcm(ps, &lane, 1, cb.data(), &f, f, sample_rate, MP_PCM_S16,
+                                                                      pcm.data() + at, cap, &got)
+                                     : mp_hip_codec_decode_pcm(codec->dev, cb.data(), f, sample_rate, MP_PCM_S16,
+                                                               pcm.data() + at, cap, &got);
+                    if (e != MP_OK) {
+                        fprintf(stderr, "Error: %s\n", mp_hip_codec_error(codec->dev));
+                        rc = 1;
+                    }
+                    pcm.resize(at + (size_t)got);
+                    continue;
+                }
                 const std::vector<float> a = cs ? magpie_codec_stream_decode(cs, cb.data(), f) : magpie_codec_decode(codec, cb.data(), f);
                 if (a.empty()) rc = 1;
                 audio.insert(audio.end(), a.begin(), a.end());
             }
             magpie_codec_stream_free(cs);
+            mp_hip_codec_stream_free(ps);
         }
     }
-    if (rc == 0 && !write_wav(out, audio, 22050)) {
+    if (rc == 0 && !(pcm_out ? write_wav(out, pcm, sample_rate) : write_wav(out, audio, 22050))) {
         fprintf(stderr, "Error: Failed to write %s\n", out);
         rc = 1;
     }
     if (rc == 0) {
         if (quiet) printf("%s\n", out);
-        else fprintf(stderr, "Done! Generated %.2f seconds of audio.\n", audio.size() / 22050.0);
+        else fprintf(stderr, "Done! Generated %.2f seconds of audio.\n",
+                     pcm_out ? pcm.size() / (double)sample_rate : audio.size() / 22050.0);
     }
     magpie_codec_free(codec);
     magpie_free(ctx);
