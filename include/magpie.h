@@ -150,10 +150,17 @@ struct magpie_context {
     float attn_prior_eps;
     int attn_prior_lookahead, attn_prior_start;
     uint32_t attn_prior_layers;
+    // added: nucleus (top-p) and min-p truncation of the top_k candidates (mp_hip_set_sampling,
+    // magpie_hip.h): top_p in (0, 1], min_p in [0, 1). The defaults 1 and 0 = off, nothing
+    // changes and nothing new is called; otherwise temperature, top_k, top_p and min_p serve
+    // every utterance of the calls that honour cfg_scale and of the two *_queue calls.
+    float top_p, min_p;
+    bool sampling_applied;  // (internal: the device holds this context's settings)
     magpie_context()
         : n_threads(4), temperature(0.7f), top_k(80), speaker_id(0), codec(nullptr), seed(0),
           max_parallel_sentences(8), continuous_codec(false), cfg_scale(0.f),
-          attn_prior_eps(0.f), attn_prior_lookahead(5), attn_prior_start(0), attn_prior_layers(0) {}
+          attn_prior_eps(0.f), attn_prior_lookahead(5), attn_prior_start(0), attn_prior_layers(0),
+          top_p(1.f), min_p(0.f), sampling_applied(false) {}
 };
 // added: the attended text position of every frame of the last batch decoded with the attention
 // prior, utterance b's row at att[b * rows] (valid for f < its frame count); false without one

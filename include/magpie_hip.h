@@ -154,6 +154,47 @@ int mp_hip_set_kv_mode(mp_dev *dev, int kv_mode);
  *     would have to install a pair into two slots (a follow-up).
  * mp_hip_lt_sample is not affected. */
 int mp_hip_set_cfg(mp_dev *dev, float scale);
+/* Per-utterance sampling settings with nucleus (top-p) and min-p truncation. Applied, values
+ * copied, from the next mp_hip_begin_batch / mp_hip_decode_queue / mp_hip_decode_queue_stream.
+ * s = NULL or n = 0: off (the default), mp_params' temperature and top_k rule as ever and no
+ * launch, kernel or bit changes. n = 1: the entry serves every utterance. Otherwise entry i is
+ * utterance i's: n must equal B at mp_hip_begin_batch and N at a queue call, else MP_ERR_ARG
+ * there. While set, mp_params' temperature and top_k are not read (still checked).
+ *
+ * One decision of one utterance, on its masked logits l (after the guidance mix), in exact
+ * arithmetic:
+ *  1. the top_k largest, in descending value, ties by ascending id; w_i = exp((l_i - l_max) /
+ *     temperature) for rank i (w_0 = 1);
+ *  2. min_p keeps the ranks with w_i >= min_p, a prefix of length n1 (rank 0 always stays);
+ *  3. top_p: with S1 the prefix's sum, n is the smallest n >= 1 whose first n weights sum to
+ *     at least top_p S1 (top_p = 1: n = n1); equal logits across the cut enter lowest id first;
+ *  4. with u the decision's uniform number (the same counter stream as without the setting:
+ *     seed, stream_base + utterance, frame, codebook) and S_n the sum of the first n weights,
+ *     the code is the first rank whose inclusive prefix sum exceeds u S_n;
+ *  5. an utterance whose temperature is < 0.01 is greedy: the masked first-max argmax.
+ * The argmax, the EOS rule and argmax_codes are what they are without the setting. The f32
+ * order is one at every pick site and batch size (nucleus_draw, csrc/mp_fused.hpp), so an
+ * utterance of a batch or of a slot pool is its single run bit for bit; with top_p = 1 and
+ * min_p = 0 the draw is the same in exact arithmetic as mp_params' but not bit for bit (the
+ * sums run in another order). A guided pair shares its utterance's settings; a refilled pool
+ * slot takes its new utterance's.
+ *
+ * Every mode's pick goes through that one function: all weight modes, batch sizes, guidance,
+ * the attention prior, both slot pools, both streaming calls and mp_hip_lt_sample (entry 0
+ * stands for its temperature and top_k arguments). No mode refuses the setting. Brought to
+ * that function rather than refused: the Q8_0 mode's one-launch LT step has no nucleus form,
+ * so under the setting a Q8_0 batch runs the generic LT steps (pick kernel + o_net), and the
+ * generic steps take the pick kernel at every batch size. A batch whose utterances are all
+ * greedy runs the plain greedy launch list.
+ * MP_ERR_ARG, nothing changed: top_p outside (0, 1] or not finite, min_p outside [0, 1) or
+ * not finite, top_k outside 1..2024 at a temperature >= 0.01. */
+typedef struct mp_sampling {
+    float temperature;
+    int top_k;
+    float top_p;
+    float min_p;
+} mp_sampling;
+int mp_hip_set_sampling(mp_dev *dev, const mp_sampling *s, int n);
 /* Attention prior: monotonic cross-attention (XA) guidance, with the alignment out. It
  * follows the shape of the model's published attention prior but is this library's own
  * definition (that source is not available here). NULL is off (the default); applied from

@@ -93,7 +93,17 @@ const char *magpie_get_backend_name(magpie_context *ctx) { return ctx && ctx->mo
 
 // ctx->cfg_scale to the device, ahead of every begin_batch / queue call (mp_hip_set_cfg)
 // and the attention prior's fields (mp_hip_set_attn_prior; attn_prior_eps 0: off)
-static bool apply_cfg(const magpie_context *ctx) {
+static bool apply_cfg(magpie_context *ctx) {
+    // top_p / min_p (mp_hip_set_sampling): the defaults call nothing, unless a setting is to be taken back
+    const bool nucleus = ctx->top_p != 1.f || ctx->min_p != 0.f;
+    if (nucleus || ctx->sampling_applied) {
+        const mp_sampling s{ctx->temperature, ctx->top_k, ctx->top_p, ctx->min_p};
+        if (mp_hip_set_sampling(ctx->model.dev, nucleus ? &s : nullptr, nucleus ? 1 : 0) != MP_OK) {
+            fprintf(stderr, "magpie: %s\n", mp_hip_error(ctx->model.dev));
+            return false;
+        }
+        ctx->sampling_applied = nucleus;
+    }
     if (mp_hip_set_cfg(ctx->model.dev, ctx->cfg_scale) != MP_OK) {
         fprintf(stderr, "magpie: cfg_scale must be finite\n");
         return false;

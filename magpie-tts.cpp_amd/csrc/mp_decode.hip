@@ -311,8 +311,10 @@ constexpr int FIN_THREADS = 256;
 // Leading arguments (gemv_kernel's note): the pick's logits and step, which head the
 // kernel's dependent chain and are loaded first, the sampling switch, and the iteration
 // counter, the done flags and ts, which the entry reads next.
-__global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *logits, int *step, int *iter, int *done_flags,
-                                                                  unsigned long long *ts, int smp_on, FinP p) {
+// (NUC: lt_finalize_nuc_kernel's body, run by batches begun with mp_hip_set_sampling)
+template <bool NUC>
+__device__ __forceinline__ void lt_finalize_body(const float *logits, int *step, int *iter, int *done_flags,
+                                                 unsigned long long *ts, int smp_on, FinP &p) {
     p.logits = logits; p.step = step; p.iter = iter; p.done = done_flags; p.ts = ts;
     p.smp.on = smp_on & 1; p.smp.guided = smp_on >> 1;
     const unsigned long long t_start = ts_begin(p.ts);
@@ -376,7 +378,7 @@ __global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *l
         if (!quad) {
             __shared__ float scratch[2 * VCB];
             const int stp = p.step[b];
-            i0 = wave_pick(p.logits + ts_dep(t_start), p.ignore_eos || stp < 4, p.audio_bos,
+            i0 = wave_pick<NUC>(p.logits + ts_dep(t_start), p.ignore_eos || stp < 4, p.audio_bos,
                            p.audio_eos, p.smp, b, stp, NCB - 1, scratch, amax);
         }
         if (tid == 0) {
@@ -438,6 +440,16 @@ __global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *l
     ts_end(p.ts, t_start);
 }
 
+__global__ __launch_bounds__(FIN_THREADS) void lt_finalize_kernel(const float *logits, int *step, int *iter, int *done_flags,
+                                                                  unsigned long long *ts, int smp_on, FinP p) {
+    lt_finalize_body<false>(logits, step, iter, done_flags, ts, smp_on, p);
+}
+__global__ __launch_bounds__(FIN_THREADS) void lt_finalize_nuc_kernel(const float *logits, int *step, int *iter,
+                                                                      int *done_flags, unsigned long long *ts, int smp_on,
+                                                                      FinP p) {
+    lt_finalize_body<true>(logits, step, iter, done_flags, ts, smp_on, p);
+}
+
 // ---------------------------------------------------------------- host launchers
 template <int NB, int RW, int K, int PRO, int EPI>
 static hipError_t launch_gemv(const GemvP &p, hipStream_t s) {
@@ -483,8 +495,9 @@ static OpTable make_f32_ops() {
         t.lt_b = &launch_gemv<NB, 1, LTD, PRO_LT_ATTN, EPI_ADD_STORE>;
         // the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots
         // lt_pick_kernel + lt_bo (the fused prologue would run a wave's slots' picks in sequence)
+        // (a batch with per-utterance settings takes lt_pick_kernel's nucleus form + lt_bo at every size)
         if constexpr (NB < 8) t.lt_bg = &launch_gemv<NB, 1, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>;
-        else t.lt_bo = &launch_gemv<NB, 1, LTD, PRO_PLAIN, EPI_ADD_STORE>;
+        t.lt_bo = &launch_gemv<NB, 1, LTD, PRO_PLAIN, EPI_ADD_STORE>;
         // (batch 1: every list takes the head with the FFN merge as its prologue)
         if constexpr (NB > 1) t.lt_e = &launch_gemv<NB, 2, LTD, PRO_PLAIN, EPI_BIAS>;
     }
@@ -556,6 +569,7 @@ hipError_t op_sa_attn(const AttnP &p, int B, hipStream_t s) {
 // residual rows, the causal attention. The attention output goes to ltq (out),
 // the residual row to ltX; the o_net GEMV (PRO_PLAIN + EPI_ADD_STORE) follows.
 // Same functions, same arithmetic as the fused path: batches stay bit-identical.
+template <bool NUC>
 __global__ __launch_bounds__(64) void lt_pick_kernel(GemvP p) {
     __shared__ float wsc[2 * VCB];
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -570,8 +584,8 @@ __global__ __launch_bounds__(64) void lt_pick_kernel(GemvP p) {
     load_logits(p.logits, p.smp, b, lv);
     const int stp = p.step[b];
     int amax;
-    const int code = wave_pick_v(lv, p.ignore_eos || stp < 4, p.audio_bos, p.audio_eos, p.smp, b, stp, p.cb - 1, wsc,
-                                 amax);
+    const int code = wave_pick_v<NUC>(lv, p.ignore_eos || stp < 4, p.audio_bos, p.audio_eos, p.smp, b, stp, p.cb - 1, wsc,
+                                      amax);
     if (lane == 0) {
         p.codes_cur[b * NCB + p.cb - 1] = code;
         if (amax == p.audio_eos) p.smp.argeos[b] = 1;
@@ -592,7 +606,8 @@ hipError_t op_lt_pick(const GemvP &p, int NB, hipStream_t s) {
     if (!p.logits || !p.codes_cur || !p.qkvtab || !p.ptab || !p.lt_pos || !p.ltk || !p.ltv || !p.lk || !p.lv ||
         !p.ltX || !p.out || !p.step || !p.smp.cfg || !p.smp.argeos || p.cb < 1)
         return hipErrorInvalidValue;
-    mp::launch(lt_pick_kernel, dim3(NB), dim3(64), 0, s, p);
+    if (smp_nuc(p.smp)) mp::launch(lt_pick_kernel<true>, dim3(NB), dim3(64), 0, s, p);
+    else mp::launch(lt_pick_kernel<false>, dim3(NB), dim3(64), 0, s, p);
     return hipGetLastError();
 }
 
@@ -698,6 +713,8 @@ __global__ __launch_bounds__(MP_BLOCK) void slot_install_kernel(InstallP p) {
         p.nframes[b] = 0;
         p.argeos[b] = 0;
         p.cfg->stream[b] = p.stream;
+        p.cfg->temperature_s[b] = p.temperature; p.cfg->top_k_s[b] = p.top_k;
+        p.cfg->top_p_s[b] = p.top_p; p.cfg->min_p_s[b] = p.min_p;
         atomicSub(p.ndone, 1);  // the slot counted as done (lt_finalize_kernel's atomicAdd)
     }
     for (int k = tid; k < D; k += MP_BLOCK) {
@@ -897,6 +914,7 @@ __device__ __forceinline__ float4 lt_y_attend(const LtFfn2P &p, int b, bool wb0,
     return make_float4(x4.x + pos4.x + a.x / l, x4.y + pos4.y + a.y / l, x4.z + pos4.z + a.z / l,
                        x4.w + pos4.w + a.w / l);
 }
+template <bool NUC = false>
 __device__ __forceinline__ float4 lt_y_finish(const LtFfn2P &p, int b, bool wb0, float *wsc, LtYPre &r) {
     const int cb = p.cb;
     if (cb == 0) {
@@ -905,8 +923,8 @@ __device__ __forceinline__ float4 lt_y_finish(const LtFfn2P &p, int b, bool wb0,
     }
     const int stp = r.stp;
     int amax;
-    const int code = wave_pick_v(r.lv, p.ignore_eos || stp < 4, p.audio_bos, p.audio_eos, p.smp, b, stp, cb - 1, wsc,
-                                 amax);
+    const int code = wave_pick_v<NUC>(r.lv, p.ignore_eos || stp < 4, p.audio_bos, p.audio_eos, p.smp, b, stp, cb - 1, wsc,
+                                      amax);
     ts_phase<0>(p.f.ts, 0);  // profiling: code picked
     return lt_y_attend(p, b, wb0, code, amax, r, lt_gather(p, code));
 }
@@ -941,10 +959,11 @@ __device__ __forceinline__ int lt_pick_split(const LtFfn2P &p, int w, const LtYP
     return pick_exchange(bv, bi, code);
 }
 
+template <bool NUC = false>
 __device__ __forceinline__ float4 lt_y_slot(const LtFfn2P &p, int b, bool wb0, float *wsc) {
     LtYPre r;
     lt_y_load(p, b, r);
-    return lt_y_finish(p, b, wb0, wsc, r);
+    return lt_y_finish<NUC>(p, b, wb0, wsc, r);
 }
 
 // The LT step of codebook cb in f32 mode: y (lt_y_slot, every workgroup for itself;
@@ -952,7 +971,7 @@ __device__ __forceinline__ float4 lt_y_slot(const LtFfn2P &p, int b, bool wb0, f
 // partial sums exactly as lt_ffn_kernel (workgroup pb owns hidden units [16pb,
 // 16pb+16)). acc[b]: this thread's (output tid) partial sum of slot b; ys (nullable):
 // slot 0's y for the caller.
-template <int NB>
+template <int NB, bool NUC = false>
 __device__ __forceinline__ void lt_step_body(const LtFfn2P &p, int pb, int dep, float (&accs)[NB], float *ys) {
     constexpr int U = LTF / LT_FFN_P, UPW = U / MP_NWAVES;
     static_assert(U % MP_NWAVES == 0 && U % 4 == 0 && LTD == MP_BLOCK, "unit split");
@@ -1002,7 +1021,7 @@ __device__ __forceinline__ void lt_step_body(const LtFfn2P &p, int pb, int dep, 
         }
     } else {
         for (int b = w; b < NB; b += MP_NWAVES) {
-            const float4 y = b == w ? lt_y_finish(p, b, pb == 0, wsc_all[w], yp) : lt_y_slot(p, b, pb == 0, wsc_all[w]);
+            const float4 y = b == w ? lt_y_finish<NUC>(p, b, pb == 0, wsc_all[w], yp) : lt_y_slot<NUC>(p, b, pb == 0, wsc_all[w]);
             if (b == 0) ts_phase<1>(p.f.ts, 0);  // profiling: y (gathers + attention)
             y_ln(b, y);
         }
@@ -1037,18 +1056,31 @@ __device__ __forceinline__ void lt_step_body(const LtFfn2P &p, int pb, int dep, 
 // positions' rows, the step, the LN weights, cb and the sampling switch -- and ts. The FFN
 // weights' pointers stay in the struct: 14 dwords hold no more, and the weights are not
 // needed before y.
-template <int NB>
-__global__ __launch_bounds__(MP_BLOCK) void lt_ffn2_kernel(const float *logits, float *ltk, float *ltv, const int *step,
-                                                           const float *lnw, unsigned long long *ts, int cb, int smp_on,
-                                                           LtFfn2P p) {
+template <int NB, bool NUC>
+__device__ __forceinline__ void lt_ffn2_body(const float *logits, float *ltk, float *ltv, const int *step, const float *lnw,
+                                             unsigned long long *ts, int cb, int smp_on, LtFfn2P &p) {
     p.logits = logits; p.ltk = ltk; p.ltv = ltv; p.step = step; p.f.lnw = lnw; p.f.ts = ts; p.cb = cb;
     p.smp.on = smp_on & 1; p.smp.guided = smp_on >> 1;
     const unsigned long long t_start = ts_begin(p.f.ts);
     float accs[NB];
-    lt_step_body<NB>(p, blockIdx.x, ts_dep(t_start), accs, nullptr);
+    lt_step_body<NB, NUC>(p, blockIdx.x, ts_dep(t_start), accs, nullptr);
 #pragma unroll
     for (int b = 0; b < NB; ++b) p.f.part[ltp_idx(b, blockIdx.x, threadIdx.x)] = accs[b];
     ts_end(p.f.ts, t_start);
+}
+
+template <int NB>
+__global__ __launch_bounds__(MP_BLOCK) void lt_ffn2_kernel(const float *logits, float *ltk, float *ltv, const int *step,
+                                                           const float *lnw, unsigned long long *ts, int cb, int smp_on,
+                                                           LtFfn2P p) {
+    lt_ffn2_body<NB, false>(logits, ltk, ltv, step, lnw, ts, cb, smp_on, p);
+}
+// (the nucleus instantiation: batches begun with mp_hip_set_sampling, codebooks >= 1)
+template <int NB>
+__global__ __launch_bounds__(MP_BLOCK) void lt_ffn2_nuc_kernel(const float *logits, float *ltk, float *ltv, const int *step,
+                                                               const float *lnw, unsigned long long *ts, int cb, int smp_on,
+                                                               LtFfn2P p) {
+    lt_ffn2_body<NB, true>(logits, ltk, ltv, step, lnw, ts, cb, smp_on, p);
 }
 
 hipError_t op_lt_ffn2(const LtFfn2P &p, int NB, hipStream_t s) {
@@ -1057,13 +1089,18 @@ hipError_t op_lt_ffn2(const LtFfn2P &p, int NB, hipStream_t s) {
         p.cb < 0 || p.cb >= NCB)
         return hipErrorInvalidValue;
 #define LT_FFN2_ARGS p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts, p.cb, smp_flags(p.smp), p
+    // (codebook 0's step picks nothing: the plain kernel serves every batch there)
+    const bool nuc = smp_nuc(p.smp) && p.cb > 0;
+#define LT_FFN2_CASE(n) \
+    case n: \
+        if (nuc) mp::launch(lt_ffn2_nuc_kernel<n>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); \
+        else mp::launch(lt_ffn2_kernel<n>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); \
+        break;
     switch (NB) {
-    case 1: mp::launch(lt_ffn2_kernel<1>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
-    case 2: mp::launch(lt_ffn2_kernel<2>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
-    case 4: mp::launch(lt_ffn2_kernel<4>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
-    case 8: mp::launch(lt_ffn2_kernel<8>, dim3(LT_FFN_P), dim3(MP_BLOCK), 0, s, LT_FFN2_ARGS); break;
+    LT_FFN2_CASE(1) LT_FFN2_CASE(2) LT_FFN2_CASE(4) LT_FFN2_CASE(8)
     default: return hipErrorInvalidValue;
     }
+#undef LT_FFN2_CASE
 #undef LT_FFN2_ARGS
     return hipGetLastError();
 }
@@ -1086,9 +1123,9 @@ __device__ __forceinline__ float bf16_round(float v) { return __uint_as_float((u
 __device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 // (leading arguments: lt_ffn2_kernel's)
-__global__ __launch_bounds__(MP_BLOCK) void lt_slot_kernel(const float *logits, float *ltk, float *ltv, const int *step,
-                                                           const float *lnw, unsigned long long *ts, int cb, int smp_on,
-                                                           LtFfn2P p) {
+template <bool NUC>
+__device__ __forceinline__ void lt_slot_body(const float *logits, float *ltk, float *ltv, const int *step, const float *lnw,
+                                             unsigned long long *ts, int cb, int smp_on, LtFfn2P &p) {
     p.logits = logits; p.ltk = ltk; p.ltv = ltv; p.step = step; p.f.lnw = lnw; p.f.ts = ts; p.cb = cb;
     p.smp.on = smp_on & 1; p.smp.guided = smp_on >> 1;
     const unsigned long long t_start = ts_begin(p.f.ts);
@@ -1122,7 +1159,7 @@ __global__ __launch_bounds__(MP_BLOCK) void lt_slot_kernel(const float *logits, 
         yw = lt_pick_split(p, w, yp, lq, g, code);
         if (w == yw) y = lt_y_attend(p, b, q == 0, code, code, yp, g);
     } else if (w == 0) {
-        y = lt_y_finish(p, b, q == 0, wsc, yp);
+        y = lt_y_finish<NUC>(p, b, q == 0, wsc, yp);
     }
     if (w == yw) {
         if (q == 0) *(float4 *)((float *)p.f.y + (size_t)b * LTD + 4 * lane) = y;
@@ -1199,13 +1236,28 @@ __global__ __launch_bounds__(MP_BLOCK) void lt_slot_kernel(const float *logits, 
     }
     ts_end(p.f.ts, t_start);
 }
+__global__ __launch_bounds__(MP_BLOCK) void lt_slot_kernel(const float *logits, float *ltk, float *ltv, const int *step,
+                                                           const float *lnw, unsigned long long *ts, int cb, int smp_on,
+                                                           LtFfn2P p) {
+    lt_slot_body<false>(logits, ltk, ltv, step, lnw, ts, cb, smp_on, p);
+}
+// (the nucleus instantiation: batches begun with mp_hip_set_sampling, codebooks >= 1)
+__global__ __launch_bounds__(MP_BLOCK) void lt_slot_nuc_kernel(const float *logits, float *ltk, float *ltv, const int *step,
+                                                               const float *lnw, unsigned long long *ts, int cb, int smp_on,
+                                                               LtFfn2P p) {
+    lt_slot_body<true>(logits, ltk, ltv, step, lnw, ts, cb, smp_on, p);
+}
 hipError_t op_lt_slot(const LtFfn2P &p, int NB, hipStream_t s) {
     if (!p.f.y || !p.f.lnw || !p.w1h || !p.w2h || !p.f.part || (p.gh && (!p.f.out || !p.iter || !p.hx_err)) || !p.ltX || !p.ltk || !p.ltv ||
         !p.qkvtab || !p.votab || !p.ptab || !p.lt_pos || !p.logits || !p.codes_cur || !p.step || !p.smp.cfg ||
         !p.smp.argeos || p.cb < 0 || p.cb >= NCB || NB < 1 || NB > 32)
         return hipErrorInvalidValue;
-    mp::launch(lt_slot_kernel, dim3(LTS_P, NB), dim3(MP_BLOCK), 0, s, p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts, p.cb,
-               smp_flags(p.smp), p);
+    if (smp_nuc(p.smp) && p.cb > 0)
+        mp::launch(lt_slot_nuc_kernel, dim3(LTS_P, NB), dim3(MP_BLOCK), 0, s, p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts,
+                   p.cb, smp_flags(p.smp), p);
+    else
+        mp::launch(lt_slot_kernel, dim3(LTS_P, NB), dim3(MP_BLOCK), 0, s, p.logits, p.ltk, p.ltv, p.step, p.f.lnw, p.f.ts,
+                   p.cb, smp_flags(p.smp), p);
     return hipGetLastError();
 }
 
@@ -1437,7 +1489,10 @@ hipError_t op_lt_kvo(const GemvP &p, int NB, hipStream_t s) {
 hipError_t op_finalize(const FinP &p, int B, hipStream_t s) {
     if (!p.smp.cfg || !p.smp.argeos) return hipErrorInvalidValue;
     if (p.x && (!p.emb || !p.pos_emb || p.pos_rows < 1)) return hipErrorInvalidValue;
-    mp::launch(lt_finalize_kernel, dim3(B), dim3(FIN_THREADS), 0, s, p.logits, p.step, p.iter, p.done, p.ts, smp_flags(p.smp), p);
+    if (smp_nuc(p.smp))
+        mp::launch(lt_finalize_nuc_kernel, dim3(B), dim3(FIN_THREADS), 0, s, p.logits, p.step, p.iter, p.done, p.ts, smp_flags(p.smp), p);
+    else
+        mp::launch(lt_finalize_kernel, dim3(B), dim3(FIN_THREADS), 0, s, p.logits, p.step, p.iter, p.done, p.ts, smp_flags(p.smp), p);
     return hipGetLastError();
 }
 

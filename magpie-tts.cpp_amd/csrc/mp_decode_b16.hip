@@ -654,8 +654,9 @@ static OpTable make_b16_ops() {
         t.lt_b = &launch_b16<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE, true>;
         // the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots
         // lt_pick_kernel, then o_net + residual
+        // (a batch with per-utterance settings takes lt_pick_kernel's nucleus form + lt_bo at every size)
         if constexpr (NB < 8) t.lt_bg = &launch_b16<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD, true>;
-        else t.lt_bo = &launch_b16<NB, LTD, PRO_PLAIN, EPI_ADD_STORE, true>;
+        t.lt_bo = &launch_b16<NB, LTD, PRO_PLAIN, EPI_ADD_STORE, true>;
         t.lt_c = &launch_b16<NB, LTD, PRO_LN, EPI_GELU, true>;
         t.lt_d = &launch_b16<NB, LTF, PRO_PLAIN, EPI_ADD_STORE, true>;
     }

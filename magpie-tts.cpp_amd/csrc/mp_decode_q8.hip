@@ -542,6 +542,9 @@ hipError_t op_lt_slot_q8(const LtSlotQ8P &p, int NB, hipStream_t s) {
                       !g.smp.argeos)))
         return hipErrorInvalidValue;
 #define LTQ8_ARGS p.g.logits, p.g.ltk, p.g.ltv, p.g.step, p.g.lt_pos, p.ts, p.g.cb, smp_flags(p.g.smp), p
+    // (its weights stay in registers across the pick: no room for the nucleus form's keys and
+    // weights without scratch, so a batch with per-utterance settings runs build_lt's generic steps)
+    if (smp_nuc(p.g.smp)) return hipErrorInvalidValue;
     if (p.part) mp::launch(lt_slot_q8_kernel<true, true, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
     else if (p.wot) mp::launch(lt_slot_q8_kernel<true, false, 64>, dim3(64, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
     else if (NB >= 8) mp::launch(lt_slot_q8_kernel<false, false, 32>, dim3(32, NB), dim3(MP_BLOCK), 0, s, LTQ8_ARGS);
@@ -1068,8 +1071,9 @@ static OpTable make_q8_ops() {
     t.lt_b = &launch_q8<NB, LTD, PRO_LT_ATTN, EPI_ADD_STORE>;
     // the LT step's pick + attention + o_net in one launch, below 8 slots; from 8 slots
     // lt_pick_kernel, then o_net + residual
+    // (a batch with per-utterance settings takes lt_pick_kernel's nucleus form + lt_bo at every size)
     if constexpr (NB < 8) t.lt_bg = &launch_q8<NB, LTD, PRO_LTARG_ATTN, EPI_LTX_ADD>;
-    else t.lt_bo = &launch_q8<NB, LTD, PRO_PLAIN, EPI_ADD_STORE>;
+    t.lt_bo = &launch_q8<NB, LTD, PRO_PLAIN, EPI_ADD_STORE>;
     t.lt_e = &launch_q8<NB, LTD, PRO_PLAIN, EPI_BIAS>;
     if constexpr (NB == 1) {
         // LT in_proj of a caller-supplied normalised hidden (magpie_local_transformer_sample_all)

@@ -69,7 +69,147 @@ __device__ __forceinline__ void cfg_logit_rows(const float *logits, const Sampli
 __device__ __forceinline__ void load_logits(const float *logits, const Sampling &smp, int b, float (&lv)[PICK_R]) {
     cfg_logit_rows<PICK_R>(logits, smp, b, 0, lv);
 }
-// wave_pick on logits already loaded by load_logits (lv is modified)
+// The nucleus pick (mp_hip_set_sampling): slot b's draw under its own
+// temperature T, top-k k, top-p P and min-p m, on the masked logits lv whose maximum is M and
+// first-max index bi. In exact arithmetic: the k largest logits in descending value (ties by
+// ascending id) with w_i = exp((l_i - M) / T); the prefix with w_i >= m, of sum S1; of it the
+// shortest prefix whose sum reaches P S1 (P = 1: all of it), of sum S_n; the code is the first
+// rank whose inclusive prefix sum exceeds u S_n. T < 0.01: the slot is greedy (wave-uniform
+// return of the argmax).
+// Nothing is sorted and nothing leaves the registers: lane l holds ids l + 64 r with their
+// 32-bit order-preserving keys and weights, and each of the three cuts is a threshold search
+// over the key space, one bit per probe from the top:
+//   top-k:  the largest t with count(key >= t) >= k (the sequential pick's radix select);
+//   top-p:  the largest t with mass(key >= t) >= P S1;
+//   draw:   the largest t with mass(key >= t) > u S_n: the drawn code's key.
+// mass(.) is the sum of the weights of the elements still in the set whose key passes, the
+// others contributing +0, always as 32 per-lane adds in row order and then wave_sum's DPP
+// tree. A fixed-order sum of non-negative terms is monotone in the set, so each bisection is
+// valid in f32, and one order serves every pick site. The elements at a search's final key are
+// equal; they enter in ascending id through a ballot / popcount carry across the rows, as many
+// as the remaining mass asks for (a division in f64 per cut, none per candidate). The scalar
+// comparisons are made in f64, where P S1 and u S_n are exact products, so rows of equal
+// logits (integer sums) cut and draw exactly. min-p needs no order at all: it is a test of each
+// lane's own weights. A probe is 32 compare-adds and one wave reduction whatever k is: no step
+// is O(k) on one lane, none is O(k^2), and there is no LDS traffic and no scratch.
+__device__ __forceinline__ float nucleus_mass(const unsigned (&key)[PICK_R], const float (&w)[PICK_R], unsigned cand) {
+    float s = 0.f;
+#pragma unroll
+    for (int r = 0; r < PICK_R; ++r) s += key[r] >= cand ? w[r] : 0.f;
+    return wave_sum(s);
+}
+// keeps in the set (w > 0 marks membership; dropped elements get w = 0) what lies above key t
+// and the first `lim` set members at t in ascending id; `em`: bit r set = row r's element is
+// a candidate at all
+__device__ __forceinline__ void nucleus_keep(const unsigned (&key)[PICK_R], float (&w)[PICK_R], unsigned &em, unsigned t,
+                                             int lim) {
+    const unsigned long long below = (1ull << (threadIdx.x & 63)) - 1ull;
+    int ties = 0;
+#pragma unroll
+    for (int r = 0; r < PICK_R; ++r) {
+        const bool in = (em >> r) & 1u, tie = in && key[r] == t;
+        const unsigned long long bt = __ballot(tie);
+        const bool keep = in && (key[r] > t || (tie && ties + __popcll(bt & below) < lim));
+        ties += __popcll(bt);
+        if (!keep) { w[r] = 0.f; em &= ~(1u << r); }
+    }
+}
+// the set members at key t: their number and their (common) weight
+__device__ __forceinline__ int nucleus_ties(const unsigned (&key)[PICK_R], const float (&w)[PICK_R], unsigned em, unsigned t,
+                                            float &wt) {
+    int n = 0;
+    float v = 0.f;
+#pragma unroll
+    for (int r = 0; r < PICK_R; ++r) {
+        const bool tie = ((em >> r) & 1u) && key[r] == t;
+        n += __popcll(__ballot(tie));
+        v = tie ? w[r] : v;
+    }
+    wt = wave_max(v);
+    return n;
+}
+__device__ inline int nucleus_draw(const float (&lv)[PICK_R], float M, int bi, const Sampling &smp, int b, int step, int cb) {
+    const SmpCfg *c = smp.cfg;
+    const float T = c->temperature_s[b];
+    if (T < 0.01f) return bi;  // a greedy utterance in a sampling batch (wave-uniform)
+    constexpr int R = PICK_R;
+    const int lane = threadIdx.x & 63;
+    const int k = min(max(c->top_k_s[b], 1), VCB);
+    const float P = c->top_p_s[b], m = c->min_p_s[b];
+    unsigned key[R];
+    float w[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const unsigned u = __float_as_uint(lv[r]);
+        const bool real = (lane + 64 * r) < VCB;
+        key[r] = real ? ((u & 0x80000000u) ? ~u : (u | 0x80000000u)) : 0u;
+        w[r] = real ? expf((lv[r] - M) / T) : 0.f;
+    }
+    // top-k (every real id when k = VCB: no search), then min-p on the lane's own weights
+    unsigned em = 0u;
+#pragma unroll
+    for (int r = 0; r < R; ++r) em |= (key[r] != 0u ? 1u : 0u) << r;
+    if (k < VCB) {
+        unsigned t = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = t | (1u << bit);
+            int cn = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) cn += key[r] >= cand;
+            if ((int)wave_sum((float)cn) >= k) t = cand;
+        }
+        int cgt = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) cgt += key[r] > t;
+        nucleus_keep(key, w, em, t, k - (int)wave_sum((float)cgt));
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (!(w[r] >= m)) { w[r] = 0.f; em &= ~(1u << r); }
+    // top-p: the shortest prefix reaching P S1 (P = 1: the whole min-p prefix, by definition)
+    if (P < 1.0f) {
+        const double target = (double)P * (double)nucleus_mass(key, w, 0u);
+        unsigned t = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned cand = t | (1u << bit);
+            if ((double)nucleus_mass(key, w, cand) >= target) t = cand;
+        }
+        float wt;
+        const int nt = nucleus_ties(key, w, em, t, wt);
+        const double rest = target - (double)(t == 0xffffffffu ? 0.f : nucleus_mass(key, w, t + 1u));
+        const int q = wt > 0.f ? (int)fmin(ceil(rest / (double)wt), (double)nt) : nt;
+        nucleus_keep(key, w, em, t, max(q, 1));
+    }
+    // the draw: the key at which the descending cumulative mass first exceeds u S_n, and among
+    // the members at that key the one the remainder reaches
+    const float u = mp_uniform(c->seed, c->stream[b], step, cb);
+    const double x = (double)u * (double)nucleus_mass(key, w, 0u);
+    unsigned t = 0;
+    for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = t | (1u << bit);
+        if ((double)nucleus_mass(key, w, cand) > x) t = cand;
+    }
+    float wt;
+    const int nt = nucleus_ties(key, w, em, t, wt);
+    const double rest = x - (double)(t == 0xffffffffu ? 0.f : nucleus_mass(key, w, t + 1u));
+    const int j = wt > 0.f ? min(max((int)fmin(floor(rest / (double)wt), (double)nt), 0), nt - 1) : nt - 1;  // 0-based
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int ties = 0, code = 1 << 30;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const bool tie = ((em >> r) & 1u) && key[r] == t;
+        const unsigned long long bt = __ballot(tie);
+        if (tie && ties + __popcll(bt & below) == j) code = lane + 64 * r;
+        ties += __popcll(bt);
+    }
+    code = wave_min_u(code);
+    return (code < 0 || code >= VCB) ? bi : code;
+}
+
+// wave_pick on logits already loaded by load_logits (lv is modified). NUC: the batch was begun
+// with per-utterance settings (mp_hip_set_sampling), and a sampling slot draws by nucleus_draw;
+// the instantiation is the launcher's choice, so the kernels of plain batches hold no trace of it.
+template <bool NUC = false>
 __device__ inline int wave_pick_v(float (&lv)[PICK_R], bool forbid_eos, int audio_bos, int audio_eos,
                                   const Sampling &smp, int stream, int step, int cb, float *scratch, int &amax) {
     const int lane = threadIdx.x & 63;
@@ -108,6 +248,7 @@ __device__ inline int wave_pick_v(float (&lv)[PICK_R], bool forbid_eos, int audi
     if (bi < 0 || bi >= VCB) bi = 0;
     amax = bi;
     if (!smp.on) return bi;
+    if constexpr (NUC) return nucleus_draw(lv, bv, bi, smp, stream, step, cb);
     const float temp = smp.cfg->temperature;
     const float M = bv;
     const int k = min(max(smp.cfg->top_k, 1), VCB);
@@ -192,11 +333,12 @@ __device__ inline int wave_pick_v(float (&lv)[PICK_R], bool forbid_eos, int audi
     return code;
 }
 // (logits: the batch's rows; `stream`, the slot, picks its row -- and its partner's)
+template <bool NUC = false>
 __device__ inline int wave_pick(const float *logits, bool forbid_eos, int audio_bos, int audio_eos, const Sampling &smp,
                                 int stream, int step, int cb, float *scratch, int &amax) {
     float lv[PICK_R];
     load_logits(logits, smp, stream, lv);
-    return wave_pick_v(lv, forbid_eos, audio_bos, audio_eos, smp, stream, step, cb, scratch, amax);
+    return wave_pick_v<NUC>(lv, forbid_eos, audio_bos, audio_eos, smp, stream, step, cb, scratch, amax);
 }
 
 // The greedy pick split over a workgroup's MP_NWAVES waves (batch-1 LT step, finalize):

@@ -136,9 +136,21 @@ struct SmpCfg {                // device-resident, so a captured graph serves an
     // (cfg_logit_rows, mp_fused.hpp), so both arrive at the same code. -1: unpaired.
     float cfg_scale;
     int partner[32];
+    // Per-utterance settings (mp_hip_set_sampling), read by the nucleus pick only
+    // (nucleus_draw, mp_fused.hpp): slot b's temperature (< 0.01: the slot is greedy), top-k,
+    // top-p and min-p. Filled by mp_hip_begin_batch, written for a refilled slot beside
+    // stream[] (slot_install_kernel), equal in the two slots of a guided pair; padding
+    // slots carry slot 0's. Batches begun without the setting read the scalars above.
+    float temperature_s[32];
+    int top_k_s[32];
+    float top_p_s[32];
+    float min_p_s[32];
 };
 struct Sampling {
-    int on;                    // temperature >= 0.01 (baked into the captured graph)
+    int on;                    // bit 0: some utterance samples (temperature >= 0.01; baked into the
+                               // captured graph); bit 1 (host side only, SMP_NUC): the batch was begun
+                               // with mp_hip_set_sampling, so its launchers take the kernels' nucleus
+                               // instantiations, which read the per-slot settings
     const SmpCfg *cfg;
     int *argeos;               // [B] 1 once a codebook's argmax was EOS this frame (4343-4346)
     int *amax;                 // optional [B][8]: every codebook's argmax (magpie_sample_result.argmax_codes)
@@ -147,6 +159,8 @@ struct Sampling {
 };
 // `on` and `guided` as the one leading kernel argument of the LT step / finalize kernels
 __host__ __device__ inline int smp_flags(const Sampling &s) { return (s.on ? 1 : 0) | (s.guided ? 2 : 0); }
+constexpr int SMP_NUC = 2;
+inline bool smp_nuc(const Sampling &s) { return (s.on & SMP_NUC) != 0; }
 
 // LT FFN up + GELU + FFN down in one launch (lt_ffn_kernel): workgroup p owns
 // hidden units [p*16, p*16+16) and writes its share of FFN down, part[b][p][256]
@@ -240,6 +254,8 @@ struct InstallP {
     int T, Tmax;
     // slot state
     int b, spk, stream, audio_bos, max_steps;
+    float temperature, top_p, min_p;  // the utterance's sampling settings (SmpCfg's per-slot entries)
+    int top_k;
     int *Tn, *spkn, *pos, *step, *done, *nframes, *argeos, *codes_prev, *codes_out, *ndone;
     SmpCfg *cfg;
     // x[b] = the BOS frame's embedding at position CTX (embed_kernel's arithmetic)

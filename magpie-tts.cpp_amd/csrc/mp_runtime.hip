@@ -148,6 +148,10 @@ struct mp_dev {
     // batch's launch list carries the PRIOR forms and xa_align_kernel
     mp_attn_prior prior_set{};
     bool prior_wanted = false, prior = false;
+    // mp_hip_set_sampling: the per-utterance settings asked for (empty: off), and the batch's
+    // Sampling::on (bit 0: some utterance samples; mp::SMP_NUC: begun with the setting)
+    std::vector<mp_sampling> smp_set;
+    int smp_on = 0;
     float *lp = nullptr, *xa_scores = nullptr;  // [NB][Tmax], [NB][L][Tmax]
     int *att_pos = nullptr, *att_out = nullptr;  // [NB], [NB][max_steps + 1]
     mp::PriorCfg *priorcfg = nullptr;
@@ -577,7 +581,9 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
             merge(l2.f);
             if (int rc = head(cb, NB == 1 ? tb.lt_em : tb.lt_e, NB == 1, 256)) return rc;
         }
-    } else if (m.weight_mode == MP_WEIGHTS_Q8 && m.lt_o8 && m.lt_out8 && m.lt_ff2q && !io.lt_only && io.ltyg) {
+    } else if (m.weight_mode == MP_WEIGHTS_Q8 && m.lt_o8 && m.lt_out8 && m.lt_ff2q && !io.lt_only && io.ltyg && !mp::smp_nuc(smp)) {
+        // (a batch with per-utterance settings takes the generic steps below: lt_slot_q8_kernel
+        // has no room for the nucleus pick)
         // Q8_0 mode: position 0's q|k|v (the Q8_0 GEMV), then per codebook the LT step as
         // LTQ_P workgroups per slot (lt_slot_q8_kernel: pick, attention, Q8_0 o_net, F32
         // FFN, partial sums merged through granules) and the Q8_0 head on its output
@@ -623,8 +629,9 @@ int build_lt(mp_dev *dev, const mp::LtIo &io, int NB, std::vector<mp::OpRec> &ou
             g.out_ld = 256; g.addsrc = io.ltX;
             if (int rc = e.gemv("lt_b", fam(m.lt_o8).lt_b, g, weight_bytes(m.lt_o8, F) * (256.0 * 256) + A * act * (256 * 5)))
                 return rc;
-        } else if (NB >= 8) {
-            // large batches: the per-slot pick + gathers + attention as one wave per slot
+        } else if (NB >= 8 || mp::smp_nuc(smp)) {
+            // large batches, and every batch begun with per-utterance settings (lt_pick_kernel's
+            // nucleus form; the fused prologue has none): the per-slot pick + gathers + attention as one wave per slot
             // (lt_pick_kernel), then o_net + residual; the same arithmetic as lt_bg
             g = base(cb);
             g.logits = io.logits; g.codes_cur = io.codes_cur; g.qkvtab = m.lt_qkvtab; g.ptab = m.lt_ptab;
@@ -691,7 +698,7 @@ int build_iteration(mp_dev *dev, std::vector<mp::OpRec> &out) {
     auto fam = [&](const mp::QW &q) -> const mp::OpTable & { return q ? tq : tb; };
     // algorithmic bytes: weights at their stored width (Q8_0: 34 B per 32), activations f32
     const double F = b16 ? 2.0 : 4.0, A = 4.0, act = (double)NB;
-    const bool sampling = dev->params.temperature >= 0.01f;
+    const int sampling = dev->smp_on;
     const mp::Sampling smp{sampling, dev->smpcfg, dev->argeos, nullptr, dev->guided};
     const Emit e{dev, out, NB, true, mp::LtDumpP{}};
     // attention prior: the O-projection + XA launch's PRIOR form, the direct XA's, and
@@ -1215,6 +1222,42 @@ int mp_hip_set_cfg(mp_dev *dev, float scale) {
     return MP_OK;
 }
 
+int mp_hip_set_sampling(mp_dev *dev, const mp_sampling *s, int n) {
+    if (!dev || n < 0) return MP_ERR_ARG;
+    if (!s || n == 0) { dev->smp_set.clear(); return MP_OK; }
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(s[i].top_p) || !(s[i].top_p > 0.f) || s[i].top_p > 1.f)
+            return fail(dev, MP_ERR_ARG, "sampling: top_p must be in (0, 1]");
+        if (!std::isfinite(s[i].min_p) || s[i].min_p < 0.f || !(s[i].min_p < 1.f))
+            return fail(dev, MP_ERR_ARG, "sampling: min_p must be in [0, 1)");
+        if (s[i].temperature >= 0.01f && (s[i].top_k < 1 || s[i].top_k > mp::VCB))
+            return fail(dev, MP_ERR_ARG, "sampling: top_k must be in 1..2024 when sampling");
+    }
+    dev->smp_set.assign(s, s + n);
+    return MP_OK;
+}
+// The settings of n utterances (mp_hip_set_sampling) into us; empty: the setting is off.
+static int resolve_sampling(mp_dev *dev, int n, std::vector<mp_sampling> &us) {
+    us.clear();
+    const size_t have = dev->smp_set.size();
+    if (have == 0) return MP_OK;
+    if (have != 1 && have != (size_t)n)
+        return fail(dev, MP_ERR_ARG, "mp_hip_set_sampling: one entry, or one per utterance of the call");
+    for (int i = 0; i < n; ++i) us.push_back(dev->smp_set[have == 1 ? 0 : i]);
+    return MP_OK;
+}
+// Sampling::on of a batch or queue: its utterances' settings us, or the shared params
+static int sampling_on(const std::vector<mp_sampling> &us, const mp_params &params) {
+    if (us.empty()) return params.temperature >= 0.01f ? 1 : 0;
+    for (const mp_sampling &u : us)
+        if (u.temperature >= 0.01f) return 1 | mp::SMP_NUC;
+    return 0;  // every utterance greedy: the plain greedy lists
+}
+// slot b's per-slot entries of cfg
+static void cfg_slot(mp::SmpCfg &cfg, int b, const mp_sampling &u) {
+    cfg.temperature_s[b] = u.temperature; cfg.top_k_s[b] = u.top_k; cfg.top_p_s[b] = u.top_p; cfg.min_p_s[b] = u.min_p;
+}
+
 int mp_hip_set_attn_prior(mp_dev *dev, const mp_attn_prior *prior) {
     if (!dev) return MP_ERR_ARG;
     if (!prior) { dev->prior_wanted = false; return MP_OK; }
@@ -1293,8 +1336,10 @@ static int check_utterances(mp_dev *dev, const int32_t *tokens, const int32_t *n
 
 // mp_hip_begin_batch. pin_tmax > 0 (the slot pool): the batch's text stride is pin_tmax,
 // not its own longest text, so a later utterance of up to pin_tmax tokens fits any slot.
+// us: the B utterances' own sampling settings (empty: params' for all); smp_on: Sampling::on of
+// the batch (a slot pool's covers its whole queue).
 static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int B,
-                       int tmax, const mp_params *params, int pin_tmax) {
+                       int tmax, const mp_params *params, int pin_tmax, const std::vector<mp_sampling> &us, int smp_on) {
     if (!dev) return MP_ERR_ARG;
     if (!dev->loaded) return fail(dev, MP_ERR_STATE, "no model loaded");
     const int bmax = mp_hip_max_batch(dev);
@@ -1338,10 +1383,11 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
     const bool trace = params->trace_hidden != 0;
     const bool same = dev->NB > 0 && dev->B == B && dev->guided == guided && dev->prior == prior && dev->Tmax == Tmax && dev->max_steps == max_steps &&
                       (dev->trace != nullptr) == trace && dev->params.ignore_eos == params->ignore_eos &&
-                      (dev->params.temperature >= 0.01f) == (params->temperature >= 0.01f) &&
+                      dev->smp_on == smp_on &&
                       dev->params.emit_eos_frame == params->emit_eos_frame &&
                       dev->kv16 == (dev->kv_mode == MP_KV_BF16) && dev->xa_direct == want_xa_direct(dev, Tmax);
     dev->params = *params;
+    dev->smp_on = smp_on;
     if (!same) {
         if (int rc = alloc_batch(dev, B, guided, prior, Tmax, max_steps, trace)) return rc;
     }
@@ -1363,8 +1409,14 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
         mp::SmpCfg cfg{params->temperature, params->top_k, (unsigned long long)params->seed, params->stream_base, {},
                        dev->cfg_scale, {}};
         for (int b = 0; b < 32; ++b) { cfg.stream[b] = params->stream_base + b; cfg.partner[b] = -1; }
-        if (guided)  // the pair draws from the utterance's stream
-            for (int b = 0; b < B; ++b) { cfg.partner[b] = B + b; cfg.partner[B + b] = b; cfg.stream[B + b] = cfg.stream[b]; }
+        // per-utterance settings (read by a batch begun with them only); padding slots carry slot 0's
+        const mp_sampling shared{params->temperature, params->top_k, 1.0f, 0.0f};
+        for (int b = 0; b < 32; ++b) cfg_slot(cfg, b, us.empty() ? shared : us[b < B ? b : 0]);
+        if (guided)  // the pair draws from the utterance's stream, under the utterance's settings
+            for (int b = 0; b < B; ++b) {
+                cfg.partner[b] = B + b; cfg.partner[B + b] = b; cfg.stream[B + b] = cfg.stream[b];
+                cfg_slot(cfg, B + b, us.empty() ? shared : us[b]);
+            }
         HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
         HIPCHK(hipMemsetAsync(dev->argeos, 0, NB * 4, dev->stream));
         if (prior) {  // the prior's settings likewise
@@ -1383,7 +1435,10 @@ static int begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_toke
 
 int mp_hip_begin_batch(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens, const int32_t *speaker, int B,
                        int tmax, const mp_params *params) {
-    return begin_batch(dev, tokens, n_tokens, speaker, B, tmax, params, 0);
+    std::vector<mp_sampling> us;  // (a call begin_batch refuses anyway is refused there, as ever)
+    if (dev && dev->loaded && B >= 1 && B <= mp_hip_max_batch(dev) && params)
+        if (int rc = resolve_sampling(dev, B, us)) return rc;
+    return begin_batch(dev, tokens, n_tokens, speaker, B, tmax, params, 0, us, params ? sampling_on(us, *params) : 0);
 }
 
 // magpie_encode_text (magpie.cpp:2284-2374) on its own: the text encoder of one
@@ -1624,6 +1679,7 @@ struct PoolRun {
     int seq = 0;
     bool drained = false;
     std::vector<char> claimed;
+    std::vector<mp_sampling> us;  // utterance i's settings (mp_hip_set_sampling; empty: params' for all)
     int cur = 0;          // the staging workspace the next install reads
     bool staged = false;  // ... holds an utterance: one is always staged ahead while any remain
     mp::Pinned h;  // [ndone 4 | done 16 | nframes 16 | codes max_steps x 8]
@@ -1676,6 +1732,10 @@ static int pool_install(mp_dev *dev, PoolRun &r, StageWs &s, int b) {
     if (batch_reads_kp(dev)) { p.skp = (const uint4 *)s.w.kp; p.svp = (const uint4 *)s.w.vp; p.kp = (uint4 *)dev->kp; p.vp = (uint4 *)dev->vp; }
     p.T = s.n; p.Tmax = dev->Tmax;
     p.b = b; p.spk = r.speaker[s.utt]; p.stream = r.params.stream_base + s.utt;
+    {   // the utterance's settings travel with it, like its stream
+        const mp_sampling u = r.us.empty() ? mp_sampling{r.params.temperature, r.params.top_k, 1.0f, 0.0f} : r.us[s.utt];
+        p.temperature = u.temperature; p.top_k = u.top_k; p.top_p = u.top_p; p.min_p = u.min_p;
+    }
     p.audio_bos = dev->m.audio_bos; p.max_steps = dev->max_steps;
     p.Tn = dev->T; p.spkn = dev->spk; p.pos = dev->pos; p.step = dev->step; p.done = dev->done; p.nframes = dev->nframes;
     p.argeos = dev->argeos; p.codes_prev = dev->codes_prev; p.codes_out = dev->codes_out; p.ndone = dev->ndone;
@@ -1728,10 +1788,17 @@ static int pool_start(mp_dev *dev, PoolRun &r, std::vector<int> &occ) {
             spk[b] = r.speaker[occ[b]];
             memcpy(&tok[(size_t)b * r.tmax], r.tokens + (size_t)occ[b] * r.tmax, (size_t)nt[b] * 4);
         }
-        if (int rc = begin_batch(dev, tok.data(), nt.data(), spk.data(), B, r.tmax, &r.params, r.tmax)) return rc;
+        std::vector<mp_sampling> us;
+        if (!r.us.empty())
+            for (int b = 0; b < B; ++b) us.push_back(r.us[occ[b]]);
+        if (int rc = begin_batch(dev, tok.data(), nt.data(), spk.data(), B, r.tmax, &r.params, r.tmax, us, sampling_on(r.us, r.params)))
+            return rc;
         // the draw streams follow the utterances, not the slots
         mp::SmpCfg cfg{r.params.temperature, r.params.top_k, (unsigned long long)r.params.seed, r.params.stream_base, {}, 0.f, {}};
-        for (int b = 0; b < 32; ++b) { cfg.stream[b] = r.params.stream_base + (b < B ? occ[b] : b); cfg.partner[b] = -1; }
+        for (int b = 0; b < 32; ++b) {
+            cfg.stream[b] = r.params.stream_base + (b < B ? occ[b] : b); cfg.partner[b] = -1;
+            cfg_slot(cfg, b, us.empty() ? mp_sampling{r.params.temperature, r.params.top_k, 1.0f, 0.0f} : us[b < B ? b : 0]);
+        }
         HIPCHK(hipMemcpyAsync(dev->smpcfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));
         HIPCHK(hipStreamSynchronize(dev->stream));
     }
@@ -1806,7 +1873,10 @@ static int pool_call(mp_dev *dev, const int32_t *tokens, const int32_t *n_tokens
     if (int rc = check_params(dev, params, &max_steps)) return rc;
     if (int rc = check_utterances(dev, tokens, n_tokens, speaker, N, tmax, &Tmax)) return rc;
     HIPCHK(hipSetDevice(dev->device));
+    std::vector<mp_sampling> us;  // entry i: utterance i's (mp_hip_set_sampling)
+    if (int rc = resolve_sampling(dev, N, us)) return rc;
     PoolRun r{tokens, n_tokens, speaker, N, tmax, slots, poll, *params, next, done, user};  // released on return
+    r.us = us;
     r.claimed.assign(N, 0);
     const int rc = run(r);
     hipStreamSynchronize(dev->stream);
@@ -2208,12 +2278,16 @@ int mp_hip_lt_sample(mp_dev *dev, const float *hidden, float temperature, int to
         io.lt_only = 1;
         io.max_steps = 1;
     }
-    io.sampling = temperature >= 0.01f;
+    // mp_hip_set_sampling's entry 0, when set, stands for the call's temperature and top_k
+    const bool own = !dev->smp_set.empty();
+    const mp_sampling us{own ? dev->smp_set[0] : mp_sampling{temperature, top_k, 1.0f, 0.0f}};
+    io.sampling = us.temperature >= 0.01f ? (own ? 1 | mp::SMP_NUC : 1) : 0;
     io.ignore_eos = forbid_eos != 0;
     // step: a call counter >= 4 (so only forbid_eos masks EOS), also the draw's step index
     const int step = 4 + dev->lt_calls++;
     mp::SmpCfg cfg{temperature, top_k, (unsigned long long)seed, -1, {-1}, 0.f, {}};
     for (int &pb : cfg.partner) pb = -1;
+    cfg_slot(cfg, 0, us);
     HIPCHK(hipMemcpyAsync(io.hidden, hidden, 768 * 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(io.step, &step, 4, hipMemcpyHostToDevice, dev->stream));
     HIPCHK(hipMemcpyAsync(io.cfg, &cfg, sizeof cfg, hipMemcpyHostToDevice, dev->stream));

@@ -69,6 +69,11 @@ class mp_attn_prior(ctypes.Structure):
                 ("layers", ctypes.c_uint32)]
 
 
+class mp_sampling(ctypes.Structure):
+    _fields_ = [("temperature", ctypes.c_float), ("top_k", ctypes.c_int), ("top_p", ctypes.c_float),
+                ("min_p", ctypes.c_float)]
+
+
 # (name, restype, argtypes) of every symbol include/magpie_hip.h declares
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -123,6 +128,7 @@ SYMBOLS = [
     ("mp_hip_set_stream_codec_mode", _I, [_P, _I]),
     ("mp_hip_set_cfg", _I, [_P, ctypes.c_float]),
     ("mp_hip_get_trace_uncond", _I, [_P, _P]),
+    ("mp_hip_set_sampling", _I, [_P, ctypes.POINTER(mp_sampling), _I]),
     ("mp_hip_set_attn_prior", _I, [_P, ctypes.POINTER(mp_attn_prior)]),
     ("mp_hip_get_alignment", _I, [_P, _P]),
     ("mp_hip_alignment_shape", _I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
@@ -144,7 +150,8 @@ OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue", "mp_hip_codec_stream_cr
             "mp_hip_codec_stream_reset", "mp_hip_codec_stream_free", "mp_hip_set_stream_codec_mode",
             "mp_hip_codec_stream_decode_ragged", "mp_hip_decode_queue_stream", "mp_hip_set_cfg",
             "mp_hip_get_trace_uncond", "mp_hip_set_attn_prior", "mp_hip_get_alignment",
-            "mp_hip_alignment_shape", "mp_hip_pcm_samples", "mp_hip_codec_decode_pcm", "mp_hip_codec_stream_decode_pcm"}
+            "mp_hip_alignment_shape", "mp_hip_pcm_samples", "mp_hip_codec_decode_pcm", "mp_hip_codec_stream_decode_pcm",
+            "mp_hip_set_sampling"}
 
 _lib = None
 
@@ -305,6 +312,29 @@ class Device:
         self._check(self.lib.mp_hip_set_cfg(self.h, float(scale)))
         self.cfg_scale = float(scale)
 
+    def set_sampling(self, settings=None) -> None:
+        """mp_hip_set_sampling: per-utterance sampling settings with top-p / min-p truncation,
+        from the next begin() / synthesize_queue() / stream_queue(). None is off (temperature
+        and top_k of the call rule); one setting serves every utterance; a list holds one per
+        utterance. A setting is a dict or a (temperature, top_k, top_p, min_p) tuple; missing
+        entries default to temperature 0.7, top_k 80, top_p 1, min_p 0. A temperature < 0.01
+        makes that utterance greedy. lt_sample() honours the first entry."""
+        if not hasattr(self.lib, "mp_hip_set_sampling"):
+            raise MagpieError("this libmagpie_hip.so has no per-utterance sampling")
+        if settings is None:
+            self._check(self.lib.mp_hip_set_sampling(self.h, None, 0))
+            return
+        if isinstance(settings, dict) or (isinstance(settings, tuple) and not isinstance(settings[0], (dict, tuple, list))):
+            settings = [settings]
+
+        def one(s):
+            if isinstance(s, dict):
+                s = (s.get("temperature", 0.7), s.get("top_k", 80), s.get("top_p", 1.0), s.get("min_p", 0.0))
+            t, k, pp, mp_ = (tuple(s) + (0.7, 80, 1.0, 0.0)[len(s):])[:4]
+            return mp_sampling(float(t), int(k), float(pp), float(mp_))
+        arr = (mp_sampling * len(settings))(*[one(s) for s in settings])
+        self._check(self.lib.mp_hip_set_sampling(self.h, arr, len(settings)))
+
     def set_attn_prior(self, epsilon: Optional[float] = None, lookahead: int = 5, start_step: int = 0,
                        layers: int = 0) -> None:
         """mp_hip_set_attn_prior: monotonic cross-attention guidance from the next begin();
@@ -383,12 +413,16 @@ class Device:
     def synthesize_queue(self, tokens: Sequence[Sequence[int]], speakers: Optional[Sequence[int]] = None,
                          slots: int = 8, poll: int = 8, next=None, max_dec_steps: int = 500,
                          temperature: float = 0.0, top_k: int = 80, ignore_eos: bool = False, seed: int = 0,
-                         stream_base: int = 0, emit_eos_frame: bool = False, trace: bool = False) -> QueueResult:
+                         stream_base: int = 0, emit_eos_frame: bool = False, trace: bool = False,
+                         sampling=None) -> QueueResult:
         """mp_hip_decode_queue (continuous batching): every utterance of `tokens` through
         `slots` decode slots, a finished slot refilled from the queue between two graph
         replays. next() -> index of the next utterance to run, or -1 once drained (None:
         0, 1, ... in order). Utterance i draws from stream stream_base + i and equals its
-        single run. Returns the per-utterance codes plus the loop's counts."""
+        single run. sampling: set_sampling()'s argument, applied first (None: the device's
+        setting stays). Returns the per-utterance codes plus the loop's counts."""
+        if sampling is not None:
+            self.set_sampling(sampling)
         n = len(tokens)
         tmax = max((len(t) for t in tokens), default=1)
         tok = np.zeros((max(n, 1), max(tmax, 1)), np.int32)
@@ -431,14 +465,16 @@ class Device:
                      speakers: Optional[Sequence[int]] = None, slots: int = 8, frames_per_chunk: int = 4,
                      continuous: bool = False, next=None, max_dec_steps: int = 500, temperature: float = 0.0,
                      top_k: int = 80, ignore_eos: bool = False, seed: int = 0, stream_base: int = 0,
-                     emit_eos_frame: bool = False, trace: bool = False) -> QueueResult:
+                     emit_eos_frame: bool = False, trace: bool = False, sampling=None) -> QueueResult:
         """mp_hip_decode_queue_stream (the streaming slot pool): synthesize_queue's utterances
         through `slots` refilled slots, each utterance's audio handed out chunk by chunk:
         on_audio(utt, samples) -> bool per chunk of up to frames_per_chunk frames (False stops
         that utterance), then on_audio(utt, None) once when the utterance has ended.
         continuous: an utterance's chunks on a lane of a stateful codec stream, so its
         concatenated audio is Codec.decode of its frames (default: stateless chunks). Returns
-        synthesize_queue's result plus first_audio_ms."""
+        synthesize_queue's result plus first_audio_ms. sampling: as synthesize_queue's."""
+        if sampling is not None:
+            self.set_sampling(sampling)
         n = len(tokens)
         tmax = max((len(t) for t in tokens), default=1)
         tok = np.zeros((max(n, 1), max(tmax, 1)), np.int32)

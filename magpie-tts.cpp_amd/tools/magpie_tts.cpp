@@ -27,6 +27,10 @@ void usage(const char *prog) {
             "  -s, --speaker ID     speaker id (default: 0)\n"
             "  --temp FLOAT         sampling temperature (default: 0.7, 0 = greedy)\n"
             "  --top-k INT          top-k sampling (default: 80)\n"
+            "  --top-p P            nucleus sampling: the smallest set of the top-k candidates whose\n"
+            "                       probability reaches P, in (0, 1] (default: 1 = off)\n"
+            "  --min-p M            drop candidates below M times the best one's probability, in [0, 1)\n"
+            "                       (default: 0 = off)\n"
             "  --seed N             sampling stream seed (default: 0)\n"
             "  --cfg-scale S        classifier-free guidance scale (default: 0 = off; the model's\n"
             "                       published setting is 2.5; f32 and bf16 weights)\n"
@@ -92,7 +96,7 @@ int main(int argc, char **argv) {
     const char *model = "weights/magpie-357m-f32.gguf", *codec_path = "weights/nano-codec-f32.gguf";
     const char *text = nullptr, *out = "output.wav";
     int speaker = 0, top_k = 80;
-    float temp = 0.7f, cfg_scale = 0.f, prior_eps = 0.f;
+    float temp = 0.7f, cfg_scale = 0.f, prior_eps = 0.f, top_p = 1.f, min_p = 0.f;
     int prior_w = 5, prior_start = 0, sample_rate = -1;  // -1: no --sample-rate
     unsigned long long seed = 0;
     bool quiet = false, stream = false, bf16 = false, continuous = false;
@@ -115,6 +119,8 @@ int main(int argc, char **argv) {
         else if (a == "--top-k") top_k = atoi(val("--top-k"));
         else if (a == "--seed") seed = strtoull(val("--seed"), nullptr, 10);
         else if (a == "--cfg-scale") cfg_scale = (float)atof(val("--cfg-scale"));
+        else if (a == "--top-p") top_p = (float)atof(val("--top-p"));
+        else if (a == "--min-p") min_p = (float)atof(val("--min-p"));
         else if (a == "--attn-prior-eps") prior_eps = (float)atof(val("--attn-prior-eps"));
         else if (a == "--attn-prior-lookahead") prior_w = atoi(val("--attn-prior-lookahead"));
         else if (a == "--attn-prior-start") prior_start = atoi(val("--attn-prior-start"));
@@ -155,6 +161,8 @@ int main(int argc, char **argv) {
     ctx->seed = seed;
     ctx->continuous_codec = continuous;
     ctx->cfg_scale = cfg_scale;
+    ctx->top_p = top_p;
+    ctx->min_p = min_p;
     ctx->attn_prior_eps = prior_eps;
     ctx->attn_prior_lookahead = prior_w;
     ctx->attn_prior_start = prior_start;
