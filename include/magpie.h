@@ -248,6 +248,10 @@ void magpie_codec_free(magpie_codec *codec);
 bool magpie_codec_load(const std::string &path, magpie_codec &codec, magpie_backend_type backend = MAGPIE_BACKEND_AUTO);
 // codes: [num_codebooks][n_frames] codebook-major; returns n_frames * 1024 samples
 std::vector<float> magpie_codec_decode(magpie_codec *codec, const int32_t *codes, int n_frames);
+// Added: the same at `speed` times the model's speaking rate (0.5..2.0, rounded to whole percent),
+// time-stretched on the device at the voice's own pitch (magpie_hip.h, speaking rate): f32 at
+// 22 050 Hz, ceil(n_frames * 1024 / speed) samples. Empty vector on failure.
+std::vector<float> magpie_codec_decode_speed(magpie_codec *codec, const int32_t *codes, int n_frames, float speed);
 // Added: a stateful streaming decode of one utterance (one lane of mp_hip_codec_stream_*).
 // Consecutive chunks (codes [num_codebooks][n_frames] each) give, concatenated, the samples
 // one magpie_codec_decode of all the frames gives, bit for bit. reset: the next chunk starts

@@ -529,6 +529,48 @@ int mp_hip_codec_decode_pcm(mp_codec *c, const int32_t *codes, int n_frames, int
 int mp_hip_codec_stream_decode_pcm(mp_codec_stream *s, const int32_t *lane_ids, int n, const int32_t *codes,
                                    const int32_t *n_frames, int max_frames, int rate, int format, void *out,
                                    int64_t stride, int64_t *n_out);
+
+/* --- speaking rate: WSOLA time stretch --------------------------------------------- */
+/* The codec's waveform stretched in time at its own pitch, on the device, between the codec's
+ * last kernel and the resampler (tsm_kernel, mp_codec.hip). The model has no duration input: a
+ * slower or faster voice is a stretched waveform. No reference counterpart.
+ *
+ * Definition (the one place: the kernel, the host code and the test restate it).
+ *   x: the codec's f32 waveform at 22 050 Hz, Lin = n_frames * 1024 samples, x[j] = 0 for j < 0
+ *   and j >= Lin. speed_pct: an integer in 50..200, the speed in percent (anything else:
+ *   MP_ERR_ARG). speed_pct = 100 is the identity: y = x exactly, no stretch kernel is launched and
+ *   the call is mp_hip_codec_decode_pcm bit for bit. Otherwise Ls = ceil(Lin * 100 / speed_pct)
+ *   output samples (64-bit integers).
+ *   Constants: H = 512 (hop and overlap length), D = 256 (search radius). Weights, computed on
+ *   the host in double and stored as f32: w[i] = sin^2(pi (i + 0.5) / 1024) for i < 512, and
+ *   w2[i] = 1 - sin^2(pi (i + 0.5) / 1024) rounded from double the same way (not 1.0f - w[i]).
+ *   Segments: M = ceil(Ls / H) of them, starting at p_m in x. p_0 = 0. For m >= 1:
+ *     r = p_{m-1} + H                               where the previous segment would continue
+ *     a = floor(m H speed_pct / 100)                the nominal position
+ *     candidates c = a + d, d = -D..D, c >= 0       (a - D >= 0 at every speed_pct >= 50: no
+ *                                                    candidate is ever excluded; c = 0 is reached
+ *                                                    at speed_pct = 50, m = 1, d = -D)
+ *     C(d) = sum_{i < H} x[r + i] x[c + i],   E(d) = sum_{i < H} x[c + i]^2
+ *     score(d) = C(d) / sqrtf(E(d) + 1e-9f)         division and square root correctly rounded
+ *     p_m = a + d*, d* the first (lowest) d holding the greatest score
+ *   f32 order of C and E: eight chains s_j, j = i mod 8, each starting at 0 and taking its terms
+ *   i ascending as s_j = fmaf(x[r + i], x[c + i], s_j) (E: fmaf(x[c + i], x[c + i], s_j)), then
+ *   ((s_0 + s_1) + (s_2 + s_3)) + ((s_4 + s_5) + (s_6 + s_7)). It depends on nothing else.
+ *   Output, n < Ls, m = n / H, i = n - m H:
+ *     m = 0: y[n] = x[n];  m >= 1: y[n] = fmaf(w[i], x[p_m + i], w2[i] * x[p_{m-1} + H + i])
+ *   y then goes through the resampler and the format conversion above unchanged, as their x with
+ *   N = Ls: ceil(Ls L / M) samples at rate R, f32 or S16.
+ * Not covered (follow-up): the stream lanes (mp_hip_codec_stream_*) and the mp_audio_cb callbacks
+ * take no speed; a lane would have to carry p_{m-1} and the input tail no segment has read yet. */
+/* samples a decode of n_frames frames yields at speed_pct and `rate`: ceil(Ls L / M); MP_ERR_ARG
+ * (< 0) for another rate, a speed_pct outside 50..200 or n_frames < 0 */
+int64_t mp_hip_tsm_samples(int n_frames, int speed_pct, int rate);
+/* mp_hip_codec_decode_pcm with the stretch in front of the resampler. starts (nullable) receives
+ * p_m for the M = ceil(Ls / 512) segments (none written at speed_pct = 100). The checks, the
+ * MP_ERR_ARG for a cap too small (the message names the size needed) and mp_hip_codec_last_ms
+ * are mp_hip_codec_decode_pcm's; last_ms covers the stretch. */
+int mp_hip_codec_decode_pcm_speed(mp_codec *c, const int32_t *codes, int n_frames, int speed_pct, int rate, int format,
+                                  void *out, int64_t cap, int64_t *n_out, int32_t *starts);
 void mp_hip_codec_free(mp_codec *c);
 const char *mp_hip_codec_error(mp_codec *c);
 

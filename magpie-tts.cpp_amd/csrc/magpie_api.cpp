@@ -4,6 +4,7 @@
 #include "../../include/magpie.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -288,6 +289,21 @@ std::vector<float> magpie_codec_decode(magpie_codec *codec, const int32_t *codes
     std::vector<float> audio((size_t)n_frames * codec->hparams.hop_length);
     if (mp_hip_codec_decode(codec->dev, codes, n_frames, audio.data()) != MP_OK) {
         fprintf(stderr, "magpie_codec_decode: %s\n", mp_hip_codec_error(codec->dev));
+        return {};
+    }
+    return audio;
+}
+// Added: the decode at `speed` times the model's speaking rate (mp_hip_codec_decode_pcm_speed).
+std::vector<float> magpie_codec_decode_speed(magpie_codec *codec, const int32_t *codes, int n_frames, float speed) {
+    const int pct = (int)lroundf(speed * 100.f);
+    const int64_t n = n_frames > 0 ? mp_hip_tsm_samples(n_frames, pct, 22050) : -1;
+    if (!codec || !codec->dev || !codes || n < 0) {
+        fprintf(stderr, "magpie_codec_decode_speed: invalid args (speed in 0.5..2.0)\n");
+        return {};
+    }
+    std::vector<float> audio((size_t)n);
+    if (mp_hip_codec_decode_pcm_speed(codec->dev, codes, n_frames, pct, 22050, MP_PCM_F32, audio.data(), n, nullptr, nullptr) != MP_OK) {
+        fprintf(stderr, "magpie_codec_decode_speed: %s\n", mp_hip_codec_error(codec->dev));
         return {};
     }
     return audio;

@@ -1384,6 +1384,189 @@ __global__ __launch_bounds__(RS_WG) void resample_kernel(RsP p) {
     }
 }
 
+// ---------------------------------------------------------------- speaking rate: the WSOLA stretch
+// The time stretch include/magpie_hip.h defines (mp_hip_codec_decode_pcm_speed), between
+// post_conv_kernel's waveform and the resampler: segment m of 512 outputs starts at p_m, the
+// candidate within 256 samples of a_m = floor(512 m speed / 100) that continues segment m - 1
+// best (normalised cross-correlation with the template x[p_{m-1} + 512 ..]), and is cross-faded
+// with that template.
+//
+// One workgroup per utterance (the call takes one; a batch of them would be the grid); the
+// chain p_1, p_2, ... is sequential, the work of a segment is not: 513 candidates x 512 taps x (C, E). Per segment the workgroup keeps
+// W_m = x[a_m - 256 .. a_m + 1280) in LDS (6 KB, two of them): its first 1024 samples are the
+// span every candidate reads, and whatever p_m turns out to be, the next template
+// x[p_m + 512 .. p_m + 1024) lies inside it, so no load ever waits for a choice. W_{m+1}
+// depends on m alone: its global loads (16-byte, into registers) are issued before segment m's
+// search and land in segment m - 1's buffer once the blend has read it.
+//  * Waves 0-3: a lane pair owns 4 adjacent candidates (4q .. 4q + 3), lane h of the pair the
+//    chains j = 4h .. 4h + 3 of the definition's eight. Per 8 taps a lane reads 7 span values
+//    (two ds_read_b128 at 16 q + 32 n + 16 h bytes: adjacent lanes, adjacent 16-byte slots,
+//    conflict-free) and 4 template values (broadcasts) for 16 fmaf of C and 7 of E (E's chains
+//    of adjacent candidates share their terms: 7 distinct ones for the 16); the pair's halves
+//    meet through one DPP quad_perm per sum: (s0+s1)+(s2+s3) from lane 0 plus (s4+s5)+(s6+s7)
+//    from lane 1, the definition's order.
+//  * Wave 4: 513 = 4 * 128 + 1. The last candidate (d = +256) is 16 lanes' work, lane j + 8 e
+//    running chain j of C (e = 0) or E (e = 1), 64 dependent fmaf beside the other waves' 1472.
+//  * First maximum: each lane's own (ascending, strict), wave_max, wave_min_u of the indices
+//    that hold it, the five waves' results merged through LDS (lower index on equal scores).
+//  * The 512 blended outputs are written by the whole workgroup, consecutive lanes consecutive
+//    addresses, from the two LDS windows; a lane keeps its two (w, w2) pairs in registers.
+// a_m advances by 512 speed / 100 in integers (quotient and remainder carried), so no 64-bit
+// division runs on the device. Plain VALU fmaf: the search is a 513 x 512 Toeplitz product in
+// f32 (0.26 M multiply-adds, twice), no MFMA shape.
+constexpr int TSM_H = 512, TSM_D = 256, TSM_NC = 2 * TSM_D + 1;
+constexpr int TSM_WIN = 2 * TSM_D + 2 * TSM_H;  // samples of W_m
+constexpr int TSM_WG = 320, TSM_LD4 = TSM_WIN / 4 + 1;  // 16-byte loads that cover a window from the boundary below it
+struct TsmP {
+    const float *x;  // [Lin] the codec's waveform
+    const float *w;  // [2][512]: w, w2
+    float *y;        // [Ls]
+    int *starts;     // [M] p_m
+    int Lin, Ls;     // input samples (a multiple of 1024), output samples
+    int M;           // segments: ceil(Ls / 512)
+    int speed;       // percent, 50..200
+};
+
+// W = x[lo .. lo + TSM_WIN), zero outside [0, Lin): this thread's 16-byte loads, from the
+// boundary at or below lo (lo >= 0; Lin is a multiple of 4, so a load is all inside or all outside)
+__device__ __forceinline__ void tsm_fetch(const float *x, int Lin, int lo, float4 (&q)[2]) {
+    const int base = lo & ~3;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int v = threadIdx.x + u * TSM_WG, j = base + 4 * v;
+        q[u] = v < TSM_LD4 && j < Lin ? *(const float4 *)(x + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+// into LDS with W[0] = x[lo]: the up to 3 samples below lo and the ones past the window are dropped
+__device__ __forceinline__ void tsm_store(float *W, int lo, const float4 (&q)[2]) {
+    const int off = lo & 3;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int v = threadIdx.x + u * TSM_WG, k = 4 * v - off;
+        if (v >= TSM_LD4) continue;
+        const float e[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (k + t >= 0 && k + t < TSM_WIN) W[k + t] = e[t];
+    }
+}
+
+__global__ __launch_bounds__(TSM_WG) void tsm_kernel(TsmP p) {
+    __shared__ __attribute__((aligned(16))) float win[2][TSM_WIN];
+    __shared__ float bv[TSM_WG / 64];
+    __shared__ int bi[TSM_WG / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const TsmP &u = p;
+    const float *x = p.x;
+    float *y = p.y;
+    int *starts = p.starts;
+    // a_m = floor(m K / 100), K = 512 speed: quotient and remainder per step
+    const int K = TSM_H * u.speed, kq = K / 100, kr = K % 100;
+    int a = kq, rem = kr;  // a_1
+    // the blend weights of this thread's outputs i = tid and tid + 320
+    const int i1 = tid + TSM_WG;
+    const float w_0 = p.w[tid], v_0 = p.w[TSM_H + tid];
+    const float w_1 = i1 < TSM_H ? p.w[i1] : 0.f, v_1 = i1 < TSM_H ? p.w[TSM_H + i1] : 0.f;
+    // segment 0 is x itself; its window starts at 0, segment 1's at a_1 - D
+    float4 q[2];
+    tsm_fetch(x, u.Lin, 0, q);
+    tsm_store(win[0], 0, q);
+    if (u.M > 1) {
+        tsm_fetch(x, u.Lin, a - TSM_D, q);
+        tsm_store(win[1], a - TSM_D, q);
+    }
+    lds_sync();
+    for (int i = tid; i < TSM_H; i += TSM_WG)
+        if (i < u.Ls) y[i] = win[0][i];
+    if (tid == 0) starts[0] = 0;
+    int tb = TSM_H;  // the template's offset in the previous window: p_{m-1} + H - lo_{m-1}
+    for (int m = 1; m < u.M; ++m) {
+        const float *cur = win[m & 1], *tp = win[(m - 1) & 1] + tb;
+        const int lo = a - TSM_D;  // candidate k is c = lo + k, cur[k + i] = x[c + i]
+        int an = a + kq, remn = rem + kr;
+        if (remn >= 100) { remn -= 100; ++an; }
+        const bool more = m + 1 < u.M;
+        if (more) tsm_fetch(x, u.Lin, an - TSM_D, q);
+        float best;
+        int bk;
+        if (wv < 4) {
+            const int h = tid & 1, k0 = (tid >> 1) * 4;
+            // E's chain j of candidate k squares the samples cur[k + j + 8 n], the very terms in the
+            // very order of chain j + 1 of candidate k - 1: one accumulator per k + j, 7 for the 16
+            float C[4][4], E[7];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) C[k][j] = 0.f;
+#pragma unroll
+            for (int t = 0; t < 7; ++t) E[t] = 0.f;
+            const float *sp = cur + k0 + 4 * h, *tq = tp + 4 * h;
+#pragma unroll 2
+            for (int n = 0; n < TSM_H / 8; ++n, sp += 8, tq += 8) {
+                const float4 s0 = *(const float4 *)sp, s1 = *(const float4 *)(sp + 4);
+                const float s[7] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z};
+                const float t[4] = {tq[0], tq[1], tq[2], tq[3]};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) C[k][j] = fmaf(t[j], s[j + k], C[k][j]);
+#pragma unroll
+                for (int z = 0; z < 7; ++z) E[z] = fmaf(s[z], s[z], E[z]);
+            }
+            best = -INFINITY;
+            bk = k0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float ch = (C[k][0] + C[k][1]) + (C[k][2] + C[k][3]), eh = (E[k] + E[k + 1]) + (E[k + 2] + E[k + 3]);
+                const float co = dpp_mov<0xB1>(ch), eo = dpp_mov<0xB1>(eh);  // the pair's other half
+                const float c = h ? co + ch : ch + co, e = h ? eo + eh : eh + eo;
+                const float sc = c / sqrtf(e + 1e-9f);
+                if (lo + k0 + k >= 0 && sc > best) { best = sc; bk = k0 + k; }
+            }
+        } else {
+            // candidate 512: lane j + 8 e runs chain j of C (e = 0) or E (e = 1); the wave's other
+            // lanes repeat them
+            const int j = lane & 7, e = (lane >> 3) & 1;
+            const float *sp = cur + (TSM_NC - 1) + j, *tq = tp + j;
+            float acc = 0.f;
+#pragma unroll 8
+            for (int n = 0; n < TSM_H / 8; ++n) {
+                const float sv = sp[8 * n];
+                acc = fmaf(e ? sv : tq[8 * n], sv, acc);
+            }
+            float s[16];
+#pragma unroll
+            for (int t = 0; t < 16; ++t) s[t] = __shfl(acc, t);
+            const float c = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+            const float en = ((s[8] + s[9]) + (s[10] + s[11])) + ((s[12] + s[13]) + (s[14] + s[15]));
+            best = c / sqrtf(en + 1e-9f);
+            bk = TSM_NC - 1;
+        }
+        // the workgroup's first maximum: the greater score, or the same score at a lower candidate
+        const float wbest = wave_max(best);
+        const int wk = wave_min_u(best == wbest ? bk : 0x7fffffff);
+        if (lane == 0) { bv[wv] = wbest; bi[wv] = wk; }
+        lds_sync();
+        float gb = bv[0];
+        int kb = bi[0];
+#pragma unroll
+        for (int t = 1; t < TSM_WG / 64; ++t)
+            if (bv[t] > gb || (bv[t] == gb && bi[t] < kb)) { gb = bv[t]; kb = bi[t]; }
+        kb = min(max(kb, 0), TSM_NC - 1);  // (an all-NaN wave leaves 0x7fffffff: keep every LDS index inside)
+        if (tid == 0) starts[m] = lo + kb;
+        // y[m H + i] = w[i] x[p_m + i] + w2[i] x[p_{m-1} + H + i]
+        const int n0 = m * TSM_H;
+        if (n0 + tid < u.Ls) y[n0 + tid] = fmaf(w_0, cur[kb + tid], v_0 * tp[tid]);
+        if (i1 < TSM_H && n0 + i1 < u.Ls) y[n0 + i1] = fmaf(w_1, cur[kb + i1], v_1 * tp[i1]);
+        lds_sync();  // the previous window has been read for the last time: the next one takes its place
+        if (more) tsm_store(win[(m - 1) & 1], an - TSM_D, q);
+        lds_sync();
+        tb = kb + TSM_H;
+        a = an;
+        rem = remn;
+    }
+}
+
 }  // namespace mpc
 
 // ====================================================================== runtime
@@ -1420,6 +1603,13 @@ struct mp_codec {
     void *rs_out = nullptr;
     size_t rs_desc_cap = 0, rs_out_cap = 0;  // chunks, bytes
     mp::Pinned rs_desc_pin, rs_out_pin;
+    // the stretch (mp_hip_codec_decode_pcm_speed): the blend weights [2][512], built when first
+    // used; the call's stretched waveform (the resampler's input) and segment starts
+    mp::DevBlocks tsm_table, tsm_mem;
+    float *tsm_w = nullptr, *tsm_y = nullptr;
+    int *tsm_starts = nullptr;
+    size_t tsm_y_cap = 0, tsm_starts_cap = 0;  // samples, segments
+    mp::Pinned tsm_starts_pin;
     // diagnostics (MAGPIE_CODEC_TS=stage,block,file): the phase stamps of one rb_kernel launch
     mp::DevBlocks ts_mem;
     unsigned long long *ts_dev = nullptr;
@@ -1857,6 +2047,8 @@ int rs_rate_index(int rate) {
 // outputs after S input samples: ceil(S L / M)
 long long rs_count(long long S, int ri) { return (S * mpc::RS_L[ri] + mpc::RS_M[ri] - 1) / mpc::RS_M[ri]; }
 size_t rs_sample_bytes(int fmt) { return fmt == MP_PCM_S16 ? 2 : 4; }
+// samples the stretch makes of n_frames frames: Ls = ceil(Lin 100 / speed_pct)
+long long tsm_count(int n_frames, int speed_pct) { return ((long long)n_frames * mpc::HOP * 100 + speed_pct - 1) / speed_pct; }
 
 // I0 by its power series, sum ((x / 2)^k / k!)^2 (x <= 9: below 1e-17 of the sum after 40 terms)
 double rs_i0(double x) {
@@ -1901,11 +2093,42 @@ struct PcmCtx {
     mp_codec_stream *st;           // the stream whose lanes the chunks are (null: stateless)
     std::vector<mpc::RsChunk> ch;  // [chunk]
     size_t ostride = 0;            // samples per chunk row: the call's largest nout, up to a multiple of 8
+    // the stretch in front of the resampler (one stateless chunk; speed 100: none): the chunk's N is Ls
+    int speed = 100, tsm_M = 0;
 };
+
+// the stretch's side of pcm_prepare: the weights (include/magpie_hip.h), in double, stored as f32;
+// the stretched waveform and the starts
+int tsm_prepare(mp_codec *c, PcmCtx &px) {
+    using namespace mpc;
+    if (!c->tsm_w) {
+        std::vector<float> w(2 * TSM_H);
+        for (int i = 0; i < TSM_H; ++i) {
+            const double s = sin(M_PI * (i + 0.5) / (2 * TSM_H));
+            w[i] = (float)(s * s);
+            w[TSM_H + i] = (float)(1.0 - s * s);
+        }
+        CHK(c->tsm_table.bytes(&c->tsm_w, w.size() * 4));
+        CHK(hipMemcpy(c->tsm_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    }
+    const size_t Ls = (size_t)px.ch[0].N, M = (size_t)px.tsm_M;
+    if (Ls > c->tsm_y_cap || M > c->tsm_starts_cap) {
+        c->tsm_mem.clear();
+        c->tsm_y_cap = c->tsm_starts_cap = 0;
+        CHK(c->tsm_mem.get(&c->tsm_y, Ls));  // (the resampler's 16-byte loads stay inside N)
+        CHK(c->tsm_mem.bytes(&c->tsm_starts, M * 4));
+        c->tsm_y_cap = Ls;
+        c->tsm_starts_cap = M;
+    }
+    CHK(c->tsm_starts_pin.reserve(M * 4));
+    return MP_OK;
+}
 
 // before the sequence: the table, the buffers, the chunk descriptors up
 int pcm_prepare(mp_codec *c, PcmCtx &px) {
     if (int rc = rs_table(c, px.ri)) return rc;
+    if (px.speed != 100)
+        if (int rc = tsm_prepare(c, px)) return rc;
     const size_t nchunk = px.ch.size();
     int most = 0;
     for (const mpc::RsChunk &d : px.ch) most = std::max(most, d.nout);
@@ -1939,10 +2162,22 @@ template <int FMT> void launch_resample(int ri, const mpc::RsP &p, dim3 grid, hi
     }
 }
 
-// behind the sequence: c->audio [chunk][F * 1024] -> c->rs_out
+// behind the sequence, in front of the resampler: c->audio [F * 1024] -> c->tsm_y [Ls], c->tsm_starts [M]
+int tsm_run(mp_codec *c, int F, const PcmCtx &px) {
+    mpc::TsmP p{};
+    p.x = c->audio; p.w = c->tsm_w; p.y = c->tsm_y; p.starts = c->tsm_starts;
+    p.Lin = F * mpc::HOP; p.Ls = px.ch[0].N; p.M = px.tsm_M; p.speed = px.speed;
+    hipLaunchKernelGGL(mpc::tsm_kernel, dim3(1), dim3(mpc::TSM_WG), 0, c->stream, p);
+    CHK(hipGetLastError());
+    return MP_OK;
+}
+
+// behind the sequence: c->audio [chunk][F * 1024] (stretched: c->tsm_y) -> c->rs_out
 int pcm_run(mp_codec *c, int F, const PcmCtx &px) {
     mpc::RsP p{};
-    p.x = c->audio; p.h = c->rs_h[px.ri]; p.ch = c->rs_desc; p.out = c->rs_out;
+    if (px.speed != 100)
+        if (int rc = tsm_run(c, F, px)) return rc;
+    p.x = px.speed != 100 ? c->tsm_y : c->audio; p.h = c->rs_h[px.ri]; p.ch = c->rs_desc; p.out = c->rs_out;
     p.hist = px.st ? px.st->rs_hist : nullptr;
     p.nlanes = px.st ? px.st->lanes : 0;
     p.Tin = F * mpc::HOP;
@@ -1983,6 +2218,8 @@ int decode_call(mp_codec *c, int nchunk, int F, size_t codes_extra, StreamCtx *s
                            hipMemcpyDeviceToHost, c->stream));
     else
         CHK(hipMemcpyAsync(c->audio_pin.p, c->audio, nsamp * 4, hipMemcpyDeviceToHost, c->stream));
+    if (px && px->speed != 100)
+        CHK(hipMemcpyAsync(c->tsm_starts_pin.p, c->tsm_starts, (size_t)px->tsm_M * 4, hipMemcpyDeviceToHost, c->stream));
     CHK(hipStreamSynchronize(c->stream));
     if (!px) memcpy(audio_out, c->audio_pin.p, nsamp * 4);
     CHK(hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
@@ -2212,22 +2449,41 @@ int64_t mp_hip_pcm_samples(int n_frames, int rate) {
 
 int mp_hip_codec_decode_pcm(mp_codec *c, const int32_t *codes, int n_frames, int rate, int format, void *out,
                             int64_t cap, int64_t *n_out) {
+    return mp_hip_codec_decode_pcm_speed(c, codes, n_frames, 100, rate, format, out, cap, n_out, nullptr);
+}
+
+int64_t mp_hip_tsm_samples(int n_frames, int speed_pct, int rate) {
+    const int ri = rs_rate_index(rate);
+    return ri < 0 || n_frames < 0 || speed_pct < 50 || speed_pct > 200 ? MP_ERR_ARG : rs_count(tsm_count(n_frames, speed_pct), ri);
+}
+
+int mp_hip_codec_decode_pcm_speed(mp_codec *c, const int32_t *codes, int n_frames, int speed_pct, int rate, int format,
+                                  void *out, int64_t cap, int64_t *n_out, int32_t *starts) {
     if (!c) return MP_ERR_ARG;
     if (!codes || !out || n_frames < 1) { c->err = "pcm: invalid arguments"; return MP_ERR_ARG; }
     const int ri = pcm_check(c, rate, format);
     if (ri < 0) return ri;
-    const long long need = rs_count((long long)n_frames * mpc::HOP, ri);
-    if (cap < need || need > INT32_MAX) {
+    if (speed_pct < 50 || speed_pct > 200) {
+        c->err = "pcm: speed " + std::to_string(speed_pct) + " % is not in 50..200";
+        return MP_ERR_ARG;
+    }
+    // Ls and everything the kernels index (the windows reach a_m + 1280 <= Lin + 1282) stay in an int
+    const long long Ls = tsm_count(n_frames, speed_pct), need = rs_count(Ls, ri);
+    if (cap < need || need > INT32_MAX || Ls > INT32_MAX - 4096 || n_frames > (INT32_MAX - 4096) / mpc::HOP) {
         c->err = "pcm: out holds " + std::to_string(cap) + " samples, " + std::to_string(n_frames) + " frames at " +
-                 std::to_string(rate) + " Hz are " + std::to_string(need);
+                 std::to_string(rate) + " Hz" + (speed_pct != 100 ? " and " + std::to_string(speed_pct) + " % speed" : "") +
+                 " are " + std::to_string(need);
         return MP_ERR_ARG;
     }
     CHK(hipSetDevice(c->device));
-    PcmCtx px{ri, format, nullptr, {mpc::RsChunk{0, 0, n_frames * mpc::HOP, (int)need, -1, 0}}};
+    PcmCtx px{ri, format, nullptr, {mpc::RsChunk{0, 0, (int)Ls, (int)need, -1, 0}}};
+    px.speed = speed_pct;
+    px.tsm_M = (int)((Ls + mpc::TSM_H - 1) / mpc::TSM_H);
     const size_t ncodes = (size_t)8 * n_frames;
     if (int rc = decode_call(c, 1, n_frames, 0, nullptr, nullptr, [&](int32_t *hc) { memcpy(hc, codes, ncodes * 4); }, &px))
         return rc;
     memcpy(out, c->rs_out_pin.p, (size_t)need * rs_sample_bytes(format));
+    if (starts && speed_pct != 100) memcpy(starts, c->tsm_starts_pin.p, (size_t)px.tsm_M * 4);
     if (n_out) *n_out = need;
     return MP_OK;
 }

@@ -135,6 +135,8 @@ SYMBOLS = [
     ("mp_hip_pcm_samples", ctypes.c_int64, [_I, _I]),
     ("mp_hip_codec_decode_pcm", _I, [_P, _P, _I, _I, _I, _P, ctypes.c_int64, _P]),
     ("mp_hip_codec_stream_decode_pcm", _I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_int64, _P]),
+    ("mp_hip_tsm_samples", ctypes.c_int64, [_I, _I, _I]),
+    ("mp_hip_codec_decode_pcm_speed", _I, [_P, _P, _I, _I, _I, _I, _P, ctypes.c_int64, _P, _P]),
 ]
 
 PCM_F32, PCM_S16 = 0, 1  # MP_PCM_*: the sample formats of the decode_pcm calls
@@ -145,13 +147,19 @@ def pcm_samples(n_frames: int, rate: int) -> int:
     """Samples n_frames codec frames yield at `rate` Hz (mp_hip_pcm_samples); < 0: not a PCM rate."""
     return int(load_library().mp_hip_pcm_samples(n_frames, rate))
 
+
+def tsm_samples(n_frames: int, speed_pct: int, rate: int) -> int:
+    """The same at speed_pct percent of the model's speaking rate (mp_hip_tsm_samples); < 0: not a PCM
+    rate or a speed outside 50..200."""
+    return int(load_library().mp_hip_tsm_samples(n_frames, speed_pct, rate))
+
 # entry points added after round 4: absent from the A/B baseline libraries
 OPTIONAL = {"mp_hip_encode_text", "mp_hip_decode_queue", "mp_hip_codec_stream_create", "mp_hip_codec_stream_decode",
             "mp_hip_codec_stream_reset", "mp_hip_codec_stream_free", "mp_hip_set_stream_codec_mode",
             "mp_hip_codec_stream_decode_ragged", "mp_hip_decode_queue_stream", "mp_hip_set_cfg",
             "mp_hip_get_trace_uncond", "mp_hip_set_attn_prior", "mp_hip_get_alignment",
             "mp_hip_alignment_shape", "mp_hip_pcm_samples", "mp_hip_codec_decode_pcm", "mp_hip_codec_stream_decode_pcm",
-            "mp_hip_set_sampling"}
+            "mp_hip_set_sampling", "mp_hip_tsm_samples", "mp_hip_codec_decode_pcm_speed"}
 
 _lib = None
 
@@ -735,21 +743,33 @@ class Codec:
             raise MagpieError(f"{_ERRS.get(rc, rc)}: {self.lib.mp_hip_codec_error(self.h).decode(errors='replace')}")
         return out
 
-    def decode_pcm(self, codes_cb_major: np.ndarray, rate: int, fmt: int = PCM_S16, cap: Optional[int] = None) -> np.ndarray:
+    def decode_pcm(self, codes_cb_major: np.ndarray, rate: int, fmt: int = PCM_S16, cap: Optional[int] = None,
+                   speed_pct: int = 100, return_starts: bool = False):
         """decode, resampled on the device to `rate` Hz (8000, 16000, 22050, 24000, 44100, 48000)
         and delivered as fmt (PCM_F32, PCM_S16): mp_hip_codec_decode_pcm. cap: the output
-        buffer's samples (default: what the decode yields)."""
+        buffer's samples (default: what the decode yields). speed_pct (50..200) other than 100: the
+        waveform time-stretched on the device first, at its own pitch (mp_hip_codec_decode_pcm_speed);
+        return_starts: (samples, the stretch's segment starts p_m as int32; empty at 100)."""
         codes = np.ascontiguousarray(codes_cb_major, np.int32)
         assert codes.ndim == 2 and codes.shape[0] == 8
         F = codes.shape[1]
+        plain = speed_pct == 100 and not return_starts  # the call as it was
         if cap is None:
-            cap = max(pcm_samples(F, rate), 0)
+            cap = max(pcm_samples(F, rate) if plain else tsm_samples(F, speed_pct, rate), 0)
         out = np.zeros(cap, _PCM_DTYPE.get(fmt, np.float32))
         n = ctypes.c_int64(0)
-        rc = self.lib.mp_hip_codec_decode_pcm(self.h, codes.ctypes.data, F, rate, fmt, out.ctypes.data, cap, ctypes.byref(n))
+        # M = ceil(Ls / 512) starts of a stretch the library accepts (it refuses the other speeds)
+        Ls = -(-F * 1024 * 100 // speed_pct) if speed_pct != 100 and 50 <= speed_pct <= 200 else 0
+        M = -(-Ls // 512)
+        starts = np.zeros(M, np.int32)
+        if plain:
+            rc = self.lib.mp_hip_codec_decode_pcm(self.h, codes.ctypes.data, F, rate, fmt, out.ctypes.data, cap, ctypes.byref(n))
+        else:
+            rc = self.lib.mp_hip_codec_decode_pcm_speed(self.h, codes.ctypes.data, F, speed_pct, rate, fmt, out.ctypes.data,
+                                                        cap, ctypes.byref(n), starts.ctypes.data if M else None)
         if rc != MP_OK:
             raise MagpieError(f"{_ERRS.get(rc, rc)}: {self.lib.mp_hip_codec_error(self.h).decode(errors='replace')}")
-        return out[:n.value]
+        return (out[:n.value], starts) if return_starts else out[:n.value]
 
     def last_ms(self) -> float:
         ms = ctypes.c_float()

@@ -5,7 +5,9 @@
 // synthesis, magpie.cpp:4843-4863), --bf16 (bf16 decode projections), --seed,
 // --continuous-codec (the codec carries its conv state from chunk to chunk: the chunks'
 // audio is one decode of all the frames; with --stream, of each sentence's frames),
-// --sample-rate (the chunks resampled and converted to 16-bit on the device: the PCM calls).
+// --sample-rate (the chunks resampled and converted to 16-bit on the device: the PCM calls),
+// --speed (the utterance time-stretched on the device at its own pitch, in one PCM call).
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +48,10 @@ void usage(const char *prog) {
             "                       chunks are resampled and converted to 16-bit on the device; a rate\n"
             "                       other than 22050 implies --continuous-codec (the filter spans the\n"
             "                       chunks). Default: 22050, converted on the host. Not with --stream.\n"
+            "  --speed S            speaking rate, 0.5 to 2.0 times the model's (whole percent), at the voice's\n"
+            "                       own pitch: the utterance's frames are decoded in one call, time-stretched\n"
+            "                       on the device and delivered at --sample-rate (22050 without it).\n"
+            "                       Not with --stream.\n"
             "  -q, --quiet          minimal output\n"
             "  -h, --help           this help\n",
             prog);
@@ -98,6 +104,7 @@ int main(int argc, char **argv) {
     int speaker = 0, top_k = 80;
     float temp = 0.7f, cfg_scale = 0.f, prior_eps = 0.f, top_p = 1.f, min_p = 0.f;
     int prior_w = 5, prior_start = 0, sample_rate = -1;  // -1: no --sample-rate
+    int speed_pct = -1;                                  // -1: no --speed
     unsigned long long seed = 0;
     bool quiet = false, stream = false, bf16 = false, continuous = false;
     for (int i = 1; i < argc; ++i) {
@@ -128,6 +135,7 @@ int main(int argc, char **argv) {
         else if (a == "--continuous-codec") continuous = true;
         else if (a == "--bf16") bf16 = true;
         else if (a == "--sample-rate") sample_rate = atoi(val("--sample-rate"));
+        else if (a == "--speed") speed_pct = (int)lround(atof(val("--speed")) * 100.0);
         else if (a == "-q" || a == "--quiet") quiet = true;
         else {
             fprintf(stderr, "Unknown option: %s\n", argv[i]);
@@ -149,6 +157,16 @@ int main(int argc, char **argv) {
         fprintf(stderr, "Error: --sample-rate does not apply to --stream\n");
         return 1;
     }
+    const bool speed_out = speed_pct != -1;
+    if (speed_out && (speed_pct < 50 || speed_pct > 200)) {
+        fprintf(stderr, "Error: --speed must be between 0.5 and 2.0\n");
+        return 1;
+    }
+    if (speed_out && stream) {
+        fprintf(stderr, "Error: --speed does not apply to --stream\n");
+        return 1;
+    }
+    if (speed_out && !pcm_out) sample_rate = 22050;
     if (bf16) setenv("MAGPIE_WEIGHTS", "bf16", 1);
     magpie_context *ctx = magpie_init(model);
     if (!ctx) {
@@ -193,17 +211,30 @@ int main(int argc, char **argv) {
             const std::vector<int32_t> codes = magpie_synthesize_codes_graph_reuse(ctx, tokens.data(), (int)tokens.size());
             const int n = (int)codes.size() / 8;
             if (codes.empty()) rc = 1;
+            if (rc == 0 && speed_out) {  // --speed: every frame in one call, codebook-major
+                std::vector<int32_t> cb((size_t)8 * n);
+                for (int t = 0; t < n; ++t)
+                    for (int k = 0; k < 8; ++k) cb[(size_t)k * n + t] = codes[(size_t)t * 8 + k];
+                int64_t got = 0;
+                pcm.resize((size_t)mp_hip_tsm_samples(n, speed_pct, sample_rate));
+                if (mp_hip_codec_decode_pcm_speed(codec->dev, cb.data(), n, speed_pct, sample_rate, MP_PCM_S16, pcm.data(),
+                                                  (int64_t)pcm.size(), &got, nullptr) != MP_OK) {
+                    fprintf(stderr, "Error: %s\n", mp_hip_codec_error(codec->dev));
+                    rc = 1;
+                }
+                pcm.resize((size_t)got);
+            }
             magpie_codec_stream *cs = continuous && !pcm_out ? magpie_codec_stream_init(codec) : nullptr;
             if (continuous && !pcm_out && !cs) rc = 1;
             // --sample-rate: the same chunks through the PCM calls, on one stream lane when the codec
             // is continuous or the rate's filter has to span the chunks (any rate but 22050)
             mp_codec_stream *ps = nullptr;
-            if (rc == 0 && pcm_out && (continuous || sample_rate != 22050) &&
+            if (rc == 0 && pcm_out && !speed_out && (continuous || sample_rate != 22050) &&
                 mp_hip_codec_stream_create(codec->dev, 1, &ps) != MP_OK)
                 rc = 1;
             // stateless 32-frame codec chunks, frame-major -> codebook-major (magpie-tts.cpp:181-206);
             // --continuous-codec: the same chunks through one stream lane
-            for (int c0 = 0; rc == 0 && c0 < n; c0 += 32) {
+            for (int c0 = 0; rc == 0 && !speed_out && c0 < n; c0 += 32) {
                 const int f = std::min(32, n - c0);
                 std::vector<int32_t> cb((size_t)8 * f);
                 for (int t = 0; t < f; ++t)
@@ -233,14 +264,14 @@ int main(int argc, char **argv) {
             mp_hip_codec_stream_free(ps);
         }
     }
-    if (rc == 0 && !(pcm_out ? write_wav(out, pcm, sample_rate) : write_wav(out, audio, 22050))) {
+    if (rc == 0 && !(pcm_out || speed_out ? write_wav(out, pcm, sample_rate) : write_wav(out, audio, 22050))) {
         fprintf(stderr, "Error: Failed to write %s\n", out);
         rc = 1;
     }
     if (rc == 0) {
         if (quiet) printf("%s\n", out);
         else fprintf(stderr, "Done! Generated %.2f seconds of audio.\n",
-                     pcm_out ? pcm.size() / (double)sample_rate : audio.size() / 22050.0);
+                     pcm_out || speed_out ? pcm.size() / (double)sample_rate : audio.size() / 22050.0);
     }
     magpie_codec_free(codec);
     magpie_free(ctx);
